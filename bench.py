@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""bench.py -- MPC QP solves/sec (horizon=10, 2 contacts) of the HIP path, with roofline and CPU-baseline legs.
+"""bench.py -- MPC QP solves/sec (horizon=10, 2 contacts) of the HIP path, with roofline and CPU-baseline legs (--full).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            # plain run: the headline figure only
+    python bench.py --gpus N --steps K --warmup W --dump-outputs DIR   # ... and the last step's outputs as DIR/<name>.npy
+    python bench.py --gpus N --steps K --warmup W --full     # + parity, roofline, side configs, CPU baseline
     python bench.py --gpus 8 --gait walking                  # BASELINE config 3: 8 x 8 192 walking sweep
     python bench.py --gpus 4 --contacts 3 --batch 2048       # BASELINE config 5: 4 x 2 048 three-contact QPs
     python bench.py --gpus N --exchange none                 # diagnosis: N ranks, NO collective -- per-rank kernel-only rates
@@ -25,9 +27,14 @@ instances whose packed records already live in HBM (consecutive steps alternate 
 blocks, --streams 1 for strictly serial launches); for N > 1 every rank owns a contiguous shard of the global batch
 (weak scaling, per-GPU batch fixed) and the step ends with the all_gather (RCCL) of the solved forces.
 The timed region is K steps between barrier + synchronize on both sides, max over ranks; it is repeated --windows times
-(default 5) and `value` / `ms_per_step` are the MEDIAN window's, with every window's value, min and max in `windows`.
-Rank 0 prints ONE JSON line.  Workload = the case BASELINE.json's metric string names: randomized 2-contact
+(default 1, 5 with --full) and `value` / `ms_per_step` are the MEDIAN window's, with every window's value, min and max in
+`windows`.  Rank 0 prints ONE JSON line.  Workload = the case BASELINE.json's metric string names: randomized 2-contact
 (standing gait) instances, horizon 10 -> 120 x 160 QPs (SURVEY.md section 8d "metric_2contact").
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given
+and prints the line.  Everything else -- the exchange self-check, the single-stream and dispatch-order reruns, the HIP-event
+kernel time and the roofline figures built on it, the parity check against the oracle, the side configs and the CPU
+baseline -- runs only with --full.  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -50,6 +57,30 @@ MFLOP_PER_SOLVE = {10: 3.744, 20: 29.952}  # 2*(12h)^2*(13h) dense B'SB contract
 HBM_PEAK_GBS = 8000.0                      # MI355X_MICROARCH.md: 8 TB/s spec
 MFMA_F32_PEAK_TF = 157.3
 FP64_VALU_PEAK_TF = 78.6                   # vector fp64 = half the fp32 vector rate of MI355X_MICROARCH.md (157.3 / 2)
+DUMP_BYTES = 64 << 20                      # --dump-outputs: every rank's files together stay below this
+
+
+def dump_outputs(outdir: str, arrays: dict, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: `arrays` (one row per instance) as <outdir>/<name>.npy, float32 kept, every other type as float64 (a
+    32-bit status word is exact in it).  When this rank's share of DUMP_BYTES cannot hold every row, a fixed sample of rows
+    (seed 0) is written instead, its instance indices in rows.npy (an unsampled dump removes a rows.npy left in DIR by an earlier
+    one).  N > 1 ranks: each writes its own shard as rank<r>_<name>.npy; rank<r>_rows.npy then holds indices within that shard."""
+    os.makedirs(outdir, exist_ok=True)
+    arrs = {k: np.asarray(v) for k, v in arrays.items()}
+    arrs = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrs.items()}
+    n = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(v.nbytes // max(1, n) for v in arrs.values())
+    budget = DUMP_BYTES // world - 4096 * (len(arrs) + 1)  # (npy headers)
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(1, budget // (row_bytes + 8)), replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    stale = os.path.join(outdir, prefix + "rows.npy")
+    if "rows" not in arrs and os.path.exists(stale):
+        os.remove(stale)
+    for k, v in arrs.items():
+        np.save(os.path.join(outdir, prefix + k + ".npy"), np.ascontiguousarray(v))
 
 
 def cpu_worker(path: str, horizon: int, first: int, count: int, kind: str = "reference", repeat: int = 1) -> None:
@@ -314,6 +345,8 @@ def bench_builder(args, torch, local_rank) -> None:
     e1.record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # the last step's outputs: clamped world_position_desired and the body-frame f_ff
+        dump_outputs(args.dump_outputs, {"world_position_desired": d_wpd.cpu().numpy(), "f_ff": d_fff.cpu().numpy()})
     kms = e0.elapsed_time(e1) / args.steps
     stride = mpc.stride
     bytes_per = 408 + stride + 16 + 48 * h + 72 + 96
@@ -536,9 +569,15 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks = GPUs of the job.  Default: WORLD_SIZE when launched under torchrun, else 1")
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--windows", type=int, default=None,
                     help="the timed region (K steps between barrier + synchronize) is repeated this many times; value / ms_per_step "
-                         "are the median window's, every window is in the line")
+                         "are the median window's, every window is in the line.  Default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: exchange self-check, single-stream and dispatch-order reruns, HIP-event kernel time "
+                         "and roofline figures, parity against the oracle (--check), side configs and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (forces float32, status words "
+                         "as float64; a fixed seeded sample of rows if they exceed 64 MB)")
     ap.add_argument("--bringup-timeout", type=float, default=120.0,
                     help="seconds a rank may take to bring up its process group and first collective before it prints its "
                          "diagnostics and exits 3")
@@ -578,7 +617,7 @@ def main() -> None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
-    args.windows = max(1, args.windows)
+    args.windows = max(1, args.windows if args.windows is not None else (5 if args.full else 1))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started without torchrun: N ranks all the same (never a silent one-GPU run that prints n_gpus = 1)
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -710,6 +749,54 @@ def main() -> None:
     if args.windows % 2 == 0:  # (the median of an even count is no window's own time: take the upper middle one)
         elapsed = sorted(window_s)[args.windows // 2]
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:  # what the last timed step computed: its launch stream's output block (before anything else runs)
+        klast = (nstep[0] - 1) % nstream
+        dump_outputs(args.dump_outputs, {"forces": d_forces_l[klast].cpu().numpy(),
+                                         "status": d_status_l[klast].cpu().numpy().view(np.uint32)}, rank, world)
+
+    metric = ("MPC QP solves/sec (horizon=10, 2 contacts)" if (h == 10 and args.gait == "standing" and nc == 2)
+              else f"MPC QP solves/sec (horizon={h}, gait={args.gait}, {nc} contacts)")
+    config = {"workload": (f"{'2-contact standing' if args.gait == 'standing' else args.gait} randomized MPC ticks, " if nc == 2 else
+                           f"3-contact (two feet + hand, BASELINE config 5 extension) randomized MPC ticks, feet {args.gait}, ") +
+                          f"horizon {h}, reduced QP up to {n_red}x{n_red // 6 * 8}; records and forces device-resident in/out; "
+                          "two batches of the same instances one 5 ms tick apart, solved alternately",
+              "batch_per_gpu": B, "global_batch": world * B, "horizon": h, "contacts": nc,
+              "exchange_backend": (("none (--exchange none: NO data-path collective; barriers and the max over ranks on gloo)" if args.exchange == "none" else
+                                    args.backend + (" (TEST transport: host-staged, ranks may share a GPU)" if args.backend == "gloo" else " (RCCL)"))
+                                   if (world > 1 or args.force_exchange) else None),
+              "launch_streams": nstream,
+              "world": world, "launcher": ("bench.py re-executed itself under torch.distributed.run (--gpus N without torchrun)"
+                                           if os.environ.get("HMPC_BENCH_SELF_LAUNCHED") else
+                                           ("torch.distributed.run (external)" if "TORCHELASTIC_RUN_ID" in os.environ or world > 1 else "python (single process)")),
+              "devices_visible": ndev,
+              "rccl_version": rccl_version(torch) if (world > 1 or args.force_exchange) else None,
+              "parallelism": ((f"batch shards x{world}, all_gather of "
+                               f"{'step-0 wrench + status (overlapped with the next solve)' if xch is not None else 'all forces'}")
+                              if args.exchange != "none" else
+                              f"batch shards x{world}, NO exchange (diagnostic mode: every rank solves its shard, nothing is gathered)")
+              if world > 1 else ("single GPU" + (", exchange code path forced on (group of one)" if xch is not None else ""))}
+    headline = {
+        "metric": metric, "value": world * B * args.steps / elapsed, "unit": "QP solves/s", "n_gpus": n_gpus, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 assembly / f64 solve", "data": "synthetic", "config": config,
+        "windows": {"n": args.windows, "steps_each": args.steps,
+                    "values": [world * B * args.steps / w for w in window_s],
+                    "value_min": world * B * args.steps / max(window_s), "value_max": world * B * args.steps / min(window_s),
+                    "spread": (max(window_s) - min(window_s)) / elapsed,
+                    "note": "the timed region (K steps between barrier + synchronize, max over ranks) repeated n times back to "
+                            "back; value / ms_per_step are the median window's"}}
+
+    def finish():
+        for m in mpcs:
+            m.close()
+        if world > 1 or args.force_exchange:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # plain run: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        return finish()
 
     exchange_check = None
     if xch is not None:  # what the last posted exchange delivered == this rank's own slice of the last step's outputs
@@ -792,8 +879,6 @@ def main() -> None:
     n_fail_all = sum(sm["failed"] for sm in summaries)
 
     if rank == 0:
-        total = world * B * args.steps
-        value = total / elapsed
         if nc == 2:
             bps = BYTES_PER_SOLVE.get(h, (54 + 12 * h) * 4 + 2 * h + 48 * h + 4)
             mfl = MFLOP_PER_SOLVE.get(h, 2 * (12 * h) ** 2 * (13 * h) / 1e6)
@@ -828,30 +913,8 @@ def main() -> None:
         fp64_flop = n_red * n_red * (n_red + 1) + it_mean * 4.0 * n_red * n_red
         fp64_tf = B * fp64_flop / (kernel_ms * 1e-3) / 1e12
         out = {
-            "metric": "MPC QP solves/sec (horizon=10, 2 contacts)" if (h == 10 and args.gait == "standing" and nc == 2)
-                      else f"MPC QP solves/sec (horizon={h}, gait={args.gait}, {nc} contacts)",
-            "value": value, "unit": "QP solves/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 assembly / f64 solve", "data": "synthetic",
-            "config": {"workload": (f"{'2-contact standing' if args.gait == 'standing' else args.gait} randomized MPC ticks, " if nc == 2 else
-                                    f"3-contact (two feet + hand, BASELINE config 5 extension) randomized MPC ticks, feet {args.gait}, ") +
-                                   f"horizon {h}, reduced QP up to {n_red}x{n_red // 6 * 8}; records and forces device-resident in/out; "
-                                   "two batches of the same instances one 5 ms tick apart, solved alternately",
-                       "batch_per_gpu": B, "global_batch": world * B, "horizon": h, "contacts": nc,
-                       "exchange_backend": (("none (--exchange none: NO data-path collective; barriers and the max over ranks on gloo)" if args.exchange == "none" else
-                                             args.backend + (" (TEST transport: host-staged, ranks may share a GPU)" if args.backend == "gloo" else " (RCCL)"))
-                                            if (world > 1 or args.force_exchange) else None),
-                       "launch_streams": nstream,
-                       "world": world, "launcher": ("bench.py re-executed itself under torch.distributed.run (--gpus N without torchrun)"
-                                                    if os.environ.get("HMPC_BENCH_SELF_LAUNCHED") else
-                                                    ("torch.distributed.run (external)" if "TORCHELASTIC_RUN_ID" in os.environ or world > 1 else "python (single process)")),
-                       "devices_visible": ndev, "rank_devices": [sm["device"] for sm in summaries],
-                       "rccl_version": rccl_version(torch) if (world > 1 or args.force_exchange) else None,
-                       "parallelism": ((f"batch shards x{world}, all_gather of "
-                                        f"{'step-0 wrench + status (overlapped with the next solve)' if xch is not None else 'all forces'}")
-                                       if args.exchange != "none" else
-                                       f"batch shards x{world}, NO exchange (diagnostic mode: every rank solves its shard, nothing is gathered)")
-                       if world > 1 else ("single GPU" + (", exchange code path forced on (group of one)" if xch is not None else "")),
+            **headline,
+            "config": {**config, "rank_devices": [sm["device"] for sm in summaries],
                        **({"exchange_selfcheck_ok": exchange_check} if exchange_check is not None else {})},
             "roofline": {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
@@ -862,12 +925,6 @@ def main() -> None:
                                  "active-set iteration inside one workgroup (LDS/VALU fp64 latency)"},
             "roofline_mfma": {"bound": "mfma", "achieved": ach_tf, "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s",
                               "frac": ach_tf / MFMA_F32_PEAK_TF, "algorithmic_mflop_per_solve": mfl},
-            "windows": {"n": args.windows, "steps_each": args.steps,
-                        "values": [world * B * args.steps / w for w in window_s],
-                        "value_min": world * B * args.steps / max(window_s), "value_max": world * B * args.steps / min(window_s),
-                        "spread": (max(window_s) - min(window_s)) / elapsed,
-                        "note": "the timed region (K steps between barrier + synchronize, max over ranks) repeated n times back to "
-                                "back; value / ms_per_step are the median window's"},
             "single_stream": {"value": B * args.steps / single_stream_s, "ms_per_step": 1e3 * single_stream_s / args.steps,
                               "note": "this rank's K passes launched back to back on one stream, no exchange; the headline value "
                                       "alternates two streams (config.launch_streams) so that the partly filled last round of "
@@ -1223,11 +1280,7 @@ def main() -> None:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(fields, h, args.cpu_per_core, target_s=args.cpu_seconds, sweep_s=0.3 * args.cpu_seconds)
         print(json.dumps(out), flush=True)
-    for m in mpcs:
-        m.close()
-    if world > 1 or args.force_exchange:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@
 #      kernel trace + stats and one SQ counter pass each
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/rocprof; rm -rf gpurun_out/rocprof/*; export TMPDIR=/tmp
 O=gpurun_out/rocprof
-CMD="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs --check 0 --streams 1"
+CMD="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-side-configs --check 0 --streams 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- $CMD > $O/kt.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pmc -- $CMD > $O/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pmc -- $CMD > $O/pmc_write.log 2>&1
@@ -17,7 +17,7 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU
 rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_FMA_F SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq2 -o pmc -- $CMD > $O/pmc_sq2.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 --output-format csv -d $O/pmc_f64 -o pmc -- $CMD > $O/pmc_f64.log 2>&1
 # (3) the default two-stream mode, trace only
-rocprofv3 --kernel-trace --output-format csv -d $O/kt2 -o kt2 -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-side-configs --check 0 > $O/kt2.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/kt2 -o kt2 -- python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-side-configs --check 0 > $O/kt2.log 2>&1
 # (4) the other variants
 for CASE in walking_b8192 h20_single_b4096 3contact_b8192 3contact_b2048 h20_double_b2048; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/var_$CASE/kt -o kt -- python scripts/quick_times.py $CASE > $O/var_$CASE.log 2>&1
@@ -36,11 +36,11 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $O/gpu_tests.txt
 # from the PMC passes above first (on this box's copy of the tree; the caller runs the summary again on its own copy)
 ROUND=${1:-r06}
 python scripts/summarize_rocprof.py $ROUND > /dev/null 2>&1
-python bench.py --steps 20 --warmup 3 > $O/bench_standing.json 2> $O/bench.err
-python bench.py --steps 20 --warmup 3 --gait walking --no-cpu-baseline > $O/bench_walking.json 2>> $O/bench.err
-python bench.py --steps 10 --warmup 2 --horizon 20 --gait single --batch 4096 --no-cpu-baseline > $O/bench_h20_single.json 2>> $O/bench.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench_standing.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 3 --gait walking --no-cpu-baseline > $O/bench_walking.json 2>> $O/bench.err
+python bench.py --full --steps 10 --warmup 2 --horizon 20 --gait single --batch 4096 --no-cpu-baseline > $O/bench_h20_single.json 2>> $O/bench.err
 # the N > 1 path launched by bench.py itself (two ranks on the one GPU over the gloo TEST transport), and the refusal of --gpus 8
-python bench.py --gpus 2 --backend gloo --steps 10 --warmup 3 --check 64 > $O/bench_gpus2_gloo.json 2>> $O/bench.err
+python bench.py --full --gpus 2 --backend gloo --steps 10 --warmup 3 --check 64 > $O/bench_gpus2_gloo.json 2>> $O/bench.err
 python bench.py --gpus 8 --steps 1 > /dev/null 2> $O/bench_gpus8_refused.txt; echo "exit code $?" >> $O/bench_gpus8_refused.txt
 find $O -name '*.db' -delete
 find $O -name '*_agent_info.csv' -delete

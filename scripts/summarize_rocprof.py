@@ -77,7 +77,7 @@ def main():
             "correction": "FETCH_SIZE doubled (gfx950 rocprofv3 reports half the bytes of a coalesced stream, "
                           "MI355X_MICROARCH.md section HBM; upper bound for our 4-B/lane burst), WRITE_SIZE as reported; units KB",
             "algorithmic_bytes_per_solve": 1200,
-            "source": "profiles/%s/pmc.csv (separate --pmc passes of: python bench.py --steps 10 --warmup 2 "
+            "source": "profiles/%s/pmc.csv (separate --pmc passes of: python bench.py --full --steps 10 --warmup 2 "
                       "--no-cpu-baseline --no-side-configs --check 0 --streams 1)" % rnd,
         }, open(os.path.join(ROOT, "profiles", "hbm_traffic.json"), "w"), indent=1)
     for r in rows:
@@ -111,7 +111,7 @@ def two_stream_trace(dst):
     d = _hmpc_dispatches(src, 8192 * 128)
     if len(d) < 24:
         return None
-    timed = d[3:23]  # 3 warm-up steps, then the 20 timed ones (bench.py --steps 20 --warmup 3)
+    timed = d[3:23]  # 3 warm-up steps, then the first window's 20 timed ones (bench.py --full --steps 20 --warmup 3)
     with open(os.path.join(dst, "two_stream_kernel_trace.csv"), "w") as fh:
         fh.write("dispatch,stream,start_us,end_us,duration_us,overlap_with_previous_us\n")
         t0 = timed[0][0]
@@ -125,7 +125,7 @@ def two_stream_trace(dst):
     span = (timed[-1][1] - timed[0][0]) / 1e9
     dur = sum(b - a for a, b, _, _ in timed) / len(timed) / 1e6
     nb = timed[0][3]
-    return ("* `two_stream_kernel_trace.csv` (rocprofv3 --kernel-trace of the DEFAULT run, `python bench.py --steps 20 --warmup 3`): "
+    return ("* `two_stream_kernel_trace.csv` (rocprofv3 --kernel-trace of the DEFAULT run, `python bench.py --full --steps 20 --warmup 3`): "
             "the 20 timed dispatches span %.3f ms = **%.3f M solves/s** from the trace alone (%d instances each); a dispatch lasts "
             "%.3f ms on average while a new one starts every %.3f ms -- consecutive dispatches (alternating streams) overlap by "
             "%.3f ms on average: the partly filled last rounds of workgroups of one launch run under the first rounds of the next"
@@ -181,7 +181,7 @@ def write_readme(dst, rnd, means, extra=()):
     """profiles/<round>/README.md generated from the CSV/JSON files next to it -- no hand-typed figures."""
     lines = ["# profiles/%s -- generated by scripts/summarize_rocprof.py from the files in this directory" % rnd, "",
              "Collected with `scripts/gpu_rocprof.sh` (one `gpurun` call; rocprofv3 passes kept separate: kernel trace + "
-             "stats, then one `--pmc` pass per counter group).  Command profiled: `python bench.py --steps 10 --warmup 2 "
+             "stats, then one `--pmc` pass per counter group).  Command profiled: `python bench.py --full --steps 10 --warmup 2 "
              "--no-cpu-baseline --no-side-configs --check 0 --streams 1` (serial launches on one stream, so that per-kernel durations are not stretched by the overlap of the default two-stream mode; 8192 randomized 2-contact h=10 instances per launch, records "
              "resident in HBM).", ""]
     ks = os.path.join(dst, "kernel_stats.csv")

@@ -25,7 +25,7 @@ def test_bench_fails_loudly_without_gpu():
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "2048",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1", "--batch", "2048",
                         "--no-side-configs", "--check", "16", "--cpu-per-core", "8", "--cpu-seconds", "1.5"], capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -71,7 +71,7 @@ def test_bench_torchrun_code_path_on_one_gpu():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1",
                         "--steps", "6", "--warmup", "2", "--batch", "1024", "--no-side-configs", "--check", "8",
-                        "--no-cpu-baseline", "--force-exchange"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-cpu-baseline", "--force-exchange", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -86,7 +86,7 @@ def _torchrun(nproc, port, *bench_args, timeout=900):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", str(nproc), *bench_args], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
+                        "--gpus", str(nproc), "--full", *bench_args], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 alone prints
@@ -144,7 +144,7 @@ def test_bench_gpus_n_launches_n_ranks_by_itself():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4",
-                        "--warmup", "1", "--batch", "1024", "--check", "16"], capture_output=True, text=True, timeout=900,
+                        "--warmup", "1", "--batch", "1024", "--check", "16", "--full"], capture_output=True, text=True, timeout=900,
                        cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -261,3 +261,81 @@ def test_bench_exchange_none_is_a_diagnosable_line_without_any_collective():
     assert d["parity"]["max_rel_force_err_vs_qpoases"] < 1e-4 and d["solver"]["failed_over_all_ranks"] == 0
     assert d["windows"]["n"] == 3 and len(d["windows"]["values"]) == 3
     assert d["windows"]["value_min"] <= d["value"] <= d["windows"]["value_max"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps steps in one window and prints the headline keys without the --full
+    measurements; --dump-outputs writes the last timed step's forces (float32) and status words (float64), the same in a second
+    run with the same arguments, and they are the solution of that step's inputs: with two launch streams, 2 warm-up and 5 timed
+    steps the last step is handle 0's fourth solve, i.e. of the tick batch one 5 ms tick later (bench.py solve_on)."""
+    import numpy as np
+
+    from hector_simulation_amd import interface, records, synthetic
+
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--batch", "1024", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert key in d, key
+        assert d["metric"] == "MPC QP solves/sec (horizon=10, 2 contacts)" and d["unit"] == "QP solves/s"
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["windows"]["n"] == 1 and d["higher_is_better"] is True
+        assert abs(d["value"] - 1024 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-6
+        for key in ("roofline", "parity", "cpu_baseline", "other_configs", "single_stream", "solver"):
+            assert key not in d, key
+        f, s = np.load(out / "forces.npy"), np.load(out / "status.npy")
+        assert f.dtype == np.float32 and f.shape == (1024, 120) and s.dtype == np.float64 and s.shape == (1024,)
+        code = interface.status_code(s.astype(np.uint32))
+        assert set(np.unique(code).tolist()) <= set(interface.STATUS_NAMES) and (code == 0).mean() > 0.99, np.unique(code)
+        dumps.append((f, s))
+    np.testing.assert_array_equal(dumps[0][0], dumps[1][0])
+    np.testing.assert_array_equal(dumps[0][1], dumps[1][1])
+    import bench
+
+    fields, _ = bench.bench_shard(0, 1024, 10, "standing", 2)
+    rec_next = records.pack_records(synthetic.advance_tick(fields, 10, seed=7), 10, 2)
+    ok = np.flatnonzero(code == 0)[:32]
+    ref = oracle.solve_records(np.ascontiguousarray(rec_next[ok]), 10, synthetic.DT_MPC, synthetic.F_MAX)
+    q = ref["q_soln"]
+    err = np.abs(f[ok].astype(np.float64) - q).max(axis=1) / np.maximum(1.0, np.abs(q).max(axis=1))
+    assert ref["n_bad"] == 0 and err.max() < 1e-4, err.max()
+
+
+def test_dump_outputs_types_and_sample_cap(tmp_path, monkeypatch):
+    """dump_outputs keeps float32, widens the rest to float64 (exactly), and above the byte cap writes the same seeded sample of
+    rows every time, with their indices; --full and --dump-outputs are options of the command line."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    f = np.arange(64 * 8, dtype=np.float32).reshape(64, 8)
+    s = (np.arange(64, dtype=np.uint32) << 20) | 0xFFF00
+    bench.dump_outputs(str(tmp_path / "all"), {"forces": f, "status": s})
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "forces.npy"), f)
+    s2 = np.load(tmp_path / "all" / "status.npy")
+    assert s2.dtype == np.float64 and np.array_equal(s2.astype(np.uint32), s)
+    assert not (tmp_path / "all" / "rows.npy").exists()
+    bench.dump_outputs(str(tmp_path / "ranks"), {"forces": f}, rank=1, world=2)
+    assert (tmp_path / "ranks" / "rank1_forces.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4096 + 16 * (32 + 8 + 8))  # room for 16 of the 64 rows
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"cut{k}"), {"forces": f, "status": s})
+    rows = np.load(tmp_path / "cut0" / "rows.npy").astype(np.int64)
+    assert rows.size == 16 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "cut0" / "forces.npy"), f[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "cut1" / "rows.npy"), rows)
+    monkeypatch.undo()  # a later dump that fits into the same DIR leaves no stale rows.npy behind
+    bench.dump_outputs(str(tmp_path / "cut1"), {"forces": f, "status": s})
+    assert not (tmp_path / "cut1" / "rows.npy").exists()
+    np.testing.assert_array_equal(np.load(tmp_path / "cut1" / "forces.npy"), f)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

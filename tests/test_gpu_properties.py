@@ -143,7 +143,7 @@ def test_bench_line_contract():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "1024",
-                          "--no-cpu-baseline", "--no-side-configs", "--check", "4"], capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--no-side-configs", "--check", "4", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
