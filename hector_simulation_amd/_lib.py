@@ -25,7 +25,7 @@ EXPORTS = [
     "hmpc_group_create_ex", "hmpc_group_contacts", "hmpc_group_set_deal", "hmpc_group_deal", "hmpc_group_member_step",
     "hmpc_upload_records_strided_async", "hmpc_set_max_iterations", "hmpc_legacy_set_max_iterations", "hmpc_tick_solve_device", "hmpc_set_dispatch_order",
     "hmpc_set_handover", "hmpc_default_params", "hmpc_set_params", "hmpc_get_params", "hmpc_legacy_set_params", "hmpc_group_set_params",
-    "hmpc_solve_command_sweep", "hmpc_set_instance_mu", "hmpc_group_solve_command_sweep",
+    "hmpc_solve_command_sweep", "hmpc_set_instance_mu", "hmpc_group_solve_command_sweep", "hmpc_debug_handover_slots",
 ]
 
 
@@ -172,6 +172,7 @@ def load():
     L.hmpc_group_download.argtypes = [vp, vp, vp]
     L.hmpc_group_last_error.restype = C.c_char_p
     L.hmpc_debug_phase_cycles.argtypes = [vp, vp]
+    L.hmpc_debug_handover_slots.argtypes = [vp, vp]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

@@ -388,6 +388,17 @@ static int enqueue_reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
   return rc;
 }
 
+// The hand-over slot table must describe the CURRENT solve for the whole batch: the continuation pass resumes instance i from slot i
+// when the table says i and the status word says "working set full" -- an entry an earlier batch left, met by a status word of this
+// solve from a launch that does not rewrite the table (the 60-variable, wide, sweep and external-QP launches; the workgroups of a
+// size-class launch that leave early), would continue the old QP's state against the new record.  Such a solve clears the table
+// first, once, before its first launch (a saving launch after it still writes its own entries); a solve that is ONE launch of a
+// saving variant rewrites every entry itself and gets nothing extra.
+static int invalidate_handover_slots(hmpc_handle *h, hipStream_t stream) {
+  if (h->d_spill_slot && h->batch > 0) HIP_TRY(hipMemsetAsync(h->d_spill_slot, 0xff, (size_t)h->batch * sizeof(int), stream));
+  return HMPC_OK;
+}
+
 // One solve of the current batch, enqueued on `stream` -- what hmpc_solve does and what hmpc_time_solve times:
 //  * widest reduced QP known (host-uploaded records, or hmpc_set_max_reduced_vars >= 0): one launch of the variant
 //    that holds it;
@@ -430,6 +441,8 @@ static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
   o.longest_first = h->order_valid;
   int rc = HMPC_OK;
   if (h->nc == 2 && h->max_stance < 0 && h->d_cls) {
+    rc = invalidate_handover_slots(h, stream);
+    if (rc != HMPC_OK) return rc;
     if (!h->cls_valid) {
       hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, stream, h->d_records,
                          (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
@@ -448,7 +461,10 @@ static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
       rc = launch(h, stream, o);
     }
   } else {
-    rc = launch(h, stream, o);
+    int vi = 0;
+    (void)pick_variant(h, &vi);
+    if (variants()[vi].spill_stride == 0) rc = invalidate_handover_slots(h, stream);
+    if (rc == HMPC_OK) rc = launch(h, stream, o);
   }
   if (rc != HMPC_OK || !repair) return rc;
   LaunchOpt s;
@@ -837,9 +853,13 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   hipStream_t st = (hipStream_t)stream;
   h->last_stream = st;
   const bool small = h->max_stance >= 0 && h->max_stance <= 60;  // single-support sweeps: the 60-variable kernel (six workgroups per CU)
+  // records whose sizes only the device knows (max_stance < 0): every group runs on the sweep variant of its size class, the one
+  // hmpc_solve's size-class launches give its instances -- what keeps the results the bits of hmpc_solve's (a member whose gait
+  // differs from its group's first record's may land in the other launch: it is reported there, never solved)
+  const bool by_class = h->max_stance < 0 && h->d_cls;
   const int vi = small ? V2_SWEEP_60 : V2_SWEEP_120;
   const int groups = h->batch / group_size;
-  const size_t need = (size_t)groups * 36 * (size_t)variants()[vi].nt * sizeof(double);
+  const size_t need = (size_t)groups * 36 * (size_t)variants()[vi].nt * sizeof(double);  // (V2_SWEEP_120 has the wider workgroups)
   if (need > h->sweep_m_bytes) {
     if (h->d_sweep_m) {
       HIP_TRY(hipStreamSynchronize(st));
@@ -852,14 +872,25 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   const bool repair = h->device_repair != 0;
   if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count, 0, 2 * sizeof(unsigned int), st));
   h->order_valid = false, h->order_batch = 0;  // (natural order inside a sweep; the next ordinary solve starts from the predictor)
-  LaunchOpt o;
-  o.variant = vi, o.sweep_k = group_size, o.sweep_phase = 0;
-  int rc = launch(h, st, o);
+  int rc = invalidate_handover_slots(h, st);  // (the sweep variants save nothing)
   if (rc != HMPC_OK) return rc;
-  o.sweep_phase = 1;
-  o.record_flagged = repair;
-  rc = launch(h, st, o);
-  if (rc != HMPC_OK || !repair) return rc;
+  if (by_class && !h->cls_valid) {
+    hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->d_records, (int)h->stride,
+                       h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int pass = 0; pass < (by_class ? 2 : 1); ++pass) {
+    LaunchOpt o;
+    o.variant = by_class ? (pass == 0 ? V2_SWEEP_60 : V2_SWEEP_120) : vi, o.sweep_k = group_size, o.sweep_phase = 0;
+    if (by_class) o.cls_lo = (pass == 0) ? 0 : 11, o.cls_hi = (pass == 0) ? 10 : 255;  // (the classes of enqueue_solve's h <= 10 launches)
+    rc = launch(h, st, o);
+    if (rc != HMPC_OK) return rc;
+    o.sweep_phase = 1;
+    o.record_flagged = repair;
+    rc = launch(h, st, o);
+    if (rc != HMPC_OK) return rc;
+  }
+  if (!repair) return HMPC_OK;
   // whatever a sweep flags is repaired as an independent instance (its record is complete): the cold safe pass
   LaunchOpt s;
   s.d_index_list = h->d_flag_list;
@@ -1141,12 +1172,28 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
   h->d_ext_H = dH, h->d_ext_g = dg, h->d_ext_Fc = dF, h->ext_ld = ld;
   LaunchOpt xo;
   xo.carry_wset = false;
-  const int rc = launch(h, h->last_stream, xo);
+  int vi = 0;
+  (void)pick_variant(h, &vi);
+  int rc = variants()[vi].spill_stride == 0 ? invalidate_handover_slots(h, h->last_stream) : HMPC_OK;
+  if (rc == HMPC_OK) rc = launch(h, h->last_stream, xo);
   hipError_t e = hipStreamSynchronize(h->last_stream);
   h->d_ext_H = h->d_ext_g = h->d_ext_Fc = nullptr;
   h->ext_ld = 0;
   if (rc != HMPC_OK) return rc;
   HIP_TRY(e);
+  return HMPC_OK;
+}
+
+int hmpc_debug_handover_slots(hmpc_handle *h, int *slots) {
+  if (!h || !slots) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  if (!h->d_spill_slot) {  // (no saving variant has run on this handle: nothing was ever handed over)
+    for (int i = 0; i < h->batch; ++i) slots[i] = -1;
+    return HMPC_OK;
+  }
+  HIP_TRY(hipMemcpy(slots, h->d_spill_slot, (size_t)h->batch * sizeof(int), hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
 

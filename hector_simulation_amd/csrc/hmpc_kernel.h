@@ -1791,8 +1791,12 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   // the safe-pass variants (working set = variable count, scalar sweeps): they also answer a Hessian that is not positive definite
   // the way the reference's qpOASES run does (KernelArgs::reg_step)
   constexpr bool REGULARISES = !ASM_ONLY && (SM::EGLOBAL || (QCAP >= NMAX && NMAX >= 120));
-  if constexpr (REGULARISES) {
+  // every variant launched over a list of flagged instances (the safe ones, the 140-row three-contact one among them, and the
+  // continuation ones) honours the list protocol; the fast variants never see it and do not compile it
+  constexpr bool LISTED = !ASM_ONLY && (REGULARISES || CONT || (NC == 3 && QCAP >= 140));
+  if constexpr (LISTED) {
     if (args.reg_step) {  // a regularisation step: only the instances the step before it left for this one
+      if constexpr (!REGULARISES) return;  // (a variant that does not regularise leaves the instance as it is)
       const uint32_t c0 = args.status[inst] & 0xffu;
       if (c0 != (uint32_t)(args.reg_step == 1 ? S_INDEFINITE : S_REG_STEP)) return;
     } else if (args.skip_ok) {  // second pass over a list of flagged instances: what the pass before it solved is left alone
@@ -1812,15 +1816,20 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       // every word of the record but the trajectory must equal the group's first record's (whose M this solve uses)
       const int first = (inst / args.sweep_k) * args.sweep_k;
       const uint32_t *base = reinterpret_cast<const uint32_t *>(args.records + (size_t)first * args.stride);
-      const int nfix = RL::NF, ntraj = 12 * args.horizon, ngw = (NC * args.horizon + 3) >> 2;
+      // (the gait table's last word holds (NC h) % 4 gait bytes when that is not 0: the padding bytes after them are not compared)
+      const int nfix = RL::NF, ntraj = 12 * args.horizon, ngw = (NC * args.horizon + 3) >> 2, gtail = (NC * args.horizon) & 3;
+      const uint32_t tail_mask = gtail ? (1u << (8 * gtail)) - 1u : 0xffffffffu;
       const uint32_t *own = reinterpret_cast<const uint32_t *>(args.records + (size_t)inst * args.stride);
       int bad = 0;
       for (int t = tid; t < nfix + ngw; t += NT) {
         const int w = t < nfix ? t : t + ntraj;
-        bad |= (own[w] != base[w]) ? 1 : 0;
+        const uint32_t mask = (t == nfix + ngw - 1) ? tail_mask : 0xffffffffu;
+        bad |= ((own[w] ^ base[w]) & mask) ? 1 : 0;
       }
       if (__syncthreads_or(bad)) {  // uniform
         for (int t = tid; t < 6 * NC * args.horizon; t += NT) args.forces[(size_t)inst * 6 * NC * args.horizon + t] = 0.0f;
+        if (args.wset)  // (terminal: nothing to carry to the next tick, as for every instance that is not solved)
+          for (int t = tid; t < C8 * args.horizon; t += NT) args.wset[(size_t)inst * C8 * args.horizon + t] = 0;
         if (tid == 0) args.status[inst] = S_SWEEP_MISMATCH;
         return;
       }

@@ -223,6 +223,13 @@ class BatchedMPC:
         _check(self.L.hmpc_download_f64(self.h, x.ctypes.data, obj.ctypes.data), "hmpc_download_f64")
         return x, obj
 
+    def debug_handover_slots(self) -> np.ndarray:
+        """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where
+        the last solve handed instance i's working set over and nothing has consumed it yet, else -1."""
+        out = np.full(self.batch, -2, dtype=np.int32)
+        _check(self.L.hmpc_debug_handover_slots(self.h, out.ctypes.data), "hmpc_debug_handover_slots")
+        return out
+
     def solve_external_qp(self, H: np.ndarray, g: np.ndarray, Fc: np.ndarray) -> None:
         """Parity hook (hmpc_debug_solve_external_qp): solver stages on caller-supplied QP data; H [batch, ld, ld] and
         g [batch, ld] in the reference's reduced order, Fc [batch, 8 nc, 6 nc]."""

@@ -104,7 +104,9 @@ enum hmpc_status_code {
   HMPC_S_WORKSET = 5,     /* more simultaneously active constraints than the FAST variant's on-chip working set holds (64 rows; 96
                              with three contacts, 152 in the wide variant).  The safe pass holds as many rows as there are
                              variables -- in LDS for 120 variables, in global memory for 180 / 240 -- and cannot overflow */
-  HMPC_S_SWEEP_MISMATCH = 7, /* hmpc_solve_command_sweep: the record differs from its chunk's first record outside the trajectory; not solved */
+  HMPC_S_SWEEP_MISMATCH = 7, /* hmpc_solve_command_sweep: the record differs from its chunk's first record outside the trajectory; not solved.
+                                Terminal: forces 0, not counted as flagged, never re-solved by a repair pass; the instance's tick-to-tick
+                                working set (hmpc_set_tick_warm_start) is cleared */
   HMPC_S_INDEFINITE = 8,  /* the reduced Hessian, assembled in binary32 as the reference assembles it (SolverMPC.cpp:560-570), is NOT
                              positive definite: a sweep pivot of the safe pass came out <= 0 (seen with 20-step horizons at 10x the
                              nominal input ranges: rounding at 6e-8 |H| against a smallest eigenvalue of ~2 alpha).  An intermediate
@@ -189,7 +191,10 @@ int hmpc_download(hmpc_handle *h, float *forces, uint32_t *status);
  * workgroup per instance -- the chip as full as for independent solves -- assembles its own g, takes M from its group's slot
  * instead of assembling and inverting H (55 % of an independent solve) and runs the block start and the active-set iteration as
  * they stand: forces and status words are BIT-IDENTICAL to hmpc_solve's.  A record that differs from its group's first record
- * anywhere but in the trajectory is not solved: status HMPC_S_SWEEP_MISMATCH, forces 0 (checked on the device, word by word).
+ * anywhere but in the trajectory is not solved: status HMPC_S_SWEEP_MISMATCH, forces 0 (checked on the device, word by word; the
+ * padding bytes after the gait table are not part of the record and are ignored).  The mismatch is terminal: nothing re-solves it.
+ * Records handed in by device pointer without a size hint run per size class, on the variants hmpc_solve gives them.  A sweep hands
+ * no working set over: it clears the handle's hand-over slot table first.
  * Flagged instances are repaired as independent ones (hmpc_download / hmpc_set_device_repair).  Two-contact handles, horizon <= 10;
  * batch % group_size must be 0; group_size 1 is hmpc_solve.  A per-call CPU solver has no counterpart: the reference assembles and
  * factorises H for every command. */
@@ -388,6 +393,10 @@ int hmpc_enable_f64_output(hmpc_handle *h);
  * f_max.  Forces/status are written as by hmpc_solve.  tests/test_reference_source.py feeds it the reference's own data. */
 int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g, const float *Fc, int ld);
 int hmpc_download_f64(hmpc_handle *h, double *x, double *obj);
+/* Test hook: the hand-over slot table of the current batch, slots[batch]: slots[i] == i where the last solve's fast launch
+ * left instance i's working set for the continuation pass (its status word HMPC_S_WORKSET) and no pass has consumed it yet,
+ * -1 everywhere else.  Never an entry of an earlier solve or batch. */
+int hmpc_debug_handover_slots(hmpc_handle *h, int *slots);
 
 /* Developer hook (only in builds with -DHMPC_PROFILE, scripts/phase_profile.py): per-phase shader-clock cycles of
  * one more launch of the current batch, [batch][32] (phase ids: hmpc_kernel.h P_*). */

@@ -92,6 +92,81 @@ def test_sweep_reports_records_that_do_not_belong_to_their_group():
     np.testing.assert_array_equal(st[~bad], st_ind[~bad])
 
 
+@pytest.mark.parametrize("h", [5, 7, 9, 10])
+def test_sweep_ignores_the_padding_bytes_after_the_gait_table(h):
+    """The group check compares the gait table, not the bytes that pad the record after it: at odd horizons 2 h % 4 = 2, so the
+    table's last word holds two padding bytes (h = 10: none, the control).  Records whose padding differs from record to record --
+    caller-built ones, uploaded or handed in by device pointer -- are solved, bit for bit as the independent solves of the same
+    records.  (h = 5: 60 reduced variables; device records carry no size hint and must still reach the 60-variable sweep variant,
+    the one hmpc_solve's size-class launch gives them.)"""
+    import torch
+
+    groups, k = 8, 4
+    b = groups * k
+    rec = records.pack_records(sweep_fields(groups, k, h, "standing", seed=53), h)
+    goff = 4 * (54 + 12 * h) + 2 * h        # first byte after the gait table
+    assert rec.shape[1] - goff >= 2
+    rec[:, goff:] = np.random.default_rng(h).integers(1, 256, (b, rec.shape[1] - goff), dtype=np.uint8)
+    assert (rec[0::k, goff] != rec[1::k, goff]).any()
+    ind = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, b)
+    ind.upload(rec)
+    ind.solve()
+    f0, s0 = ind.download()
+    ind.close()
+    assert (interface.status_code(s0) == 0).all()
+    d_rec = torch.from_numpy(rec).cuda()
+    for device in (False, True):
+        sw = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, b)
+        sw.set_auto_resolve(False)
+        if device:
+            sw.set_device_records(d_rec.data_ptr(), b, keepalive=d_rec)
+        else:
+            sw.upload(rec)
+        sw.solve_command_sweep(k)
+        f1, s1 = sw.download()
+        sw.close()
+        assert (interface.status_code(s1) != 7).all(), (device, np.flatnonzero(interface.status_code(s1) == 7))
+        np.testing.assert_array_equal(s1, s0)
+        np.testing.assert_array_equal(f1.view(np.uint32), f0.view(np.uint32))
+
+
+def test_a_mismatched_sweep_record_leaves_no_tick_warm_row_behind():
+    """HMPC_S_SWEEP_MISMATCH is terminal and carries nothing to the next tick: with the tick-to-tick warm start on, the next ordinary
+    solve of the mismatched instance starts from an empty working set -- its status word and forces are those of a handle whose
+    rows were just reset (hmpc_reset_tick_warm_start), not of one warm-started from what the instance solved before the sweep."""
+    h, groups, k = 10, 8, 8
+    b = groups * k
+    f = sweep_fields(groups, k, h, "standing", seed=43)
+    rec = records.pack_records(f, h)
+    j = 3 * k + 5
+    f2 = {key: np.array(v, copy=True) for key, v in f.items()}
+    f2["weights"][j, 2] *= 1.5
+    rec2 = records.pack_records(f2, h)
+    m = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, b)
+    m.set_tick_warm_start(True)
+    m.upload(rec)
+    m.solve()
+    _, s_first = m.download()                      # every instance leaves its final working set for the next tick
+    m.upload(rec2)
+    m.solve_command_sweep(k)
+    _, s_sw = m.download()
+    assert interface.status_code(s_sw)[j] == 7 and (np.delete(interface.status_code(s_sw), j) == 0).all()
+    m.upload(rec)
+    m.solve()
+    f_after, s_after = m.download()
+    m.reset_tick_warm_start()
+    m.solve()
+    f_reset, s_reset = m.download()
+    m.upload(rec)                                  # (the control: a row carried over does change instance j's solve)
+    m.solve()
+    _, s_warm = m.download()
+    m.close()
+    assert s_warm[j] != s_reset[j] and interface.status_iters(s_reset)[j] > interface.status_iters(s_warm)[j], (s_warm[j], s_reset[j])
+    assert interface.status_code(s_first)[j] == 0 and interface.status_code(s_after)[j] == 0
+    assert s_after[j] == s_reset[j], (s_after[j], s_reset[j])
+    np.testing.assert_array_equal(f_after[j].view(np.uint32), f_reset[j].view(np.uint32))
+
+
 def test_sweep_argument_errors_and_the_group_of_one():
     h = 10
     rec = records.pack_records(sweep_fields(4, 4, h, "standing", seed=44), h)

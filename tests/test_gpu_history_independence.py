@@ -1,0 +1,153 @@
+"""History independence of a handle: what it returns for a batch depends on that batch alone (plus the tick-to-tick working sets
+the caller opted into), never on what the handle solved before.
+
+The repair chain (continuation from a hand-over slot -> perturbed safe pass -> exact pass -> regularisation -> last resort) reuses
+per-handle state that outlives a solve: the hand-over slot table and its slots, the status words, the flagged list.  A batch A whose
+working sets outgrew the fast variant and that was NOT repaired (auto-resolve off, no hmpc_resolve_failed) leaves its slots behind;
+a batch B solved next by launches that do not rewrite the slot table (command sweeps, the 240-variable wide variant, the workgroups
+of a size-class launch that leave early) must never be continued from them.  Every case here checks that the regime really occurs
+(A leaves unconsumed slots, B flags instances on the very indices A handed over), that B's outputs are the bits a fresh handle
+gives for B alone, that they are qpOASES' answers, and -- white box, independent of whether a resumed state happens to change the
+bits -- that the slot table names only the hand-overs of the solve that just ran."""
+import numpy as np
+import pytest
+
+from hector_simulation_amd import interface, records, synthetic
+
+pytestmark = pytest.mark.gpu
+
+NB = 256
+hard_batch = synthetic.hard_batch
+
+
+def _sweep_records(groups, k, h, seed, scale):
+    """`groups` off-nominal states (hard_batch), each under `k` commands: the records of a command sweep (group size k)"""
+    base = hard_batch(groups, h, "standing", seed, scale)
+    f = {key: np.repeat(np.asarray(v), k, axis=0) for key, v in base.items()}
+    rng = np.random.default_rng(seed + 5)
+    tr = f["traj"].reshape(groups * k, h, 12).copy()
+    tr[:, :, 9] += rng.uniform(-0.5, 0.5, groups * k)[:, None]
+    f["traj"] = tr.reshape(groups * k, -1)
+    return records.pack_records(f, h)
+
+
+def _case(name):
+    """(h, records of A, records of B, sweep group size of B or 0, device-resident records, wide[i] of B)"""
+    if name == "sweep":    # A: standing h = 10 at 10x (the fast 120-variable variant saves); B: a command sweep at 6x (variants 14 / 15)
+        rec_a = records.pack_records(hard_batch(NB, 10, "standing", 17, 10), 10)
+        return 10, rec_a, _sweep_records(NB // 8, 8, 10, 23, 6), 8, False, np.zeros(NB, dtype=bool)
+    if name == "wide":     # A: single support h = 20 at 10x (variant 3 saves); B: double support h = 20 at 6x (the wide variant)
+        rec_a = records.pack_records(hard_batch(NB, 20, "single", 17, 10), 20)
+        rec_b = records.pack_records(hard_batch(NB, 20, "standing", 31, 6), 20)
+        return 20, rec_a, rec_b, 0, False, np.ones(NB, dtype=bool)
+    # "classes": unsized device records h = 20, single and double support mixed (size-class launches); B's wide instances sit
+    # exactly on the indices that held A's 120-variable ones
+    nh = NB // 2
+    cat_a = np.concatenate([records.pack_records(hard_batch(nh, 20, "single", 17, 10), 20),
+                            records.pack_records(hard_batch(nh, 20, "standing", 29, 10), 20)])
+    cat_b = np.concatenate([records.pack_records(hard_batch(nh, 20, "standing", 31, 6), 20),
+                            records.pack_records(hard_batch(nh, 20, "single", 37, 6), 20)])
+    perm = np.random.default_rng(3).permutation(NB)
+    return 20, np.ascontiguousarray(cat_a[perm]), np.ascontiguousarray(cat_b[perm]), 0, True, perm < nh
+
+
+class _Batch:
+    """loads a batch into a handle (upload, or device pointer without a size hint) and solves it (hmpc_solve or a sweep)"""
+
+    def __init__(self, rec, sweep_k, device):
+        self.rec, self.sweep_k, self.d_rec = rec, sweep_k, None
+        if device:
+            import torch
+
+            self.d_rec = torch.from_numpy(rec).cuda()
+
+    def solve(self, m):
+        if self.d_rec is not None:
+            m.set_device_records(self.d_rec.data_ptr(), self.rec.shape[0], keepalive=self.d_rec)
+        else:
+            m.upload(self.rec)
+        if self.sweep_k:
+            m.solve_command_sweep(self.sweep_k)
+        else:
+            m.solve()
+
+
+def _handle(h):
+    m = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, NB)
+    m.set_auto_resolve(False)
+    return m
+
+
+def _leave_a_unrepaired(m, a):
+    """solves A on `m` with every repair off; returns (A's fast status codes, A's handed-over instances)"""
+    a.solve(m)
+    _, st_a = m.download()
+    code_a = interface.status_code(st_a)
+    handed = m.debug_handover_slots() == np.arange(NB)
+    assert (code_a == 5).mean() > 0.1, np.unique(code_a, return_counts=True)  # A leaves full working sets behind ...
+    assert handed.any() and (code_a[handed] == 5).all()                     # ... in slots nobody consumes
+    return code_a, handed
+
+
+_CASES = [("sweep", "host"), ("sweep", "device"), ("sweep", "continuation"), ("wide", "host"), ("wide", "device"),
+          ("classes", "host"), ("classes", "device")]
+
+
+@pytest.mark.parametrize("name,repair", _CASES)
+def test_outputs_for_b_do_not_depend_on_an_unrepaired_a(name, repair):
+    """A handle that solved A (left unrepaired) and then B returns for B the forces and status words, bit for bit, that a fresh
+    handle returns for B alone; every instance HMPC_S_OK and within 2e-6 of qpOASES.  Repair of B: hmpc_download (host), the
+    device-side chain (hmpc_set_device_repair 1), or its continuation pass followed by hmpc_download (2)."""
+    from oracle import pool
+
+    h, rec_a, rec_b, k, device, _ = _case(name)
+    a, b = _Batch(rec_a, 0, device), _Batch(rec_b, k, device)
+    # B's fast pass alone (a fresh handle, nothing repaired): what it flags must sit on indices A handed over
+    probe = _handle(h)
+    b.solve(probe)
+    _, st_b_fast = probe.download()
+    probe.close()
+    flagged_b = np.isin(interface.status_code(st_b_fast), (1, 4, 5))
+    outs = []
+    for with_history in (True, False):
+        m = _handle(h)
+        if with_history:
+            _, handed_a = _leave_a_unrepaired(m, a)
+            assert (flagged_b & handed_a).sum() > 0, (int(flagged_b.sum()), int(handed_a.sum()))
+        if repair != "host":
+            m.set_device_repair(1 if repair == "device" else 2)
+        b.solve(m)
+        m.set_auto_resolve(True)
+        outs.append(m.download())
+        m.close()
+    (f_hist, st_hist), (f_fresh, st_fresh) = outs
+    code = interface.status_code(st_hist)
+    assert (code == 0).all(), np.unique(code, return_counts=True)
+    np.testing.assert_array_equal(st_hist, st_fresh)
+    np.testing.assert_array_equal(f_hist.view(np.uint32), f_fresh.view(np.uint32))
+    ref = pool.solve_records_parallel(rec_b, h, synthetic.DT_MPC, synthetic.F_MAX)
+    q = ref["q_soln"]
+    err = np.abs(f_hist - q).max(axis=1) / np.maximum(1.0, np.abs(q).max(axis=1))
+    assert ref["n_bad"] == 0 and err.max() < 2e-6, (err.max(), int(np.argmax(err)))
+
+
+@pytest.mark.parametrize("name", ["sweep", "wide", "classes"])
+def test_handover_slot_table_names_only_this_solves_hand_overs(name):
+    """White box (hmpc_debug_handover_slots): after any fast solve, slot[i] == i exactly where THIS solve's saving variant handed
+    instance i over (fast status HMPC_S_WORKSET, instance of the 120-variable shape), -1 everywhere else -- after A (a saving
+    launch) and after B (sweep, wide variant, or size-class launches), before any repair."""
+    h, rec_a, rec_b, k, device, wide_b = _case(name)
+    m = _handle(h)
+    code_a, handed_a = _leave_a_unrepaired(m, _Batch(rec_a, 0, device))
+    wide_a = np.zeros(NB, dtype=bool) if name != "classes" else ~wide_b  # (classes: A's wide instances sit where B's are not)
+    np.testing.assert_array_equal(handed_a, (code_a == 5) & ~wide_a)
+    _Batch(rec_b, k, device).solve(m)
+    _, st_b = m.download()
+    slots = m.debug_handover_slots()
+    m.close()
+    code_b = interface.status_code(st_b)
+    assert (code_b == 5).any()                                  # B's fast pass does leave full working sets
+    saved_b = (code_b == 5) & ~wide_b & (k == 0)                # (sweeps and the wide variant hand nothing over)
+    stale = (slots != -1) & ~saved_b
+    assert not stale.any(), (int(stale.sum()), np.flatnonzero(stale)[:8], int((stale & handed_a).sum()))
+    np.testing.assert_array_equal(slots[saved_b], np.flatnonzero(saved_b))

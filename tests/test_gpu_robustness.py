@@ -104,21 +104,26 @@ def test_repeated_solves_are_bitwise_identical(gait, h, nb):
         np.testing.assert_array_equal(forces.view(np.uint32), outs[0][0].view(np.uint32))
 
 
-@pytest.mark.parametrize("gait,h", [("standing", 10), ("single", 20)])
-def test_device_side_safe_pass_equals_the_host_driven_one(gait, h):
+@pytest.mark.parametrize("gait,h,nc", [("standing", 10, 2), ("single", 20, 2), ("standing", 10, 3)],
+                         ids=["standing-10", "single-20", "standing-10-contacts3"])
+def test_device_side_safe_pass_equals_the_host_driven_one(gait, h, nc):
     """hmpc_set_device_repair: the safe variant runs behind the fast launch on the same stream over the device-resident
     list of flagged instances -- the outputs in HBM equal those of hmpc_resolve_failed's first (exact) pass, bit for bit,
-    with no host round trip; nominal batches are unaffected."""
+    with no host round trip; nominal batches are unaffected.  Every instance the device side ends HMPC_S_OK is left alone by
+    the host-driven passes that follow its first safe pass (skip_ok; three contacts: the 140-row safe variant as well)."""
     nb = 256
-    rec = records.pack_records(hard_batch(nb, h, gait, 23, 6), h)
-    a = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, nb)
+    if nc == 3:
+        rec = records.pack_records(_hard3(nb, 23, 6), h, 3)
+    else:
+        rec = records.pack_records(hard_batch(nb, h, gait, 23, 6), h)
+    a = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, nb, contacts=nc)
     a.set_auto_resolve(False)
     a.upload(rec)
     a.solve()
     _, st_fast = a.download()
     n_flagged = int(np.isin(interface.status_code(st_fast), (1, 2, 4, 5)).sum())
     assert n_flagged > 0
-    b = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, nb)
+    b = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, nb, contacts=nc)
     b.set_auto_resolve(False)
     b.set_device_repair(True)
     b.upload(rec)
@@ -128,6 +133,15 @@ def test_device_side_safe_pass_equals_the_host_driven_one(gait, h):
     a.set_auto_resolve(True)
     f_host, st_host = a.download()
     a.close()
+    # the device's safe launch and the host's pass (2) are the same launch: what it ends ok, the host side ends with the same bits
+    dev_ok = interface.status_code(st_dev) == 0
+    np.testing.assert_array_equal(st_host[dev_ok], st_dev[dev_ok])
+    np.testing.assert_array_equal(f_host[dev_ok].view(np.uint32), f_dev[dev_ok].view(np.uint32))
+    if nc == 3:
+        # (the precondition: the safe launch did end instances ok that the fast variant had flagged)
+        assert dev_ok.sum() > (interface.status_code(st_fast) == 0).sum(), (int(dev_ok.sum()), n_flagged)
+        assert np.isin(interface.status_code(st_host), (0, 6)).all(), np.unique(interface.status_code(st_host), return_counts=True)
+        return
     # what the safe variant itself solves is the same bits either way; the few instances that also need the host-driven
     # last-resort passes (perturbed bounds + exact re-solve: exact on the host side since round 4) stay flagged on the device
     exact = (interface.status_code(st_host) == 0) & (interface.status_code(st_dev) == 0)
@@ -174,6 +188,8 @@ def test_hard_inputs_three_contacts(oracle, scale, min_ok):
     code = interface.status_code(status)
     ok = (code == 0) | (code == 6)
     assert ok.mean() >= min_ok, np.unique(code, return_counts=True)
+    if scale <= 6:
+        assert (code == 0).all(), np.unique(code, return_counts=True)  # exact: not even HMPC_S_OK_RELAXED (as test_hard_inputs)
     ref = oracle.solve_records(rec, 10, synthetic.DT_MPC, synthetic.F_MAX, nc=3)
     q = ref["q_soln"]
     err = np.abs(forces - q).max(axis=1) / np.maximum(1.0, np.abs(q).max(axis=1))
