@@ -42,30 +42,30 @@ thread_local std::string g_hip_err;
 // The extension with a third (hand) contact -- BASELINE config 5, 180 variables x 240 rows at h = 10 -- runs 256-thread
 // workgroups with two register blocks per thread (465 blocks, two workgroups per CU; round 2: 512 threads, one per CU --
 // still the shape of its safe pass).  BPT = blocks per thread, see hmpc_kernel.h.
+constexpr int N_VARIANTS = 15;
 const Variant *variants() {
-  static const Variant v[] = {hmpc_variant_0(), hmpc_variant_1(), hmpc_variant_2(),  hmpc_variant_3(),
-                              hmpc_variant_4(), hmpc_variant_5(), hmpc_variant_6(),  hmpc_variant_7(),
-                              hmpc_variant_8(), hmpc_variant_9(), hmpc_variant_10(), hmpc_variant_11(),
-                              hmpc_variant_12(), hmpc_variant_13(), hmpc_variant_14(), hmpc_variant_15()};
+#define HMPC_VARIANT_ENTRY(IDX, ...) hmpc_variant_##IDX(),
+  static const Variant v[] = {HMPC_VARIANT_TABLE(HMPC_VARIANT_ENTRY)};
+#undef HMPC_VARIANT_ENTRY
+  static_assert(sizeof(v) / sizeof(v[0]) == N_VARIANTS, "hmpc_variants.h");
   return v;
 }
 constexpr int N_FAST = 4;       // two-contact fast variants [0, N_FAST), their safe variants N_FAST + (h > 10)
-constexpr int V3_FAST = 6, V3_SAFE = 7, V3_FAST_512 = 8;  // (V3_FAST_512: the one-workgroup-per-CU variant of round 2, HMPC_3C_512=1)
+constexpr int V3_FAST = 6, V3_SAFE = 7;
 // double support over more than ten steps (two contacts, 121 .. 240 reduced variables, h <= 20): 820 register blocks on 512
 // threads, two each, one workgroup per CU; working set up to HMPC_QCAP_WIDE rows (what 160 KB of LDS leave room for).
-constexpr int V2_WIDE = 9;
+constexpr int V2_WIDE = 8;
 // QCAP = 0: working set as large as the variable count with the packed Schur inverse in GLOBAL memory (a scratch slice per
 // workgroup; 231 KB for 240 variables -- more than a CU's LDS): the safe pass of the wide variant, and the second safe pass of
 // the three-contact one (whose LDS-resident safe variant holds 140 of 180 possible rows)
-constexpr int V2_WIDE_SAFE = 10, V3_SAFE_G = 11;
+constexpr int V2_WIDE_SAFE = 9, V3_SAFE_G = 10;
 // the CONTINUATION variants of the 120-variable shapes (h <= 10, h <= 20): working set of HMPC_QCAP_CONT = 96 rows, 70 KB of LDS = two
 // workgroups per CU; they take over -- state and all -- the solves whose working set outgrew the fast variants' 64 rows, run block
 // rounds of up to 96 rows on them, and leave what outgrows them in turn (HMPC_S_WORKSET again) to the 120-row safe variants
-constexpr int V2_CONT = 12;  // + (h > 10)
-// command sweeps (MODE 1, hmpc_solve_command_sweep): a workgroup solves a chunk of instances that share state and gait on ONE
+constexpr int V2_CONT = 11;  // + (h > 10)
+// command sweeps (hmpc_solve_command_sweep): a workgroup solves a chunk of instances that share state and gait on ONE
 // inverse -- the 120-variable h <= 10 shape and the 60-variable (single support) one
-constexpr int V2_SWEEP_120 = 14, V2_SWEEP_60 = 15;
-constexpr int N_VARIANTS = 16;
+constexpr int V2_SWEEP_120 = 13, V2_SWEEP_60 = 14;
 constexpr int MAX_VARS_ANY = 240;
 constexpr int DBG_FLOATS_MAX = hmpc::DbgLayout<240, 2>::TOTAL > hmpc::DbgLayout<180, 3>::TOTAL
                                    ? hmpc::DbgLayout<240, 2>::TOTAL
@@ -147,25 +147,30 @@ constexpr int REPAIR_GRID_CAP = 65536;  // workgroups of the device-side safe la
 constexpr double SAFE_PASS_RELAX = 1e-6;  // first safe pass (device- and host-driven): bounds moved outward by this, exact re-solve + exact KKT check at its end
 constexpr int SPILL_SLOT_CAP = 32768;   // hand-over slots per handle at most (101 KB each for 120 variables: 3.3 GB of the 288 GB); instances beyond it are re-solved cold
 constexpr int EGLOBAL_CHUNK = 512;         // host-driven safe pass of the global-E variants: instances per launch (118 MB of scratch at 240 variables)
-constexpr int DEVICE_REG_MIN_HORIZON = 10;  // device-side chain: the regularisation launches are enqueued for longer horizons only (enqueue_reg_steps)
+constexpr int DEVICE_REG_MIN_HORIZON = 10;  // device-side chain: the regularisation launches are enqueued for longer horizons only (device_reg_steps)
 constexpr int REG_LIST_CAP = 256;  // device-side chain: instances per solve whose Hessian is not positive definite that get the regularisation launches (the rest: hmpc_resolve_failed)
 constexpr int REPAIR_GRID_CAP_WIDE = 4096;  // ... of the wide variant's, whose safe pass keeps 231 KB per workgroup in global memory (0.95 GB of 288: the list mixes size classes, so a small cap could leave a wide instance behind 256 others unrepaired -- ADVICE round 5)
 
+// grows a device buffer of the handle to at least `bytes` (contents undefined).  The old buffer is freed only once nothing can still
+// be using it: its users' stream is synchronised first, or the whole device when they may be on any stream (whole_device).
+template <class T>
+static int grow(T **buf, size_t *have, size_t bytes, hipStream_t stream, bool whole_device) {
+  if (*buf && bytes <= *have) return HMPC_OK;
+  if (*buf) {
+    HIP_TRY(whole_device ? hipDeviceSynchronize() : hipStreamSynchronize(stream));
+    HIP_TRY(hipFree(*buf));
+    *buf = nullptr, *have = 0;
+  }
+  HIP_TRY(hipMalloc((void **)buf, bytes));
+  *have = bytes;
+  return HMPC_OK;
+}
+
 // returns a device buffer of at least `bytes` owned by the handle (contents undefined)
 static int scratch(hmpc_handle *h, size_t bytes, void **out) {
-  if (bytes > h->scratch_bytes) {
-    if (h->d_scratch) {
-      HIP_TRY(hipDeviceSynchronize());  // a previous user of the old buffer may still be in flight
-      HIP_TRY(hipFree(h->d_scratch));
-      h->d_scratch = nullptr;
-      h->scratch_bytes = 0;
-    }
-    const size_t want = (bytes + 4095) & ~(size_t)4095;
-    HIP_TRY(hipMalloc(&h->d_scratch, want));
-    h->scratch_bytes = want;
-  }
+  const int rc = grow(&h->d_scratch, &h->scratch_bytes, (bytes + 4095) & ~(size_t)4095, nullptr, /*whole_device=*/true);
   *out = h->d_scratch;
-  return HMPC_OK;
+  return rc;
 }
 
 // RAII for the two timing events of hmpc_time_solve
@@ -177,19 +182,12 @@ struct EventPair {
   }
 };
 
-static const Variant &pick_variant(const hmpc_handle *h, int *index) {
+// the fast variant of a batch: the one that holds its widest reduced QP (the only place a handle is mapped to a fast variant)
+static int pick_variant(const hmpc_handle *h) {
   const Variant *v = variants();
   const int hz = h->setup.horizon;
-  if (h->nc == 3) {
-    static const bool old512 = getenv("HMPC_3C_512") && getenv("HMPC_3C_512")[0] == '1';  // developer A/B switch
-    const int vi3 = old512 ? V3_FAST_512 : V3_FAST;
-    if (index) *index = vi3;
-    return v[vi3];
-  }
-  if (h->max_stance > HMPC_MAX_VARS && hz > 10) {  // double support beyond ten steps: the wide variant
-    if (index) *index = V2_WIDE;
-    return v[V2_WIDE];
-  }
+  if (h->nc == 3) return V3_FAST;
+  if (h->max_stance > HMPC_MAX_VARS && hz > 10) return V2_WIDE;  // double support beyond ten steps: the wide variant
   int best = -1;
   for (int i = 0; i < N_FAST; ++i) {
     if (v[i].hmax < hz) continue;
@@ -197,15 +195,24 @@ static const Variant &pick_variant(const hmpc_handle *h, int *index) {
     if (h->max_stance < 0 && v[i].nmax < HMPC_MAX_VARS) continue;
     if (best < 0 || v[i].smem < v[best].smem) best = i;
   }
-  if (best < 0) best = N_FAST - 1;  // oversize batches are reported per instance (HMPC_S_TOO_LARGE)
-  if (index) *index = best;
-  return v[best];
+  return best < 0 ? N_FAST - 1 : best;  // oversize batches are reported per instance (HMPC_S_TOO_LARGE)
+}
+
+// the variant of a list launch of the continuation (role CONT) or the safe pass (SAFE): the safe variants hold a working set as
+// large as the variable count -- for 240 variables only in global memory; ultimate = the three-contact safe pass's second level,
+// whose working set cannot overflow either (global memory as well)
+static int repair_variant(const hmpc_handle *h, Role role, bool ultimate = false) {
+  const int long_h = h->setup.horizon > 10 ? 1 : 0;
+  if (role == Role::CONT) return V2_CONT + long_h;
+  if (pick_variant(h) == V2_WIDE) return V2_WIDE_SAFE;
+  if (h->nc == 3) return ultimate ? V3_SAFE_G : V3_SAFE;
+  return N_FAST + long_h;
 }
 
 struct LaunchOpt {
   bool assemble_only = false;
   int dbg_index = 0;
-  const int *d_index_list = nullptr;  // workgroup b solves instance d_index_list[b] with the SAFE variant (re-solve of flagged ones)
+  const int *d_index_list = nullptr;  // workgroup b solves instance d_index_list[b] (the repair passes over flagged instances)
   int n_list = 0;
   double relax = 0.0;
   int warm = -1;           // -1 = the handle's setting, 0/1 = override for this launch (the safe pass chooses per pass without touching the handle)
@@ -213,14 +220,9 @@ struct LaunchOpt {
   const unsigned int *d_list_count = nullptr;
   bool record_flagged = false;
   bool longest_first = false;  // workgroup b takes instance h->d_order[b] (enqueue_solve, hmpc_set_dispatch_order)
-  int variant = -1;        // -1 = pick_variant; else this entry of variants() (the size-class launches)
-  bool ultimate = false;   // safe pass, second level (three contacts): the variant whose working set cannot overflow
   int cls_lo = 0, cls_hi = -1;  // cls_hi >= 0: only instances whose size class lies in [cls_lo, cls_hi] (h->d_cls)
-  int safe_variant = -1;   // safe pass over an index list: this entry of variants() instead of the one derived from pick_variant
-  bool resume = false;     // safe pass over an index list: instances whose fast solve left its state in a hand-over slot continue from it
-  bool continuation = false;  // list launch of the CONTINUATION variant (V2_CONT): only instances with a hand-over slot, everything else on the list is left alone
   int skip_ok = 0;         // list launch: instances an earlier pass over the same list solved are left alone (1: ok / ok-relaxed, 2: ok only)
-  int sweep_k = 0, sweep_phase = 0;  // command sweep: group size; phase 0 = one workgroup per group forms M, 1 = one per instance solves with it (variant = a MODE 1 entry)
+  int sweep_k = 0, sweep_phase = 0;  // command sweep: group size; phase 0 = one workgroup per group forms M, 1 = one per instance solves with it (a SWEEP variant)
   bool list_indefinite = false;  // device-side chain, safe launch: instances ended as HMPC_S_INDEFINITE are appended to the handle's short list
   int reg_step = 0;        // safe pass over an index list: regularisation step 1 / 2 for instances whose Hessian is not positive definite (KernelArgs::reg_step)
 };
@@ -229,19 +231,10 @@ struct LaunchOpt {
 // HMPC_S_INDEFINITE; the two counters sit next to each other (one memset clears both)
 static int flag_list_cap(const hmpc_handle *h) { return h->max_batch < REPAIR_GRID_CAP ? h->max_batch : REPAIR_GRID_CAP; }
 
-static int launch(hmpc_handle *h, hipStream_t stream, const LaunchOpt &o) {
-  int vi = 0;
-  const Variant *pv = &pick_variant(h, &vi);
-  if (o.variant >= 0) vi = o.variant, pv = &variants()[vi];
-  if (o.d_index_list) {  // safe variant: working set as large as the variable count
-    if (o.continuation) vi = V2_CONT + (h->setup.horizon > 10 ? 1 : 0);
-    else if (o.safe_variant >= 0) vi = o.safe_variant;
-    else if (vi == V2_WIDE) vi = V2_WIDE_SAFE;             // ... which for 240 variables only global memory holds
-    else if (h->nc == 3) vi = o.ultimate ? V3_SAFE_G : V3_SAFE;
-    else vi = (h->setup.horizon <= 10) ? N_FAST : N_FAST + 1;
-    pv = &variants()[vi];
-  }
-  const Variant &v = *pv;
+// One launch of variants()[vi].  A list launch of the CONTINUATION variant resumes the listed instances whose fast solve handed its
+// state over (KernelArgs::resume = 2) and leaves every other one alone; where nothing can have been handed over it launches nothing.
+static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
+  const Variant &v = variants()[vi];
   const int grid_all = o.assemble_only ? 1 : (o.d_index_list ? o.n_list : ((o.sweep_k > 0 && o.sweep_phase == 0) ? h->batch / o.sweep_k : h->batch));
   if (grid_all < 1) return HMPC_OK;
   // EGLOBAL variants keep NMAX (NMAX + 1) / 2 doubles of global scratch per WORKGROUP (231 KB for 240 variables): a host-driven
@@ -249,22 +242,14 @@ static int launch(hmpc_handle *h, hipStream_t stream, const LaunchOpt &o) {
   // keeps the chunks apart).  The device-driven pass (d_list_count) is one launch, capped by its caller.
   const int chunk = (v.qcap == 0 && o.d_index_list && !o.d_list_count && grid_all > EGLOBAL_CHUNK) ? EGLOBAL_CHUNK : grid_all;
   if (v.qcap == 0) {  // EGLOBAL: one slice of packed triangle per workgroup of this launch
-    const size_t need = (size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double);
-    if (need > h->e_bytes) {
-      if (h->d_escratch) {
-        HIP_TRY(hipStreamSynchronize(stream));  // (an earlier launch on this stream may still be using the old buffer)
-        HIP_TRY(hipFree(h->d_escratch));
-        h->d_escratch = nullptr, h->e_bytes = 0;
-      }
-      HIP_TRY(hipMalloc(&h->d_escratch, need));
-      h->e_bytes = need;
-    }
+    const int rc = grow(&h->d_escratch, &h->e_bytes, (size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double), stream, false);
+    if (rc != HMPC_OK) return rc;
   }
   // hand-over slots: allocated on the first launch of a variant that saves its state (one slot per instance of the handle).
   // The per-instance slot table is written by EVERY ordinary launch of such a variant (-1 where nothing was saved), also when
   // saving itself is off for the launch, so that a later safe pass never meets an entry of an earlier batch.
   if (o.assemble_only && !v.assemble) return HMPC_E_ARG;
-  if ((v.mode == 1) != (o.sweep_k > 0)) return HMPC_E_ARG;
+  if ((v.role == Role::SWEEP) != (o.sweep_k > 0)) return HMPC_E_ARG;
   const bool can_save = v.spill_stride > 0 && !o.assemble_only && !o.d_index_list;
   const bool saves = can_save && h->handover && !h->d_ext_H;
   if (can_save && !h->d_spill_slot) {
@@ -272,13 +257,10 @@ static int launch(hmpc_handle *h, hipStream_t stream, const LaunchOpt &o) {
     HIP_TRY(hipMemset(h->d_spill_slot, 0xff, (size_t)h->max_batch * sizeof(int)));
   }
   if (saves && (!h->d_spill || h->spill_stride < v.spill_stride)) {
-    if (h->d_spill) {
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipFree(h->d_spill));
-      h->d_spill = nullptr;
-    }
     const int cap = h->max_batch < SPILL_SLOT_CAP ? h->max_batch : SPILL_SLOT_CAP;
-    HIP_TRY(hipMalloc(&h->d_spill, (size_t)cap * v.spill_stride));
+    size_t have = h->d_spill ? (size_t)h->spill_cap * h->spill_stride : 0;
+    const int rc = grow(&h->d_spill, &have, (size_t)cap * v.spill_stride, stream, /*whole_device=*/true);
+    if (rc != HMPC_OK) return rc;
     h->spill_stride = v.spill_stride, h->spill_cap = cap;
   }
   kernel_fn fn = o.assemble_only ? v.assemble : v.solve;
@@ -322,11 +304,11 @@ static int launch(hmpc_handle *h, hipStream_t stream, const LaunchOpt &o) {
   if (can_save) {
     a.spill_slot = h->d_spill_slot;
     if (saves) a.spill = h->d_spill, a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap;
-  } else if (o.d_index_list && o.resume && v.resumes && h->handover && h->d_spill && h->d_spill_slot && o.relax == 0.0 && !h->d_ext_H) {
+  } else if (v.role == Role::CONT) {
+    // nothing was handed over (hand-over off / no slots), or the pass is one that must not resume: nothing to do
+    if (!o.d_index_list || !h->handover || !h->d_spill || !h->d_spill_slot || o.relax != 0.0 || h->d_ext_H) return HMPC_OK;
     a.spill = h->d_spill, a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap, a.spill_slot = h->d_spill_slot;
-    a.resume = o.continuation ? 2 : 1;
-  } else if (o.continuation) {
-    return HMPC_OK;  // nothing was handed over (hand-over off / no slots): the continuation pass has nothing to do
+    a.resume = 2;
   }
   a.skip_ok = o.skip_ok;
   if (o.d_index_list && !h->d_reg_rho) HIP_TRY(hipMalloc(&h->d_reg_rho, (size_t)h->max_batch * sizeof(double)));  // (safe variants: where a pivot that is not positive is left)
@@ -348,55 +330,112 @@ static int launch(hmpc_handle *h, hipStream_t stream, const LaunchOpt &o) {
   return HMPC_OK;
 }
 
-// The safe pass over a list of flagged instances.  Where the host knows the batch's widest reduced QP (or the family has one safe
-// variant) that is one launch.  A two-contact batch at h > 10 whose sizes only the DEVICE knows (records built on the device or
-// handed in by pointer: max_stance < 0) may hold both <= 120-variable instances and double-support ones with up to 240: the list
-// is then run twice, once per safe variant, each workgroup leaving at once unless its instance's size class belongs to the
-// variant -- a wide instance must never reach the 120-variable kernel (it would end as HMPC_S_TOO_LARGE with zero forces, which
-// nothing re-solves).
-static int launch_safe(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
-  if (h->nc == 2 && h->max_stance < 0 && h->setup.horizon > 10 && h->d_cls) {
-    s.safe_variant = N_FAST + 1, s.cls_lo = 0, s.cls_hi = 20;
-    int rc = launch(h, stream, s);
-    if (rc != HMPC_OK) return rc;
-    s.safe_variant = V2_WIDE_SAFE, s.cls_lo = 21, s.cls_hi = 255;
-    if (s.d_list_count && s.n_list > REPAIR_GRID_CAP_WIDE) s.n_list = REPAIR_GRID_CAP_WIDE;  // (one launch: bounded scratch)
-    return launch(h, stream, s);
+// the size classes of a two-contact batch whose widest reduced QP only the device knows (records built on the device or handed in by
+// pointer): every variant of the family runs over the whole batch, a workgroup whose instance belongs to another one leaving at once
+static bool by_class(const hmpc_handle *h) { return h->nc == 2 && h->max_stance < 0 && h->d_cls; }
+
+// The fast pass of one solve: one launch of variant `vi` over the batch, or (by_class) the size-class launches --
+//  * ordinary solves (variants(): [0] <60,10,128>, [1] <120,10,256>, [2] <60,20,128>, [3] <120,20,256>, V2_WIDE <240,20,512>):
+//    [0, 10] on 0 / 2, [11, 255] (h <= 10) or [11, 20] (h > 10) on 1 / 3, [21, 255] on the wide variant (h > 10 only);
+//  * command sweeps (o.sweep_k > 0; vi and the class variants are SWEEP variants): the h <= 10 classes, each launch in its two
+//    phases, the first of which lists nothing.
+// The hand-over slot table must describe the CURRENT solve for the whole batch: the continuation pass resumes instance i from slot i
+// when the table says i and the status word says "working set full" -- an entry an earlier batch left, met by a status word of this
+// solve from a launch that does not rewrite the table (the 60-variable, wide, sweep and external-QP launches; the workgroups of a
+// size-class launch that leave early), would continue the old QP's state against the new record.  So the table is cleared first,
+// unless the solve is ONE launch of a saving variant, which rewrites every entry itself.
+static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes, LaunchOpt o) {
+  const bool sweep = o.sweep_k > 0, long_h = h->setup.horizon > 10;
+  struct { int vi, lo, hi; } l[3] = {{vi, 0, -1}};
+  int n = 1;
+  if (classes && sweep) {
+    l[0] = {V2_SWEEP_60, 0, 10}, l[1] = {V2_SWEEP_120, 11, 255}, n = 2;
+  } else if (classes) {
+    l[0] = {long_h ? 2 : 0, 0, 10}, l[1] = {long_h ? 3 : 1, 11, long_h ? 20 : 255}, l[2] = {V2_WIDE, 21, 255}, n = long_h ? 3 : 2;
   }
-  return launch(h, stream, s);
+  if ((n > 1 || variants()[l[0].vi].spill_stride == 0) && h->d_spill_slot && h->batch > 0)
+    HIP_TRY(hipMemsetAsync(h->d_spill_slot, 0xff, (size_t)h->batch * sizeof(int), stream));
+  if (classes && !h->cls_valid) {
+    hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, stream, h->d_records,
+                       (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
+    HIP_TRY(hipGetLastError());
+  }
+  const bool record_flagged = o.record_flagged;
+  for (int k = 0; k < n; ++k) {
+    o.cls_lo = l[k].lo, o.cls_hi = l[k].hi;
+    if (sweep) {
+      o.sweep_phase = 0, o.record_flagged = false;
+      const int rc = launch(h, stream, l[k].vi, o);
+      if (rc != HMPC_OK) return rc;
+      o.sweep_phase = 1, o.record_flagged = record_flagged;
+    }
+    const int rc = launch(h, stream, l[k].vi, o);
+    if (rc != HMPC_OK) return rc;
+  }
+  return HMPC_OK;
 }
 
-// Device-side chain, behind the safe launch: instances whose Hessian is not positive definite (that launch found a sweep pivot <= 0,
-// ended them as HMPC_S_INDEFINITE and listed them) get the reference's two regularised QPs (KernelArgs::reg_step; hmpc_resolve_failed
-// runs the same two launches from the status words).  The list is a short one of its own (REG_LIST_CAP entries, its counter next to
-// the flagged counter), so the two launches are a few hundred workgroups that leave at once when it is empty.
-static int enqueue_reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
-  // Two launches = ~4 us of dispatch latency per solve even when their list is empty (scripts/dev/chain_overhead.py: the whole chain
-  // 11 -> 15 us at b8192, 6 -> 10 us at b1024), so only where such Hessians occur: horizons beyond 10 steps (binary32 round-off in H
-  // grows with the horizon; 107 of 4 096 double-support h = 20 instances at 10x the input ranges, none in any h <= 10 stress row up to
-  // 10x -- 20 000 instances).  A shorter-horizon handle would leave such an instance HMPC_S_INDEFINITE for hmpc_resolve_failed.
+// The repair steps over a list of flagged instances (the device-side chain's list, trimmed on the device by its counter, or a list
+// the host uploaded), in the order each chain calls them.
+// (1) continuation: instances whose working set outgrew the fast variant go on, from the state it handed over, on the variant with
+//     96 rows and block rounds of its own (two per CU).  *taken = whether the step applies (the safe pass behind it then leaves
+//     alone what it solved), also when the launch finds nothing to resume.
+static int continuation_pass(hmpc_handle *h, hipStream_t stream, const LaunchOpt &s, bool *taken) {
+  *taken = h->nc == 2 && h->handover && h->d_spill;
+  return *taken ? launch(h, stream, repair_variant(h, Role::CONT), s) : HMPC_OK;
+}
+
+// (2) the safe pass.  Where the host knows the batch's widest reduced QP (or the family has one safe variant) that is one launch.  A
+// two-contact batch at h > 10 whose sizes only the DEVICE knows (by_class) may hold both <= 120-variable instances and double-support
+// ones with up to 240: the list is then run twice, once per safe variant, each workgroup leaving at once unless its instance's size
+// class belongs to the variant -- a wide instance must never reach the 120-variable kernel (it would end as HMPC_S_TOO_LARGE with zero
+// forces, which nothing re-solves).
+static int safe_pass(hmpc_handle *h, hipStream_t stream, LaunchOpt s, bool ultimate = false) {
+  if (!by_class(h) || h->setup.horizon <= 10) return launch(h, stream, repair_variant(h, Role::SAFE, ultimate), s);
+  s.cls_lo = 0, s.cls_hi = 20;
+  const int rc = launch(h, stream, N_FAST + 1, s);
+  if (rc != HMPC_OK) return rc;
+  s.cls_lo = 21, s.cls_hi = 255;
+  if (s.d_list_count && s.n_list > REPAIR_GRID_CAP_WIDE) s.n_list = REPAIR_GRID_CAP_WIDE;  // (one launch: bounded scratch)
+  return launch(h, stream, V2_WIDE_SAFE, s);
+}
+
+// (3) instances whose Hessian is not positive definite (the safe variants' sweeps found a pivot <= 0 and ended them as
+// HMPC_S_INDEFINITE) get the reference's two regularised QPs (KernelArgs::reg_step): H + rho I, then one more QP with the gradient
+// g - rho x_1 (QProblem.cpp:1753-1860, QProblemB.cpp:1999-2031)
+static int reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
+  s.relax = 0.0, s.warm = 1, s.skip_ok = 0, s.list_indefinite = false;
+  for (int step = 1; step <= 2; ++step) {
+    s.reg_step = step;
+    const int rc = safe_pass(h, stream, s);
+    if (rc != HMPC_OK) return rc;
+  }
+  return HMPC_OK;
+}
+
+// the device-side chain's list: what the fast launches flagged, min(batch, REPAIR_GRID_CAP) workgroups (fewer for the wide variant,
+// whose safe pass keeps 231 KB of global scratch per workgroup); workgroups beyond the flagged count leave at once
+static LaunchOpt device_list(const hmpc_handle *h) {
+  LaunchOpt s;
+  s.d_index_list = h->d_flag_list;
+  s.d_list_count = h->d_flag_count;
+  s.n_list = h->batch < REPAIR_GRID_CAP ? h->batch : REPAIR_GRID_CAP;
+  if (pick_variant(h) == V2_WIDE && s.n_list > REPAIR_GRID_CAP_WIDE) s.n_list = REPAIR_GRID_CAP_WIDE;
+  return s;
+}
+
+// The device-side chain's regularisation steps run over a short list of their own (REG_LIST_CAP entries, its counter next to the
+// flagged counter, filled by the safe launch), so the two launches are a few hundred workgroups that leave at once when it is empty.
+// Two launches = ~4 us of dispatch latency per solve even when their list is empty (scripts/dev/chain_overhead.py: the whole chain
+// 11 -> 15 us at b8192, 6 -> 10 us at b1024), so only where such Hessians occur: horizons beyond 10 steps (binary32 round-off in H
+// grows with the horizon; 107 of 4 096 double-support h = 20 instances at 10x the input ranges, none in any h <= 10 stress row up to
+// 10x -- 20 000 instances).  A shorter-horizon handle would leave such an instance HMPC_S_INDEFINITE for hmpc_resolve_failed.
+static int device_reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
   if (h->setup.horizon <= DEVICE_REG_MIN_HORIZON) return HMPC_OK;
   s.d_index_list = h->d_flag_list + flag_list_cap(h);
   s.d_list_count = h->d_flag_count + 1;
   s.n_list = h->batch < REG_LIST_CAP ? h->batch : REG_LIST_CAP;
-  s.relax = 0.0, s.warm = 1, s.skip_ok = 0, s.list_indefinite = false;
-  int rc = HMPC_OK;
-  for (int step = 1; step <= 2 && rc == HMPC_OK; ++step) {
-    s.reg_step = step;
-    rc = launch_safe(h, stream, s);
-  }
-  return rc;
-}
-
-// The hand-over slot table must describe the CURRENT solve for the whole batch: the continuation pass resumes instance i from slot i
-// when the table says i and the status word says "working set full" -- an entry an earlier batch left, met by a status word of this
-// solve from a launch that does not rewrite the table (the 60-variable, wide, sweep and external-QP launches; the workgroups of a
-// size-class launch that leave early), would continue the old QP's state against the new record.  Such a solve clears the table
-// first, once, before its first launch (a saving launch after it still writes its own entries); a solve that is ONE launch of a
-// saving variant rewrites every entry itself and gets nothing extra.
-static int invalidate_handover_slots(hmpc_handle *h, hipStream_t stream) {
-  if (h->d_spill_slot && h->batch > 0) HIP_TRY(hipMemsetAsync(h->d_spill_slot, 0xff, (size_t)h->batch * sizeof(int), stream));
-  return HMPC_OK;
+  return reg_steps(h, stream, s);
 }
 
 // One solve of the current batch, enqueued on `stream` -- what hmpc_solve does and what hmpc_time_solve times:
@@ -406,7 +445,7 @@ static int invalidate_handover_slots(hmpc_handle *h, hipStream_t stream) {
 //    on the device (from the record builder, else counted here from the gait bytes) and EVERY variant of the family is
 //    launched over the whole batch -- a workgroup whose instance belongs to another variant leaves at once -- so that a
 //    walking sweep built on the device runs on the 60-variable kernel without the host ever seeing a gait table;
-//  * device repair: the fast launches list what they flag, the safe variant follows over that list (trimmed on the
+//  * device repair: the fast launches list what they flag, the repair steps follow over that list (trimmed on the
 //    device by the counter: workgroups beyond it leave at once).  One stream per handle at a time: the list and its
 //    counter belong to the handle, two solves of one handle in flight on two streams would race on them.
 static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
@@ -439,72 +478,25 @@ static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
   o.carry_wset = carry_wset;
   o.record_flagged = repair;
   o.longest_first = h->order_valid;
-  int rc = HMPC_OK;
-  if (h->nc == 2 && h->max_stance < 0 && h->d_cls) {
-    rc = invalidate_handover_slots(h, stream);
-    if (rc != HMPC_OK) return rc;
-    if (!h->cls_valid) {
-      hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, stream, h->d_records,
-                         (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
-      HIP_TRY(hipGetLastError());
-    }
-    const int hz = h->setup.horizon;
-    // variants(): [0] <60,10,128>, [1] <120,10,256>, [2] <60,20,128>, [3] <120,20,256>, V2_WIDE <240,20,512>
-    o.variant = (hz <= 10) ? 0 : 2, o.cls_lo = 0, o.cls_hi = 10;
-    rc = launch(h, stream, o);
-    if (rc != HMPC_OK) return rc;
-    o.variant = (hz <= 10) ? 1 : 3, o.cls_lo = 11, o.cls_hi = (hz <= 10) ? 255 : 20;  // (> 20 at h <= 10 cannot occur)
-    rc = launch(h, stream, o);
-    if (rc != HMPC_OK) return rc;
-    if (hz > 10) {
-      o.variant = V2_WIDE, o.cls_lo = 21, o.cls_hi = 255;
-      rc = launch(h, stream, o);
-    }
-  } else {
-    int vi = 0;
-    (void)pick_variant(h, &vi);
-    if (variants()[vi].spill_stride == 0) rc = invalidate_handover_slots(h, stream);
-    if (rc == HMPC_OK) rc = launch(h, stream, o);
-  }
+  int rc = enqueue_fast(h, stream, pick_variant(h), by_class(h), o);
   if (rc != HMPC_OK || !repair) return rc;
-  LaunchOpt s;
-  s.d_index_list = h->d_flag_list;
-  s.n_list = h->batch < REPAIR_GRID_CAP ? h->batch : REPAIR_GRID_CAP;
-  {
-    int vsel = 0;
-    (void)pick_variant(h, &vsel);
-    if (vsel == V2_WIDE && s.n_list > REPAIR_GRID_CAP_WIDE) s.n_list = REPAIR_GRID_CAP_WIDE;  // (231 KB of global scratch per workgroup)
-  }
+  LaunchOpt s = device_list(h);
   s.warm = 1;  // (the block start: what differs from the fast variant is capacity, periodic rebuild of E, in-kernel perturbation)
   s.carry_wset = carry_wset;
-  s.d_list_count = h->d_flag_count;
-  // (1) continuation: instances whose working set outgrew the fast variant go on, from the state it handed over, on the variant
-  //     with 96 rows and block rounds of its own (two per CU); (2) the safe variant, cold, for everything still flagged -- what
-  //     the fast variant flagged for other reasons, and what outgrew the continuation variant as well
-  if (h->nc == 2 && h->handover && h->d_spill) {
-    LaunchOpt c = s;
-    c.continuation = true, c.resume = true;
-    rc = launch(h, stream, c);
-    if (rc != HMPC_OK) return rc;
-    s.skip_ok = 1;
-    static const bool cont_only = getenv("HMPC_DEBUG_CONT_ONLY") && getenv("HMPC_DEBUG_CONT_ONLY")[0] == '1';  // developer switch: what the continuation pass alone leaves
-    if (cont_only) return HMPC_OK;
-  }
+  bool cont = false;
+  rc = continuation_pass(h, stream, s, &cont);
+  if (rc != HMPC_OK) return rc;
+  if (cont) s.skip_ok = 1;
   if (h->device_repair == 2) return HMPC_OK;  // continuation only: the safe pass is left to hmpc_resolve_failed / hmpc_download
   // The safe pass over what is still flagged: cold, with every bound moved outward by SAFE_PASS_RELAX (1 + frac(0.618 row)) from the start.
   // What reaches it are the instances that cycle at degenerate vertices (the continuation's budget, a KKT check): perturbed, they
   // take ~150 iterations instead of up to 480, and the kernel's epilogue re-solves on the final working set with the EXACT bounds and
   // repeats the exact KKT check -- measured at 6x the input ranges: 8.8 -> 6.9 ms for the whole chain AND 3 -> 0 of 8 192 left flagged
   // (10x: 19.5 -> 14.6 ms, 10 -> 1); every one of them HMPC_S_OK, exact (profiles/r06/range_scale.txt).
-  s.relax = SAFE_PASS_RELAX, s.warm = 0;
-  {
-    static const char *dbg_relax = getenv("HMPC_DEBUG_SAFE_RELAX");  // developer A/B: another perturbation (0 = the exact, warm pass of before)
-    if (dbg_relax && *dbg_relax) s.relax = atof(dbg_relax), s.warm = (s.relax == 0.0) ? 1 : 0;
-  }
-  s.list_indefinite = true;
-  rc = launch_safe(h, stream, s);
+  s.relax = SAFE_PASS_RELAX, s.warm = 0, s.list_indefinite = true;
+  rc = safe_pass(h, stream, s);
   if (rc != HMPC_OK) return rc;
-  return enqueue_reg_steps(h, stream, s);
+  return device_reg_steps(h, stream, s);
 }
 
 extern "C" {
@@ -856,51 +848,24 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   // records whose sizes only the device knows (max_stance < 0): every group runs on the sweep variant of its size class, the one
   // hmpc_solve's size-class launches give its instances -- what keeps the results the bits of hmpc_solve's (a member whose gait
   // differs from its group's first record's may land in the other launch: it is reported there, never solved)
-  const bool by_class = h->max_stance < 0 && h->d_cls;
   const int vi = small ? V2_SWEEP_60 : V2_SWEEP_120;
-  const int groups = h->batch / group_size;
-  const size_t need = (size_t)groups * 36 * (size_t)variants()[vi].nt * sizeof(double);  // (V2_SWEEP_120 has the wider workgroups)
-  if (need > h->sweep_m_bytes) {
-    if (h->d_sweep_m) {
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipFree(h->d_sweep_m));
-      h->d_sweep_m = nullptr, h->sweep_m_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&h->d_sweep_m, need));
-    h->sweep_m_bytes = need;
-  }
+  const size_t need = (size_t)(h->batch / group_size) * 36 * (size_t)variants()[vi].nt * sizeof(double);  // (V2_SWEEP_120 has the wider workgroups)
+  int rc = grow(&h->d_sweep_m, &h->sweep_m_bytes, need, st, /*whole_device=*/false);
+  if (rc != HMPC_OK) return rc;
   const bool repair = h->device_repair != 0;
   if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count, 0, 2 * sizeof(unsigned int), st));
   h->order_valid = false, h->order_batch = 0;  // (natural order inside a sweep; the next ordinary solve starts from the predictor)
-  int rc = invalidate_handover_slots(h, st);  // (the sweep variants save nothing)
+  LaunchOpt o;
+  o.sweep_k = group_size, o.record_flagged = repair;
+  rc = enqueue_fast(h, st, vi, by_class(h), o);
+  if (rc != HMPC_OK || !repair) return rc;
+  // whatever a sweep flags is repaired as an independent instance (its record is complete): the cold safe pass (sweeps save nothing:
+  // no continuation), also under device-repair mode 2
+  LaunchOpt s = device_list(h);
+  s.warm = 0, s.list_indefinite = true;
+  rc = safe_pass(h, st, s);
   if (rc != HMPC_OK) return rc;
-  if (by_class && !h->cls_valid) {
-    hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, st, h->d_records, (int)h->stride,
-                       h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
-    HIP_TRY(hipGetLastError());
-  }
-  for (int pass = 0; pass < (by_class ? 2 : 1); ++pass) {
-    LaunchOpt o;
-    o.variant = by_class ? (pass == 0 ? V2_SWEEP_60 : V2_SWEEP_120) : vi, o.sweep_k = group_size, o.sweep_phase = 0;
-    if (by_class) o.cls_lo = (pass == 0) ? 0 : 11, o.cls_hi = (pass == 0) ? 10 : 255;  // (the classes of enqueue_solve's h <= 10 launches)
-    rc = launch(h, st, o);
-    if (rc != HMPC_OK) return rc;
-    o.sweep_phase = 1;
-    o.record_flagged = repair;
-    rc = launch(h, st, o);
-    if (rc != HMPC_OK) return rc;
-  }
-  if (!repair) return HMPC_OK;
-  // whatever a sweep flags is repaired as an independent instance (its record is complete): the cold safe pass
-  LaunchOpt s;
-  s.d_index_list = h->d_flag_list;
-  s.n_list = h->batch < REPAIR_GRID_CAP ? h->batch : REPAIR_GRID_CAP;
-  s.warm = 0;
-  s.d_list_count = h->d_flag_count;
-  s.list_indefinite = true;
-  rc = launch_safe(h, st, s);
-  if (rc != HMPC_OK) return rc;
-  return enqueue_reg_steps(h, st, s);
+  return device_reg_steps(h, st, s);
 }
 
 int hmpc_set_device_repair(hmpc_handle *h, int on) {
@@ -962,79 +927,68 @@ int hmpc_resolve_failed(hmpc_handle *h, int *n_resolved) {
   // (launch parameters; the handle's own warm-start setting is not touched)
   LaunchOpt so;
   so.d_index_list = d_idx, so.n_list = (int)idx.size(), so.warm = 1;  // (first pass: with the block start; the perturbed passes below start cold)
-  int rc = HMPC_OK;
-  if (h->nc == 2 && h->handover && h->d_spill) {
-    // continuation first (see enqueue_solve): instances with a hand-over slot go on where the fast variant stopped
-    LaunchOpt c = so;
-    c.continuation = true, c.resume = true;
-    rc = launch(h, h->last_stream, c);
-    if (rc != HMPC_OK) return rc;
-    so.skip_ok = 1;
-  }
+  bool cont = false;
+  int rc = continuation_pass(h, h->last_stream, so, &cont);
+  if (rc != HMPC_OK) return rc;
+  if (cont) so.skip_ok = 1;
   // (the same launch as the device-side chain's: cold, bounds perturbed by SAFE_PASS_RELAX, exact re-solve at its end -- see enqueue_solve)
   so.relax = SAFE_PASS_RELAX, so.warm = 0;
-  rc = launch_safe(h, h->last_stream, so);
+  rc = safe_pass(h, h->last_stream, so);
   if (rc != HMPC_OK) return rc;
   // ... then, for what is still flagged, the exact pass with the block start (the first safe pass of rounds 4-6a)
   so.relax = 0.0, so.warm = 1, so.skip_ok = 2;  // (an answer that is only ok-relaxed gets the exact attempt as well)
-  rc = launch_safe(h, h->last_stream, so);
+  rc = safe_pass(h, h->last_stream, so);
   so.skip_ok = 0;
   if (rc != HMPC_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->last_stream));
   if (n_resolved) *n_resolved = (int)idx.size();
-  {
-    // A Hessian that is not positive definite (found by the safe variants' sweeps: HMPC_S_INDEFINITE; the fast variants diverge on it
-    // and flag it through their KKT check): the reference's qpOASES run regularises -- H + rho I, then one more QP with the gradient
-    // g - rho x_1 (QProblem.cpp:1753-1860, QProblemB.cpp:1999-2031; KernelArgs::reg_step) -- and so do two more launches here
-    std::vector<int> indef;
+  // each later pass: copy the status words back, keep the members of idx whose code `keep` accepts, upload them, run `pass` over
+  // them (a copy of `so` with that list), synchronise; *ran = whether anything was kept
+  auto rerun = [&](auto keep, auto pass, bool *ran) -> int {
+    std::vector<int> sub;
     HIP_TRY(hipMemcpy(st.data(), h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int i : idx)
-      if (HMPC_STATUS_CODE(st[i]) == HMPC_S_INDEFINITE) indef.push_back(i);
-    if (!indef.empty()) {
-      HIP_TRY(hipMemcpy(d_idx, indef.data(), indef.size() * sizeof(int), hipMemcpyHostToDevice));
-      LaunchOpt ro = so;
-      ro.n_list = (int)indef.size(), ro.relax = 0.0, ro.warm = 1, ro.skip_ok = 0;
-      for (int step = 1; step <= 2; ++step) {
-        ro.reg_step = step;
-        rc = launch_safe(h, h->last_stream, ro);
-        if (rc != HMPC_OK) return rc;
-      }
-      HIP_TRY(hipStreamSynchronize(h->last_stream));
-      HIP_TRY(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));  // (the passes below index into the full list again)
-    }
-  }
+      if (keep(st[i])) sub.push_back(i);
+    *ran = !sub.empty();
+    if (sub.empty()) return HMPC_OK;
+    HIP_TRY(hipMemcpy(d_idx, sub.data(), sub.size() * sizeof(int), hipMemcpyHostToDevice));
+    LaunchOpt o = so;
+    o.n_list = (int)sub.size();
+    const int prc = pass(o);
+    if (prc != HMPC_OK) return prc;
+    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    return HMPC_OK;
+  };
+  bool ran = false;
+  // A Hessian that is not positive definite (found by the safe variants' sweeps: HMPC_S_INDEFINITE; the fast variants diverge on it
+  // and flag it through their KKT check): the reference's qpOASES run regularises, and so do two more launches here
+  rc = rerun([](uint32_t w) { return HMPC_STATUS_CODE(w) == HMPC_S_INDEFINITE; },
+             [&](const LaunchOpt &o) { return reg_steps(h, h->last_stream, o); }, &ran);
+  if (rc != HMPC_OK) return rc;
   // last resort for instances that cycle at a degenerate vertex even with the full-size working set: bounds moved outward
-  // by 1e-7, then 1e-6 (a different amount per row), reported as HMPC_S_OK_RELAXED
+  // by 1e-7, 1e-6, then 1e-5 (a different amount per row), reported as HMPC_S_OK_RELAXED.  For three contacts first a second level:
+  // instances whose working set outgrew even the LDS-resident safe variant (140 of 180 rows); once that has run, the relax levels
+  // run on the same variant (ultimate)
+  bool ultimate = false;
   if (h->nc == 3) {
-    // second level for three contacts: instances whose working set outgrew even the LDS-resident safe variant (140 of 180 rows)
-    std::vector<int> full;
-    HIP_TRY(hipMemcpy(st.data(), h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int i : idx)
-      if (HMPC_STATUS_CODE(st[i]) == HMPC_S_WORKSET) full.push_back(i);
-    if (!full.empty()) {
-      HIP_TRY(hipMemcpy(d_idx, full.data(), full.size() * sizeof(int), hipMemcpyHostToDevice));
-      so.n_list = (int)full.size(), so.ultimate = true;
-      rc = launch(h, h->last_stream, so);
-      if (rc != HMPC_OK) return rc;
-      HIP_TRY(hipStreamSynchronize(h->last_stream));
-    }
+    rc = rerun([](uint32_t w) { return HMPC_STATUS_CODE(w) == HMPC_S_WORKSET; },
+               [&](const LaunchOpt &o) { return safe_pass(h, h->last_stream, o, /*ultimate=*/true); }, &ultimate);
+    if (rc != HMPC_OK) return rc;
   }
   // (with the exact re-solve that ends a relaxed pass -- see the kernel -- a larger perturbation costs nothing when its working
   //  set turns out to be optimal for the exact bounds: such an instance is reported HMPC_S_OK, exact)
-  const double relax_levels[3] = {1e-7, 1e-6, 1e-5};
-  for (int lvl = 0; lvl < 3; ++lvl) {
-    std::vector<int> still;
-    HIP_TRY(hipMemcpy(st.data(), h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (int i : idx) {
-      const uint32_t c = HMPC_STATUS_CODE(st[i]);
-      if ((c == HMPC_S_MAXITER && !capped_by_caller(h, st[i])) || c == HMPC_S_INFEASIBLE || c == HMPC_S_KKT || c == HMPC_S_WORKSET) still.push_back(i);
-    }
-    if (still.empty()) break;
-    HIP_TRY(hipMemcpy(d_idx, still.data(), still.size() * sizeof(int), hipMemcpyHostToDevice));
-    so.n_list = (int)still.size(), so.relax = relax_levels[lvl], so.warm = 0;
-    rc = launch_safe(h, h->last_stream, so);
-    if (rc != HMPC_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->last_stream));
+  for (const double relax : {1e-7, 1e-6, 1e-5}) {
+    rc = rerun(
+        [&](uint32_t w) {
+          const uint32_t c = HMPC_STATUS_CODE(w);
+          return (c == HMPC_S_MAXITER && !capped_by_caller(h, w)) || c == HMPC_S_INFEASIBLE || c == HMPC_S_KKT || c == HMPC_S_WORKSET;
+        },
+        [&](LaunchOpt o) {
+          o.relax = relax, o.warm = 0;
+          return safe_pass(h, h->last_stream, o, ultimate);
+        },
+        &ran);
+    if (rc != HMPC_OK || !ran) return rc;
   }
   return HMPC_OK;
 }
@@ -1106,8 +1060,8 @@ int hmpc_debug_assemble(hmpc_handle *h, int index, int *n, int *m, int *var_ind,
                         float *lb, float *ub, float *x0, float *Acd, float *Bcd) {
   if (!h || index < 0 || index >= h->batch) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  int vi = 0;
-  const Variant &v = pick_variant(h, &vi);
+  const int vi = pick_variant(h);
+  const Variant &v = variants()[vi];
   if (!h->d_dbg_f) {
     HIP_TRY(hipMalloc(&h->d_dbg_f, sizeof(float) * (size_t)DBG_FLOATS_MAX));
     HIP_TRY(hipMalloc(&h->d_dbg_i, sizeof(int) * (2 + MAX_VARS_ANY)));
@@ -1115,7 +1069,7 @@ int hmpc_debug_assemble(hmpc_handle *h, int index, int *n, int *m, int *var_ind,
   HIP_TRY(hipMemset(h->d_dbg_i, 0, sizeof(int) * (2 + MAX_VARS_ANY)));
   LaunchOpt ao;
   ao.assemble_only = true, ao.dbg_index = index;
-  int rc = launch(h, 0, ao);
+  int rc = launch(h, 0, vi, ao);
   if (rc != HMPC_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
   std::vector<float> hf(v.dbg_floats);
@@ -1150,9 +1104,7 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
   {
     // the kernel reads H[i*ld + j], g[i] for i, j < the instance's reduced-variable count: ld must cover the widest one
     // (known for host-uploaded records; otherwise whatever the variant that will be launched can hold)
-    int vi = 0;
-    const Variant &v = pick_variant(h, &vi);
-    const int need = (h->max_stance >= 0) ? h->max_stance : v.nmax;
+    const int need = (h->max_stance >= 0) ? h->max_stance : variants()[pick_variant(h)].nmax;
     if (ld < need) return HMPC_E_ARG;
   }
   HIP_TRY(hipSetDevice(h->device));
@@ -1172,10 +1124,7 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
   h->d_ext_H = dH, h->d_ext_g = dg, h->d_ext_Fc = dF, h->ext_ld = ld;
   LaunchOpt xo;
   xo.carry_wset = false;
-  int vi = 0;
-  (void)pick_variant(h, &vi);
-  int rc = variants()[vi].spill_stride == 0 ? invalidate_handover_slots(h, h->last_stream) : HMPC_OK;
-  if (rc == HMPC_OK) rc = launch(h, h->last_stream, xo);
+  const int rc = enqueue_fast(h, h->last_stream, pick_variant(h), /*classes=*/false, xo);
   hipError_t e = hipStreamSynchronize(h->last_stream);
   h->d_ext_H = h->d_ext_g = h->d_ext_Fc = nullptr;
   h->ext_ld = 0;
@@ -1210,7 +1159,7 @@ int hmpc_debug_phase_cycles(hmpc_handle *h, long long *cycles /*[batch][NPROF = 
   if (!h->d_prof) HIP_TRY(hipMalloc(&h->d_prof, nb));
   HIP_TRY(hipMemset(h->d_prof, 0, nb));
   // (with the device-side repair on, the whole chain: an instance's slot then holds the numbers of the LAST variant that ran it)
-  int rc = h->device_repair ? enqueue_solve(h, h->last_stream, false) : launch(h, h->last_stream, LaunchOpt());
+  int rc = h->device_repair ? enqueue_solve(h, h->last_stream, false) : launch(h, h->last_stream, pick_variant(h), LaunchOpt());
   if (rc != HMPC_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->last_stream));
   HIP_TRY(hipMemcpy(cycles, h->d_prof, (size_t)h->batch * hmpc::NPROF * sizeof(long long), hipMemcpyDeviceToHost));

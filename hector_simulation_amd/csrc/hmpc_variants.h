@@ -19,40 +19,39 @@ constexpr int HMPC_QCAP_3C = 96;     // ... of the fast three-contact variant (2
 
 typedef void (*kernel_fn)(hmpc::KernelArgs);
 
+// FAST: the first pass of every solve (on the hand-over shape it saves a working set that outgrew it); CONT: resumes those; SAFE:
+// re-solves what is still flagged; SWEEP: command sweeps (kernel MODE 1: a workgroup per chunk of instances sharing state and gait)
+enum class Role { FAST, CONT, SAFE, SWEEP };
 struct Variant {
   int nmax, hmax, nt, qcap, nc;
-  int mode;  // 0: a workgroup per instance; 1: command sweeps (a workgroup per chunk of instances sharing state and gait)
-  kernel_fn solve, assemble;
+  Role role;
+  kernel_fn solve, assemble;  // assemble: the assembly-only debug kernel (FAST variants only, nullptr otherwise)
   size_t smem;
   int dbg_floats;
-  // hand-over of a full working set (KernelArgs::spill): bytes of one slot when this variant SAVES its state (fast 120-variable
-  // variants), 0 otherwise; resumes = this variant can continue from such a slot (the safe variants of the same shape)
+  // bytes of one hand-over slot (KernelArgs::spill) when this variant SAVES its state (FAST on the hand-over shape), 0 otherwise
   size_t spill_stride;
-  bool resumes;
 };
 
-// index = position in hmpc_capi.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, MODE), group = translation unit that builds it.
-// MODE 1 = command sweeps (a workgroup solves a chunk of instances that share state and gait on one inverse, hmpc_kernel.h).
+// index = position in hmpc_capi.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE), group = translation unit that builds it.
 // The groups are balanced by compile time (the two-blocks-per-thread and 512-thread variants are the slow ones).
 #define HMPC_VARIANT_TABLE(X)                             \
-  X(0, 0, 60, 10, 128, 60, 2, 1, 0)                       \
-  X(1, 0, 120, 10, 256, HMPC_QCAP_FAST, 2, 1, 0)          \
-  X(2, 0, 60, 20, 128, 60, 2, 1, 0)                       \
-  X(3, 1, 120, 20, 256, HMPC_QCAP_FAST, 2, 1, 0)          \
-  X(4, 1, 120, 10, 256, 120, 2, 1, 0)                     \
-  X(5, 1, 120, 20, 256, 120, 2, 1, 0)                     \
-  X(6, 2, 180, 10, 256, HMPC_QCAP_3C, 3, 2, 0)            \
-  X(7, 3, 180, 10, 512, 140, 3, 1, 0)                     \
-  X(8, 2, 180, 10, 512, 100, 3, 1, 0)                     \
-  X(9, 3, 240, 20, 512, HMPC_QCAP_WIDE, 2, 2, 0)          \
-  X(10, 3, 240, 20, 512, 0, 2, 2, 0)                      \
-  X(11, 2, 180, 10, 512, 0, 3, 1, 0)                      \
-  X(12, 0, 120, 10, 256, HMPC_QCAP_CONT, 2, 1, 0)         \
-  X(13, 1, 120, 20, 256, HMPC_QCAP_CONT, 2, 1, 0)         \
-  X(14, 2, 120, 10, 256, HMPC_QCAP_FAST, 2, 1, 1)         \
-  X(15, 3, 60, 10, 128, 60, 2, 1, 1)
+  X(0, 0, 60, 10, 128, 60, 2, 1, FAST)                    \
+  X(1, 0, 120, 10, 256, HMPC_QCAP_FAST, 2, 1, FAST)       \
+  X(2, 0, 60, 20, 128, 60, 2, 1, FAST)                    \
+  X(3, 1, 120, 20, 256, HMPC_QCAP_FAST, 2, 1, FAST)       \
+  X(4, 1, 120, 10, 256, 120, 2, 1, SAFE)                  \
+  X(5, 1, 120, 20, 256, 120, 2, 1, SAFE)                  \
+  X(6, 2, 180, 10, 256, HMPC_QCAP_3C, 3, 2, FAST)         \
+  X(7, 3, 180, 10, 512, 140, 3, 1, SAFE)                  \
+  X(8, 3, 240, 20, 512, HMPC_QCAP_WIDE, 2, 2, FAST)       \
+  X(9, 3, 240, 20, 512, 0, 2, 2, SAFE)                    \
+  X(10, 2, 180, 10, 512, 0, 3, 1, SAFE)                   \
+  X(11, 0, 120, 10, 256, HMPC_QCAP_CONT, 2, 1, CONT)      \
+  X(12, 1, 120, 20, 256, HMPC_QCAP_CONT, 2, 1, CONT)      \
+  X(13, 2, 120, 10, 256, HMPC_QCAP_FAST, 2, 1, SWEEP)     \
+  X(14, 3, 60, 10, 128, 60, 2, 1, SWEEP)
 constexpr int HMPC_VARIANT_GROUPS = 4;
 
-#define HMPC_DECLARE_VARIANT(IDX, GRP, NMAX, HMAX, NT, QCAP, NC, BPT, MODE) Variant hmpc_variant_##IDX();
+#define HMPC_DECLARE_VARIANT(IDX, GRP, NMAX, HMAX, NT, QCAP, NC, BPT, ROLE) Variant hmpc_variant_##IDX();
 HMPC_VARIANT_TABLE(HMPC_DECLARE_VARIANT)
 #undef HMPC_DECLARE_VARIANT

@@ -1,12 +1,11 @@
 #!/usr/bin/env python3
-"""Developer tool: what the continuation pass alone does (HMPC_DEBUG_CONT_ONLY=1: the safe pass behind it is skipped).
+"""Developer tool: what the continuation pass alone does (set_device_repair(2): the safe pass behind it is skipped).
     python scripts/dev/cont_probe.py [scale] [batch]"""
 import os
 import sys
 
 import numpy as np
 
-os.environ["HMPC_DEBUG_CONT_ONLY"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
@@ -28,7 +27,7 @@ t0 = m0.time_solve(1)
 m0.close()
 m = interface.BatchedMPC(synthetic.DT_MPC, h, synthetic.F_MAX, B)
 m.set_auto_resolve(False)
-m.set_device_repair(True)
+m.set_device_repair(2)
 m.upload(rec)
 m.solve()
 _, st1 = m.download()

@@ -138,14 +138,17 @@ def test_developer_switches_cannot_reach_the_product_library():
         assert gone not in ksrc, gone
 
 
-def test_every_kernel_variant_is_built_by_exactly_one_translation_unit():
-    """csrc/hmpc_variants.h: sixteen variants over HMPC_VARIANT_GROUPS groups, build.py compiles one unit per group."""
+def test_each_of_the_fifteen_variants_is_built_by_exactly_one_translation_unit():
+    """csrc/hmpc_variants.h: fifteen variants (each with its role) over HMPC_VARIANT_GROUPS groups, as many as the host's
+    variants() holds; build.py compiles one unit per group."""
     from hector_simulation_amd import build
 
     hdr = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_variants.h")).read()
-    rows = re.findall(r"X\((\d+), (\d+),", hdr)
-    assert [int(i) for i, _ in rows] == list(range(16))
-    groups = sorted({int(g) for _, g in rows})
+    rows = re.findall(r"X\((\d+), (\d+),[^)]*, (FAST|CONT|SAFE|SWEEP)\)", hdr)
+    assert [int(i) for i, _, _ in rows] == list(range(15))
+    capi = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_capi.hip")).read()
+    assert "constexpr int N_VARIANTS = 15;" in capi
+    groups = sorted({int(g) for _, g, _ in rows})
     assert groups == list(range(build.VARIANT_GROUPS))
     assert f"HMPC_VARIANT_GROUPS = {build.VARIANT_GROUPS}" in hdr
     units = build.compile_commands("/tmp/x", "hipcc")

@@ -33,7 +33,7 @@ def _sweep_records(groups, k, h, seed, scale):
 
 def _case(name):
     """(h, records of A, records of B, sweep group size of B or 0, device-resident records, wide[i] of B)"""
-    if name == "sweep":    # A: standing h = 10 at 10x (the fast 120-variable variant saves); B: a command sweep at 6x (variants 14 / 15)
+    if name == "sweep":    # A: standing h = 10 at 10x (the fast 120-variable variant saves); B: a command sweep at 6x (variants 13 / 14)
         rec_a = records.pack_records(hard_batch(NB, 10, "standing", 17, 10), 10)
         return 10, rec_a, _sweep_records(NB // 8, 8, 10, 23, 6), 8, False, np.zeros(NB, dtype=bool)
     if name == "wide":     # A: single support h = 20 at 10x (variant 3 saves); B: double support h = 20 at 6x (the wide variant)
