@@ -240,8 +240,8 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
   // EGLOBAL variants keep NMAX (NMAX + 1) / 2 doubles of global scratch per WORKGROUP (231 KB for 240 variables): a host-driven
   // safe pass over thousands of flagged instances goes through the list in chunks that reuse one bounded buffer (stream order
   // keeps the chunks apart).  The device-driven pass (d_list_count) is one launch, capped by its caller.
-  const int chunk = (v.qcap == 0 && o.d_index_list && !o.d_list_count && grid_all > EGLOBAL_CHUNK) ? EGLOBAL_CHUNK : grid_all;
-  if (v.qcap == 0) {  // EGLOBAL: one slice of packed triangle per workgroup of this launch
+  const int chunk = (v.e_global && o.d_index_list && !o.d_list_count && grid_all > EGLOBAL_CHUNK) ? EGLOBAL_CHUNK : grid_all;
+  if (v.e_global) {  // one slice of packed triangle per workgroup of this launch
     const int rc = grow(&h->d_escratch, &h->e_bytes, (size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double), stream, false);
     if (rc != HMPC_OK) return rc;
   }
@@ -833,7 +833,7 @@ int hmpc_solve(hmpc_handle *h, void *stream) {
   return enqueue_solve(h, (hipStream_t)stream, /*carry_wset=*/true);
 }
 
-// Command sweeps (MODE 1 kernels): phase 0 forms every group's M = H^-1 once (one workgroup per group) and leaves it in HBM, phase 1
+// Command sweeps (the SWEEP variants): phase 0 forms every group's M = H^-1 once (one workgroup per group) and leaves it in HBM, phase 1
 // solves every instance with its group's M (one workgroup per instance, stages H and S skipped).
 int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   if (!h || group_size < 1) return HMPC_E_ARG;

@@ -4,7 +4,7 @@
 //   update_problem_data -> solve_mpc -> qpOASES::QProblem::init
 //   (ConvexMPC/convexMPC_interface.cpp:83-103, ConvexMPC/SolverMPC.cpp:371-738, third_party/qpOASES/src/QProblem.cpp:316).
 //
-// Compiled for three waves per SIMD where the LDS footprint allows it (168 VGPRs; see WAVES_PER_EU_* below).
+// Compiled for three waves per SIMD where the LDS footprint allows it (168 VGPRs; VariantTraits::WAVES_PER_EU below).
 // Phases (all state lives in LDS / registers; HBM sees only the ~716 B record in and 12h floats + 1 word out):
 //   A  assembly in binary32 under the HMPC-A1 arithmetic contract (bit-identical to the CPU oracle):
 //      trig -> scalar algebra -> Acd^k, Phi_k = Acd^k Bcd -> tracking error -> swing elimination tables
@@ -34,9 +34,6 @@
 
 #include <type_traits>
 
-#ifndef HMPC_QCAP_CONT
-#define HMPC_QCAP_CONT 96  // working-set capacity of the continuation variant of the 120-variable shapes (70 KB of LDS: two workgroups per CU)
-#endif
 #ifndef HMPC_REFINE
 #define HMPC_REFINE 1  // corrections u += E (b_W - N_W x(u)) applied to the multipliers of the final working set
 #endif
@@ -102,7 +99,7 @@ struct Smem {
   // working-set capacity (packed Schur inverse E); QCAP = NMAX can never overflow.  QCAP = 0: capacity NMAX with E in GLOBAL
   // memory (a per-workgroup scratch slice, L2-resident) instead of LDS -- the safe pass of the wide variant, whose 240 x 240
   // packed triangle (231 KB) no CU's LDS holds
-  static constexpr bool EGLOBAL = (QCAP == 0);
+  static constexpr bool EGLOBAL = (QCAP == 0);  // (the one place that reads QCAP == 0: everything else asks EGLOBAL)
   static constexpr int QMAX = EGLOBAL ? NMAX : QCAP;
   static constexpr int EP_LDS = EGLOBAL ? 1 : QMAX * (QMAX + 1) / 2;
   static constexpr int RECW = ((RecLayout<NC>::NF + 12 * HMAX) * 4 + NC * HMAX + 15) / 16 * 4;  // record words
@@ -273,27 +270,10 @@ __device__ inline void quat_to_R(const float *q, float *R, float *Rt) {
 }
 
 }  // namespace hmpc
-// Waves per SIMD ("execution unit") each variant is compiled for -- the second argument of HIP's __launch_bounds__ --
-// which fixes the register budget (512 / waves):
-//   fast variants with h <= 10 (256 threads / 120 variables / working set <= 64 rows: 49 KB LDS; 128 threads / 60
-//   variables: 26 KB LDS): THREE waves per SIMD = 168 VGPRs = three resp. six resident workgroups per CU.  The kernel is
-//   bound by dependent-instruction latency and barrier phases, not by issue: the third wave is worth +30 % (profiles/r02).
-//   Everything else (h = 20 scratch, safe variants, 512 threads): two.
-// Tuning constants.  (Until round 6 this was a list of 29 `#ifndef HMPC_*` A/B switches; every one whose other side had been
-// measured worse -- profiles/r02 ... r05 keep the numbers -- is now simply the code: FLIP4, PIN_SWEEP, CHAIN_BALANCE,
-// MFS_PUBLISH_FIRST, S0_ACTIVE_ROWS, REFINE_FROM_X, MFS_DEAL_PAIRED, MFS_RCP_NEWTON = 2, MFS_PST_PAD = 18, SCHUR_MFMA*, BLOCK_FRICTION,
-// MFMA_SWEEP*, and the wrong-numbers timing switches MFS_NO_* / MFS_ONLY_WAVE.  What is left as a macro is compiled with a
-// non-default value by tests/test_switches_compile.py so that it cannot rot.)
-namespace hmpc {
-constexpr int WAVES_PER_EU_256 = 3, WAVES_PER_EU_128 = 3;  // fast variants: three waves per SIMD (168 VGPRs) where the LDS allows it
-constexpr int BLOCK_ROUNDS_2C = 2;     // block start: rounds at most, 120-variable variants (a third instantiation: 86 spilled registers)
-constexpr int BLOCK_ROUNDS_3C = 3;     // ... three-contact variant
-constexpr int BLOCK_MIN_NEW_2C = 3;    // a further round needs at least this many newly violated rows (5 until the Schur matrix went to the matrix cores: profiles/r05/block_round_ab.txt)
-constexpr int BLOCK_MIN_NEW_3C = 2;    // ... three-contact variant (its single-row iteration is dearer)
-constexpr int EPT_3C = 7;              // three-contact variant on 256 threads: packed-triangle entries per thread in the register-resident Schur inversion
-constexpr int MFS_GT = 4;              // matrix-core sweeps, 20 tiles per wave: tiles per group of operand reads (two groups in flight)
-constexpr int MFS_PST_PAD = 18;        // padding of a pivot-panel row in doubles (see MfsPanel; 16 was the round-4 layout: 4-way bank conflicts on the column publishes)
-}  // namespace hmpc
+// Tuning constants.  (Until round 6 this was a list of 29 `#ifndef HMPC_*` A/B switches; every one whose other side had been measured worse -- profiles/r02
+// ... r05 keep the numbers -- is now simply the code: FLIP4, PIN_SWEEP, CHAIN_BALANCE, MFS_PUBLISH_FIRST, S0_ACTIVE_ROWS, REFINE_FROM_X, MFS_DEAL_PAIRED,
+// MFS_RCP_NEWTON = 2, MFS_PST_PAD = 18, SCHUR_MFMA*, BLOCK_FRICTION, MFMA_SWEEP*, and the wrong-numbers timing switches MFS_NO_* / MFS_ONLY_WAVE.  What is left as
+// a macro is compiled with a non-default value by tests/test_switches_compile.py so that it cannot rot.  What depends on the variant: VariantTraits below.)
 #ifndef HMPC_EARLY_HANDOVER_MARGIN
 #define HMPC_EARLY_HANDOVER_MARGIN 8  // fast variants: candidates beyond the block start's capacity that send an instance to the continuation variant at once
 #endif
@@ -307,6 +287,102 @@ constexpr int MFS_PST_PAD = 18;        // padding of a pivot-panel row in double
 #define HMPC_CONT_ROUNDS 4       // continuation variant: block rounds a resumed solve runs before its single-row iteration (0 .. 4)
 #endif
 namespace hmpc {
+constexpr int MFS_GT = 4;              // matrix-core sweeps, 20 tiles per wave: tiles per group of operand reads (two groups in flight)
+constexpr int MFS_PST_PAD = 18;        // padding of a pivot-panel row in doubles (see MfsPanel; 16 was the round-4 layout: 4-way bank conflicts on the column publishes)
+
+// ---------------------------------------------------------------------------------------------------------------
+// What a variant IS: every fact the kernel, make_variant (hmpc_variants.hip) and the host derive from a row (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE) of the
+// variant table (hmpc_variants.h), defined HERE once; the kernel body only reads these names.  Role first, shape second: what a variant does in a solve follows
+// from its ROLE, what it can afford (registers, LDS, threads) from its shape.  ASM_ONLY: the assembly-only debug kernel of a FAST row (no solve: all that is off).
+template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT, Role ROLE, bool ASM_ONLY = false>
+struct VariantTraits {
+  using SM = Smem<NMAX, HMAX, NT, QCAP, NC, BPT>;
+  // ---- the shapes
+  static constexpr bool WALK_SHAPE = NT == 128;     // 60 variables on two waves (walking: one foot down); first pass only -- the safe pass of two-contact batches runs on the 120-variable SAFE variants
+  static constexpr bool HANDOVER_SHAPE = SM::MFS2;  // 120 variables on four waves, one register block per thread: FAST saves a full working set, CONT resumes from it, SAFE re-solves
+  static constexpr bool THREE_CONTACT = NC == 3;    // two feet + hand, 180 variables
+  static constexpr bool WIDE_SHAPE = NMAX == 240;   // double support over h = 11 .. 20
+  static constexpr bool EIGHT_WAVES = NT >= 512;
+  static constexpr bool EGLOBAL = SM::EGLOBAL;      // E in KernelArgs::e_scratch (the host's Variant::e_global)
+  static constexpr bool NO_OVERFLOW = EGLOBAL || QCAP >= NMAX;  // the working set cannot overflow (true of the 60-variable FAST / SWEEP variants as well: QCAP = NMAX)
+  // Waves per SIMD ("execution unit") the variant is compiled for -- the second argument of HIP's __launch_bounds__ -- which fixes the register budget
+  // (512 / waves).  Fast variants with h <= 10 (256 threads / 120 variables / working set <= 64 rows: 49 KB LDS; 128 threads / 60 variables: 26 KB LDS): THREE
+  // waves per SIMD = 168 VGPRs = three resp. six resident workgroups per CU, whose LDS must fit the CU's 160 KB.  The kernel is bound by dependent-instruction
+  // latency and barrier phases, not by issue: the third wave is worth +30 % (profiles/r02).  Everything else (h = 20 scratch, safe variants, 512 threads): two.
+  static constexpr bool THREE_WAVES = BPT == 1 && !EIGHT_WAVES && sizeof(SM) * (size_t)(3 * 256 / NT) <= (size_t)160 * 1024;
+  static constexpr int WAVES_PER_EU = THREE_WAVES ? 3 : 2;
+  // Per-thread constants recomputed at every use instead of held in a register (LazyInt below): LAZY, with two blocks per thread (144 registers of matrix);
+  // LAZY_IDX, the integer roles only, also FAST, SWEEP and CONT on the hand-over shape (exactly on their 168-register budget), not its SAFE variants
+  static constexpr bool LAZY = BPT == 2, LAZY_IDX = LAZY || (HANDOVER_SHAPE && ROLE != Role::SAFE);
+
+  // ---- the role: command sweeps, hand-over of a full working set (KernelArgs::spill, SpillLayout), passes over a list of flagged instances
+  static constexpr bool SWEEP = ROLE == Role::SWEEP;  // the two sweep phases (see hmpc_kernel); otherwise the FAST variant of its shape
+  // SAVES: a violated row while the working set is full -> the live Goldfarb-Idnani state goes to the instance's slot.  (Variant 13, the SWEEP row of the
+  // shape, compiles the save path too although the host never arms it: SPILL_STRIDE 0, args.spill_slot == nullptr.)
+  static constexpr bool SAVES = !ASM_ONLY && HANDOVER_SHAPE && (ROLE == Role::FAST || SWEEP);
+  static constexpr size_t SPILL_STRIDE = (SAVES && ROLE == Role::FAST) ? SpillLayout<SM, NT, BPT>::stride_for(QCAP) : 0;  // Variant::spill_stride
+  // RESUMES: the continuation variant (96 rows, two per CU) takes over what the fast variants hand over, with block rounds of its own (up to its 96 rows at
+  // once, the Schur matrix as 6 x 6 tiles on the matrix cores) and an iteration budget, and flags what outgrows it in turn for the safe variant.  Instances
+  // of its launch without a valid slot start cold (resume == 1), which is why it has MFMA_SWEEP.
+  static constexpr bool RESUMES = ROLE == Role::CONT;
+  // every variant launched over a list of flagged instances honours the list protocol (skip_ok, reg_step) -- variant 7, the 140-row three-contact one,
+  // because it is a SAFE row like the others; the first-pass variants never see it and do not compile it
+  static constexpr bool LISTED = ROLE == Role::SAFE || RESUMES;
+  // LONGRUN: the SAFE variants whose working set cannot overflow -- what hmpc_resolve_failed / the device-side repair launch last (always cold), the only
+  // ones that ever run for hundreds of iterations.  Scalar sweeps, in-place inversion beyond the block start's capacity, KKT tolerance 2e-5 -- and
+  // (REGULARISES) they answer a Hessian that is not positive definite the way the reference's qpOASES run does (KernelArgs::reg_step).  Variant 7 is a SAFE
+  // row whose 140 rows CAN overflow: LISTED, but neither of these (a regularisation launch leaves its instances as they are).
+  // REFRESHES: E rebuilt every REFRESH_EVERY changes (stage Q; not the continuation variant: measured no difference at 6x, and a seventh instantiation of the round costs it 113 spilled registers)
+  static constexpr bool LONGRUN = ROLE == Role::SAFE && NO_OVERFLOW, REGULARISES = LONGRUN, REFRESHES = LONGRUN;
+  // Anti-cycling (the variants that run the hard instances: continuation and safe).  At a degenerate vertex -- several rows active with zero multipliers --
+  // round-off can make the dual iteration drop and re-add the same rows with zero-length steps until the iteration bound (seen: 600 iterations on the
+  // continuation variant, 1 664 on the safe one, each the whole tail of its launch).  In exact arithmetic a row is added at most 3 times per solve in all but
+  // the genuinely cycling instances (scripts/dev/emulate_rounds.py, 6x and 10x the input ranges), so a row the single-row iteration has already added
+  // HMPC_READD_LIMIT times is set aside like a redundant row: the final KKT check looks at every row again and decides.
+  static constexpr bool ANTICYCLE = (LONGRUN || RESUMES) && HMPC_READD_LIMIT > 0;
+  // Iteration bound 10 m + 64 instead of 4 m + 16: the safe variants may take as long as a cold qpOASES run (nWSR up to ~330 seen), so may whatever cannot hand its
+  // solve on (the 60-variable first pass) -- and the wide FAST variant 8 has it since it shared the literal "QCAP >= 140" with variant 7, by accident or not
+  static constexpr bool ITER_LONG = ROLE == Role::SAFE || NO_OVERFLOW || WIDE_SHAPE;
+
+  // ---- stage S, M = H^-1.  Matrix-core sweeps (4 x 4 block pivots, 16 x 16 tiles read straight from the staging of H): every variant of the hand-over shape
+  // but the SAFE ones.  The safe-pass variants keep the scalar sweeps: 4 x 4 block pivots apply an explicitly inverted pivot block, whose forward error carries
+  // cond(D) -- at 10x the nominal input ranges that showed as forces up to 9e-5 from qpOASES in the safe pass (7e-8 with scalar pivots), while nominal inputs
+  // are unaffected (5.8e-8 either way) and whatever the fast variants get wrong beyond 2e-6 is caught by their KKT check and handed to the safe pass anyway.
+  static constexpr bool MFMA_SWEEP = !ASM_ONLY && HANDOVER_SHAPE && ROLE != Role::SAFE;
+  // ... and the FAST three-contact variant (180 variables, two blocks per thread: 78 tiles, 20 per wave) and the wide one (Smem::MFS3).  Their staging of H
+  // holds the block-diagonals in two passes, so the register blocks are filled as for the scalar sweeps and turned into tiles in stage S.
+  static constexpr bool MFMA_SWEEP3 = !ASM_ONLY && SM::MFS3 && ROLE == Role::FAST;
+  static constexpr int MFS3_NTG = (NMAX + 15) / 16;
+
+  // ---- stage W, the block start.  Rounds at most: walking ~1.6 iterations per solve, nothing to gain: one; three contacts: three (1.13 -> 1.18 M solves/s
+  // over two); everything else two (a third one is worth <1 % on 120 variables and its third copy of the phase tips the register allocation of the 168-VGPR
+  // variant over: 86 spilled registers, 1.43 -> 1.78 ms)
+  static constexpr int BLOCK_ROUNDS = WALK_SHAPE ? 1 : THREE_CONTACT ? 3 : 2;
+  static constexpr int CONT_ROUNDS = HMPC_CONT_ROUNDS;  // block rounds of a resumed solve (the continuation variant: 256 VGPRs, a loop fits)
+  static constexpr bool BLOCK_FRICTION = !WALK_SHAPE;   // friction rows (0-3) enter the block start as well
+  // a further round needs at least this many newly violated rows (two contacts: 5 until the Schur matrix went to the matrix cores, profiles/r05/block_round_ab.txt; three contacts: its single-row iteration is dearer)
+  static constexpr int BLOCK_MIN_NEW = THREE_CONTACT ? 2 : 3;
+  // Schur matrix of the block start on the matrix cores (schur_invert), NTGS x NTGS tiles of 16 rows: 6 = the continuation variant's 96 rows, 5 = 80 rows on
+  // eight waves (the wide variant and variant 7), 4 = 64 rows with three contacts on 256 threads, 3 = 48 rows for the 120-variable variants.  Not the
+  // 128-thread variants (measured slower there, profiles/r05/schur_128_ab.txt), not the LONGRUN ones (register budget).
+  static constexpr int NTGS = RESUMES ? 6 : EIGHT_WAVES ? 5 : THREE_CONTACT ? 4 : 3;
+  static constexpr bool SCHUR_MFMA = !LONGRUN && !WALK_SHAPE && SM::QMAX >= 16 * NTGS;
+  // ... otherwise register-resident, two pivots per barrier: EPT packed-triangle entries per thread, which bound the rows a round can take: KBMAX (KBMAX + 1) / 2
+  // <= EPT NT.  (7 entries = 59 rows were the three-contact variant's on 256 threads; it inverts on the matrix cores now.)
+  static constexpr int EPT = 5;
+  static constexpr int KBMAX = SCHUR_MFMA ? 16 * NTGS : EIGHT_WAVES ? 71 : WALK_SHAPE ? 34 : 45;  // rows of a block round (LONGRUN: beyond it in place, up to QMAX)
+
+  // ---- what a row of the table must satisfy
+  static_assert(sizeof(SM) <= 160 * 1024, "LDS budget of a gfx950 CU");
+  static_assert(BPT == 1 || EIGHT_WAVES || sizeof(SM) <= 80 * 1024, "two workgroups per CU");
+  static_assert(SM::NG * (SM::NG + 1) / 2 <= BPT * NT && SM::MMAX <= NT && NMAX <= NT, "threads per block / constraint row / variable");
+  static_assert((SCHUR_MFMA || KBMAX * (KBMAX + 1) / 2 <= EPT * NT) && KBMAX <= SM::QMAX, "block start capacity");
+  static_assert(!ASM_ONLY || ROLE == Role::FAST, "assembly-only debug kernels belong to the FAST rows");
+  static_assert(!SWEEP || (!ASM_ONLY && BPT == 1 && NC == 2 && !EGLOBAL), "command sweeps: the fast two-contact shapes");
+  static_assert(!(HANDOVER_SHAPE && (ROLE == Role::FAST || SWEEP)) || QCAP < HMPC_QCAP_CONT, "a FAST / SWEEP variant on the hand-over shape saves a full working set for the CONT variant to resume: its capacity (HMPC_QCAP_FAST) must be below HMPC_QCAP_CONT");
+  static_assert(!RESUMES || (HANDOVER_SHAPE && QCAP >= HMPC_QCAP_CONT && QCAP < NMAX), "a CONT variant exists only on the hand-over shape, with at least HMPC_QCAP_CONT rows and fewer than variables");
+  static_assert(!(HANDOVER_SHAPE && ROLE == Role::SAFE) || NO_OVERFLOW, "the SAFE variant of the hand-over shape ends the chain: its working set cannot overflow");
+};
 
 // A per-thread constant derived from threadIdx.x.  LAZY = false: an ordinary register.  LAZY = true (the two-blocks-per-thread
 // variants, whose 144 registers of matrix leave no room for long-lived scalars): recomputed at every use from an opaque
@@ -930,12 +1006,6 @@ __device__ __forceinline__ void schur_invert(SchurPanel<NTG> &SP, const int k0, 
   schur_load<NTG, NWV, WV>(acc, k0, Ep, SP.kexp);
   mfs_steps<NTG, NWV, WV, true>(SP.pn, acc, k0);
   schur_store<NTG, NWV, WV>(acc, k0, Ep, SP.kexp);
-}
-
-// three waves per SIMD = 3 (256 threads) or 6 (128 threads) workgroups per CU: their LDS must fit the CU's 160 KB
-template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT>
-constexpr bool fits_three_waves() {
-  return BPT == 1 && sizeof(Smem<NMAX, HMAX, NT, QCAP, NC, BPT>) * (size_t)(3 * 256 / NT) <= (size_t)160 * 1024;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1718,8 +1788,8 @@ __device__ __forceinline__ void stage_h(Smem<NMAX, HMAX, NT, QCAP, NC, BPT> &S, 
   }
 }
 
-// MODE 0: the product path, one workgroup = one independent instance.
-// MODE 1: COMMAND SWEEPS (hmpc_solve_command_sweep).  The batch is groups of args.sweep_k consecutive records that share
+// Every role but SWEEP: the product path, one workgroup = one independent instance.  (What a variant does is read off VariantTraits, VT:: below.)
+// Role SWEEP: COMMAND SWEEPS (hmpc_solve_command_sweep).  The batch is groups of args.sweep_k consecutive records that share
 // everything but the reference trajectory -- state, feet, joints, weights, gait table (ConvexMPCLocomotion.cpp:351-406 builds the
 // trajectory from the commands; SolverMPC.cpp:398-447, 488-570 builds A_qp, B_qp, H and the constraint block from the state and
 // the gait alone) -- so H and its inverse M are a property of the GROUP.  Two launches of this kernel:
@@ -1727,13 +1797,12 @@ __device__ __forceinline__ void stage_h(Smem<NMAX, HMAX, NT, QCAP, NC, BPT> &S, 
 //     group's slot in HBM (36 x NT doubles, the register blocks' own layout, coalesced), nothing else;
 //   phase 1, one workgroup per INSTANCE (the chip stays as full as for independent solves): stage A on the instance's own
 //     record (its own g, the same chains), M read from its group's slot instead of stages H and S (55 % of an independent solve),
-//     then stages W and Q as they stand.  Same operands, same instructions: forces and status words are bit-identical to MODE 0's.
+//     then stages W and Q as they stand.  Same operands, same instructions: forces and status words are bit-identical to the FAST variant's.
 //   A record that differs from its group's first one anywhere but in the trajectory is not solved (HMPC_S_SWEEP_MISMATCH).
-template <int NMAX, int HMAX, int NT, int QCAP, bool ASM_ONLY, int NC = 2, int BPT = 1, int MODE = 0>
-__global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, QCAP, NC, BPT>()) ? (NT == 128 ? WAVES_PER_EU_128 : WAVES_PER_EU_256) : 2) void hmpc_kernel(KernelArgs args) {
-  using SM = Smem<NMAX, HMAX, NT, QCAP, NC, BPT>;
-  constexpr bool SWEEP = (MODE == 1);
-  static_assert(!SWEEP || (!ASM_ONLY && BPT == 1 && NC == 2 && QCAP != 0), "command sweeps: the fast two-contact variants");
+template <int NMAX, int HMAX, int NT, int QCAP, bool ASM_ONLY, int NC = 2, int BPT = 1, Role ROLE = Role::FAST>
+__global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, ROLE, ASM_ONLY>::WAVES_PER_EU)) void hmpc_kernel(KernelArgs args) {
+  using VT = VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, ROLE, ASM_ONLY>;
+  using SM = typename VT::SM;
   using RL = RecLayout<NC>;
   constexpr int NG = SM::NG, NW = SM::NW, U = SM::U, PS = SM::PS, C8 = 8 * NC;
   static_assert(NC == 2 || (NC == 3 && NT * BPT >= 512), "contacts: two feet (reference) or two feet + hand (extension)");
@@ -1744,7 +1813,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   auto &Q = S.u.s;
   // the packed Schur inverse: LDS, or this workgroup's slice of the global scratch
   double *const Ep = [&]() __attribute__((always_inline)) -> double * {
-    if constexpr (SM::EGLOBAL) return args.e_scratch + (size_t)blockIdx.x * (size_t)(NMAX * (NMAX + 1) / 2);
+    if constexpr (VT::EGLOBAL) return args.e_scratch + (size_t)blockIdx.x * (size_t)(NMAX * (NMAX + 1) / 2);
     else return S.u.s.Ep;
   }();
   auto Eat = [&](int i, int j) __attribute__((always_inline)) -> double & {
@@ -1758,45 +1827,31 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   // (uniform by construction -- but when it comes from the index list it arrives through a vector load: told to the compiler, so
   //  that the instance's base addresses are scalar arithmetic instead of register pairs that live for the whole kernel)
   const int inst = uni(ASM_ONLY ? args.dbg_index
-                                : ((SWEEP && args.sweep_phase == 0) ? (int)blockIdx.x * args.sweep_k  // the group's first record
+                                : ((VT::SWEEP && args.sweep_phase == 0) ? (int)blockIdx.x * args.sweep_k  // the group's first record
                                                                     : (args.index_list ? args.index_list[blockIdx.x] : (int)blockIdx.x)));
   const int h = args.horizon;
   if (inst >= args.batch) return;
   // command sweeps: M comes from (phase 1) or goes to (phase 0) this group's slot
-  const bool sweep_prepare = SWEEP && args.sweep_phase == 0, sweep_given = SWEEP && args.sweep_phase != 0;
-  double *const sweep_m = SWEEP ? args.sweep_m + (size_t)(inst / (SWEEP ? args.sweep_k : 1)) * (size_t)(GS * GS * NT) : nullptr;
+  const bool sweep_prepare = VT::SWEEP && args.sweep_phase == 0, sweep_given = VT::SWEEP && args.sweep_phase != 0;
+  double *const sweep_m = VT::SWEEP ? args.sweep_m + (size_t)(inst / (VT::SWEEP ? args.sweep_k : 1)) * (size_t)(GS * GS * NT) : nullptr;
   if (!ASM_ONLY && args.cls) {  // uniform: this instance belongs to another variant's launch
     const int c = args.cls[inst];
     if (c < args.cls_lo || c > args.cls_hi) return;
   }
   PROF_DECL;
-  // Hand-over of a full working set (KernelArgs::spill, SpillLayout): the fast 120-variable variants SAVE their state, the safe
-  // variants of the same shape (working set = variable count, in LDS) RESUME from it -- they assemble the instance again (index
-  // tables, constraint normals, g: cheap and bit-identical), then take M, E and the Goldfarb-Idnani state from the slot instead of
-  // running stages H, S and the start
-  constexpr bool SHAPE_HANDOVER = !ASM_ONLY && NMAX == 120 && NT == 256 && NC == 2 && BPT == 1 && !SM::EGLOBAL;
-  constexpr bool SPILLS = SHAPE_HANDOVER && QCAP < HMPC_QCAP_CONT;      // the fast variants (working set of 64 rows, three per CU)
-  // the continuation variant (96 rows, two per CU): takes over what the fast variants hand over, with block rounds of its own (up to
-  // its 96 rows at once, the Schur matrix as 6 x 6 tiles on the matrix cores), and flags what outgrows it in turn for the safe variant
-  constexpr bool RESUMABLE = SHAPE_HANDOVER && QCAP >= HMPC_QCAP_CONT && QCAP < NMAX;
-  constexpr bool CONT = RESUMABLE;
+  // Hand-over of a full working set (KernelArgs::spill, SpillLayout; VT::SAVES, VT::RESUMES): a resumed solve assembles the instance again (index tables, constraint
+  // normals, g: cheap and bit-identical), then takes M, E and the Goldfarb-Idnani state from the slot instead of running stages H, S and the start
   using SPL = SpillLayout<SM, NT, BPT>;
   bool resumed = false;
-  if constexpr (RESUMABLE) {
+  if constexpr (VT::RESUMES) {
     // (the slot must be this instance's own and its status word must still say "working set full": both are written by the fast
     //  variant in the same solve; anything else -- a stale entry of an earlier batch -- starts cold)
     if (args.resume) resumed = ub(args.spill_slot[inst] == inst && inst < args.spill_cap && (args.status[inst] & 0xffu) == (uint32_t)S_WORKSET);
     if (args.resume == 2 && !resumed) return;  // a continuation-only launch: everything else on the list is the safe variant's
   }
-  // the safe-pass variants (working set = variable count, scalar sweeps): they also answer a Hessian that is not positive definite
-  // the way the reference's qpOASES run does (KernelArgs::reg_step)
-  constexpr bool REGULARISES = !ASM_ONLY && (SM::EGLOBAL || (QCAP >= NMAX && NMAX >= 120));
-  // every variant launched over a list of flagged instances (the safe ones, the 140-row three-contact one among them, and the
-  // continuation ones) honours the list protocol; the fast variants never see it and do not compile it
-  constexpr bool LISTED = !ASM_ONLY && (REGULARISES || CONT || (NC == 3 && QCAP >= 140));
-  if constexpr (LISTED) {
+  if constexpr (VT::LISTED) {
     if (args.reg_step) {  // a regularisation step: only the instances the step before it left for this one
-      if constexpr (!REGULARISES) return;  // (a variant that does not regularise leaves the instance as it is)
+      if constexpr (!VT::REGULARISES) return;  // (a variant that does not regularise leaves the instance as it is)
       const uint32_t c0 = args.status[inst] & 0xffu;
       if (c0 != (uint32_t)(args.reg_step == 1 ? S_INDEFINITE : S_REG_STEP)) return;
     } else if (args.skip_ok) {  // second pass over a list of flagged instances: what the pass before it solved is left alone
@@ -1811,7 +1866,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     const int nwords = args.stride >> 2;
     for (int t = tid; t < nwords; t += NT) A.rec[t] = src[t];
   }
-  if constexpr (SWEEP) {
+  if constexpr (VT::SWEEP) {
     if (sweep_given) {
       // every word of the record but the trajectory must equal the group's first record's (whose M this solve uses)
       const int first = (inst / args.sweep_k) * args.sweep_k;
@@ -1865,19 +1920,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   // ---- register blocks of the sweeps (stage S): thread t owns the 6x6 blocks number t, t + NT, ... (< NG(NG+1)/2) of the
   // symmetric matrix in sweep order, block-row-major: (e0, e1), e0 <= e1.  Declared here because the blocks are filled
   // straight from the staging area of H, pass by pass where that area holds only part of the block-diagonals at a time.
-  // Matrix-core sweeps: the FAST 120-variable variants only.  The safe-pass variants (working set = variable count) keep the
-  // scalar sweeps: 4 x 4 block pivots apply an explicitly inverted pivot block, whose forward error carries cond(D) -- at 10x
-  // the nominal input ranges that showed as forces up to 9e-5 from qpOASES in the safe pass (7e-8 with scalar pivots), while
-  // nominal inputs are unaffected (5.8e-8 either way) and whatever the fast variants get wrong beyond 2e-6 is caught by
-  // their KKT check and handed to the safe pass anyway.
-  constexpr bool MFMA_SWEEP = !ASM_ONLY && QCAP != 0 && (SM::MFS2 && QCAP < NMAX);
-  // (the 60-variable variants are fast-pass only: the safe pass of two-contact batches runs on the 120-variable safe variants)
-  // ... and the fast three-contact variant (180 variables, two blocks per thread): 78 tiles, 20 per wave.  Its staging of H holds
-  // the block-diagonals in two passes, so the register blocks are filled as for the scalar sweeps and turned into tiles in stage S.
-  constexpr bool MFMA_SWEEP3 = SM::MFS3 && !ASM_ONLY && QCAP != 0 && QCAP < NMAX;
-  constexpr int MFS3_NTG = (NMAX + 15) / 16;
   constexpr int NTILE = NG * (NG + 1) / 2;
-  static_assert(NTILE <= BPT * NT && SM::MMAX <= NT && NMAX <= NT, "threads per block / constraint row / variable");
   // which 6 x 6 register blocks this thread holds (BlockOwner above); thin local names for the accessors
   BlockOwner<NG, NT, BPT> bo;
   auto pk_fence = [&]() __attribute__((always_inline)) { bo.fence(); };
@@ -1889,9 +1932,9 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   auto DIAG = [&](const int s) __attribute__((always_inline)) -> bool { return bo.DIAG(s); };
   auto own_blocks = [&]() __attribute__((always_inline)) { bo.assign(); };
   double a[BPT][GS][GS];
-  if (!((RESUMABLE && resumed) || sweep_given)) {  // (a resumed solve takes M from its hand-over slot, a command-sweep solve from its group's: no H, no sweeps)
+  if (!((VT::RESUMES && resumed) || sweep_given)) {  // (a resumed solve takes M from its hand-over slot, a command-sweep solve from its group's: no H, no sweeps)
     // ---------------- A5: H = 2(B'SB + alpha) on the matrix cores into the staging area, then the register blocks (stage_h above)
-    stage_h<NMAX, HMAX, NT, QCAP, ASM_ONLY, NC, BPT, MFMA_SWEEP>(S, args, inst, h, n, ng, bo, a);
+    stage_h<NMAX, HMAX, NT, QCAP, ASM_ONLY, NC, BPT, VT::MFMA_SWEEP>(S, args, inst, h, n, ng, bo, a);
   }  // !resumed
 
   PROF_MARK(P_HG);
@@ -1943,7 +1986,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   const bool is_v = tid < n, is_c = tid < m;
   // (the register blocks were loaded from the staging area of H at the end of stage A5)
   if (sweep_given) {
-    if constexpr (SWEEP) {
+    if constexpr (VT::SWEEP) {
       // ---- command sweep, phase 1: the group's M as phase 0 left it (the same threads own the same blocks)
       __syncthreads();  // g has been formed from the staging of the assembly, which the solver state aliases
       own_blocks();
@@ -1953,8 +1996,8 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         for (int jj = 0; jj < GS; ++jj) a[0][ii][jj] = sweep_m[(ii * GS + jj) * NT + tid];
     }
   } else
-  if (RESUMABLE && resumed) {
-    if constexpr (RESUMABLE) {
+  if (VT::RESUMES && resumed) {
+    if constexpr (VT::RESUMES) {
       // ---- hand-over: M from the slot's tail (the layout the fast variant's threads left: same block ownership)
       __syncthreads();  // g has been formed from the staging of the assembly, which the solver state aliases
       own_blocks();
@@ -1966,7 +2009,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         for (int jj = 0; jj < GS; ++jj) a[0][ii][jj] = mb[(ii * GS + jj) * NT + tid];
     }
   } else
-  if constexpr (MFMA_SWEEP) {
+  if constexpr (VT::MFMA_SWEEP) {
     // ---- matrix-core sweeps (mfma_sweeps above): tiles from the staging of H, 4 x 4 block pivots, M back in the 6 x 6 blocks
     auto hinfo = [&](const int i) __attribute__((always_inline)) -> int {  // i < n, sweep order
       if constexpr (SM::FULLBLK) return (int)S.sinfo[i];  // horizon step | component << 8
@@ -1998,10 +2041,10 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       case 2: mfma_sweeps<NTG1, 4, 2, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
       default: mfma_sweeps<NTG1, 4, 3, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
     }
-  } else if constexpr (MFMA_SWEEP3) {
+  } else if constexpr (VT::MFMA_SWEEP3) {
     // ---- the same on the tiles filled in stage A5
-    MfsPanel<MFS3_NTG> &PN = *reinterpret_cast<MfsPanel<MFS3_NTG> *>(&Q.ST[0][0]);
-    static_assert(sizeof(MfsPanel<MFS3_NTG>) <= sizeof(Q.ST), "the pivot panels live in the (not yet used) mat-vec staging");
+    MfsPanel<VT::MFS3_NTG> &PN = *reinterpret_cast<MfsPanel<VT::MFS3_NTG> *>(&Q.ST[0][0]);
+    static_assert(sizeof(MfsPanel<VT::MFS3_NTG>) <= sizeof(Q.ST), "the pivot panels live in the (not yet used) mat-vec staging");
     double *stage = reinterpret_cast<double *>(&S.u);
     static_assert(sizeof(S.u) / sizeof(double) >= 48 * (NMAX + 1), "re-layout staging of the matrix-core sweeps: 48 rows of M");
     __syncthreads();  // every block is loaded before the staging area of H is written over
@@ -2012,16 +2055,16 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     for (int s = 0; s < BPT; ++s) e0a[s] = E0(s), e1a[s] = E1(s), owa[s] = OWN(s), lva[s] = OWN(s) && E1(s) < ng;
     float *hb = reinterpret_cast<float *>(&S.u);
     static_assert(sizeof(S.u) >= (size_t)NTILE * GS * GS * sizeof(float), "the parked blocks fit the staging area");
-    mfs_park_blocks<NMAX, BPT, NT, MFS3_NTG>(hb, n, S.kexp, owa, e0a, e1a, lva, a);
+    mfs_park_blocks<NMAX, BPT, NT, VT::MFS3_NTG>(hb, n, S.kexp, owa, e0a, e1a, lva, a);
     __syncthreads();
     switch (wv) {  // uniform: per-wave specialised code
 #define HMPC_MFS3_WAVE(W)                                                                  \
-  MfsAcc<MFS3_NTG, NW> acc;                                                                \
-  mfs_load_parked<MFS3_NTG, NW, W, NMAX>(acc, n, hb, S.kexp);                              \
+  MfsAcc<VT::MFS3_NTG, NW> acc;                                                                \
+  mfs_load_parked<VT::MFS3_NTG, NW, W, NMAX>(acc, n, hb, S.kexp);                              \
   __syncthreads(); /* every tile is loaded before the panel (which aliases the parked blocks) is written */ \
-  mfs_steps<MFS3_NTG, NW, W>(PN, acc, n);                                                  \
+  mfs_steps<VT::MFS3_NTG, NW, W>(PN, acc, n);                                                  \
   double aw[BPT][GS][GS];                                                                  \
-  mfs_relayout<MFS3_NTG, NW, W, NMAX, BPT, NT>(stage, acc, n, S.kexp, e0a, e1a, lva, aw);  \
+  mfs_relayout<VT::MFS3_NTG, NW, W, NMAX, BPT, NT>(stage, acc, n, S.kexp, e0a, e1a, lva, aw);  \
   mfs_move_blocks<BPT>(a, aw);
       case 0: { HMPC_MFS3_WAVE(0) } break;
       case 1: { HMPC_MFS3_WAVE(1) } break;
@@ -2036,7 +2079,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     pk_fence();
   } else {
   __syncthreads();  // every block is loaded before the solver state (which aliases the staging area) is written
-  if constexpr (REGULARISES) {
+  if constexpr (VT::REGULARISES) {
     if (args.reg_step != 0) {  // uniform
       // H += rho I as qpOASES does after a failed Cholesky factorisation (KernelArgs::reg_step; QProblemB.cpp:1418-1431, 1999-2031):
       // |H|_F over the reduced matrix -- this thread's blocks, an off-diagonal block standing for its mirror image too --,
@@ -2089,7 +2132,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     }
   }
   if (tid < NMAX) Q.piv[0][tid] = 0.0, Q.piv[1][tid] = 0.0;
-  if constexpr (REGULARISES) {
+  if constexpr (VT::REGULARISES) {
     if (tid == 0) Q.gamma = 1.0;  // the first sweep pivot that is not positive (free until the solver starts)
   }
   __syncthreads();
@@ -2122,7 +2165,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       const double *pv = Q.piv[k & 1];
       double *pn = Q.piv[(k + 1) & 1];
       const double d = Q.pd[k & 1];
-      if constexpr (REGULARISES) {
+      if constexpr (VT::REGULARISES) {
         if (!(d > 0.0) && tid == 0 && Q.gamma > 0.0) Q.gamma = d;  // H is not positive definite (rare branch; thread 0 alone reads and writes the slot)
       }
       // v_rcp_f64 is good to 2^-24 (scripts/micro/rcp64_accuracy.hip); one Newton step brings 2e-15, a second one would
@@ -2193,7 +2236,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     }
   }
   pk_fence();
-  if constexpr (REGULARISES) {
+  if constexpr (VT::REGULARISES) {
     const double negp = uni_d(Q.gamma);  // (the last sweep ended with a barrier)
     if (!(negp > 0.0)) {
       // Not positive definite: nothing a dual active-set method can start from -- x_u = -H^-1 g is not a minimiser; the fast variants
@@ -2232,7 +2275,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   }
   }  // scalar sweeps
   PROF_MARK(P_SWEEP);
-  if constexpr (SWEEP) {
+  if constexpr (VT::SWEEP) {
     if (sweep_prepare) {  // uniform.  Phase 0 of a command sweep: this group's M to its slot, nothing else
 #pragma unroll
       for (int ii = 0; ii < GS; ++ii)
@@ -2347,12 +2390,8 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   // registers; thread i < n = variable i (leg-step i/6, position i%6).
   const double INF = __builtin_huge_val();
   const double FEAS_TOL = 1e-9;
-  constexpr bool LAZY = (BPT == 2);
-  // (the fast 256-thread two-contact variants sit exactly on their 168-register budget: their integer roles are recomputed at
-  //  every use as well -- one instruction each -- instead of being the allocator's first victims)
-  constexpr bool LAZY_IDX = LAZY || (NT == 256 && BPT == 1 && NC == 2 && QCAP != 0 && QCAP < NMAX);
-  const auto c_e = lazy_int<LAZY_IDX>([](int t) { return t >> 3; });
-  const auto c_rr = lazy_int<LAZY_IDX>([](int t) { return t & 7; });
+  const auto c_e = lazy_int<VT::LAZY_IDX>([](int t) { return t >> 3; });
+  const auto c_rr = lazy_int<VT::LAZY_IDX>([](int t) { return t & 7; });
   // the lower bound of a row is 0 -- except in the last-resort pass (args.relax != 0), where it is recomputed on use
   // rather than kept in a register pair for the whole solve
   // (read through LDS: a value the compiler cannot prove loop-invariant across the barriers, or it hoists the whole
@@ -2379,7 +2418,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   double c_ub_r = INF;
   bool c_hasl_r = false, c_hasu_r = false;
   const double *c_cn_r = S.Cn[0][0];  // this row's 6 coefficients (LDS; re-read where used: cheaper than 12 live VGPRs)
-  if constexpr (!LAZY) {
+  if constexpr (!VT::LAZY) {
     if (is_c) {
       const int leg = S.ls_leg[c_e];
       c_cn_r = S.Cn[leg][c_rr];
@@ -2390,16 +2429,16 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   }
   // (callers are rows of the QP, tid < m -- except the lane that publishes a selection record when no row is a candidate)
   auto row_cn = [&]() __attribute__((always_inline)) -> const double * {
-    if constexpr (!LAZY) return c_cn_r;
+    if constexpr (!VT::LAZY) return c_cn_r;
     else return (tid < m) ? S.Cn[S.ls_leg[c_e]][c_rr] : S.Cn[0][0];
   };
-  auto row_ub = [&]() __attribute__((always_inline)) -> double { if constexpr (!LAZY) return c_ub_r; else return row_ub_calc(); };
-  auto row_hasl = [&]() __attribute__((always_inline)) -> bool { if constexpr (!LAZY) return c_hasl_r; else { const int rr = c_rr; return rr <= 4 || rr == 7; } };
-  auto row_hasu = [&]() __attribute__((always_inline)) -> bool { if constexpr (!LAZY) return c_hasu_r; else return c_rr >= 4; };
-  const auto v_e = lazy_int<LAZY_IDX>([](int t) { return t / GS; });
-  const auto v_k = lazy_int<LAZY_IDX>([](int t) { return t % GS; });
-  const int v_leg_r = (!LAZY_IDX && is_v) ? S.ls_leg[v_e] : 0;
-  auto var_leg = [&]() __attribute__((always_inline)) -> int { if constexpr (!LAZY_IDX) return v_leg_r; else return (tid < n) ? (int)S.ls_leg[v_e] : 0; };
+  auto row_ub = [&]() __attribute__((always_inline)) -> double { if constexpr (!VT::LAZY) return c_ub_r; else return row_ub_calc(); };
+  auto row_hasl = [&]() __attribute__((always_inline)) -> bool { if constexpr (!VT::LAZY) return c_hasl_r; else { const int rr = c_rr; return rr <= 4 || rr == 7; } };
+  auto row_hasu = [&]() __attribute__((always_inline)) -> bool { if constexpr (!VT::LAZY) return c_hasu_r; else return c_rr >= 4; };
+  const auto v_e = lazy_int<VT::LAZY_IDX>([](int t) { return t / GS; });
+  const auto v_k = lazy_int<VT::LAZY_IDX>([](int t) { return t % GS; });
+  const int v_leg_r = (!VT::LAZY_IDX && is_v) ? S.ls_leg[v_e] : 0;
+  auto var_leg = [&]() __attribute__((always_inline)) -> int { if constexpr (!VT::LAZY_IDX) return v_leg_r; else return (tid < n) ? (int)S.ls_leg[v_e] : 0; };
   int q = 0, iters = 0, code = S_OK;
 #ifdef HMPC_DEBUG_STATS  // developer build (scripts/dev/cont_probe.py): what happened inside a solve, packed into obj64
   int dbg_bad = 0, dbg_rounds = 0, dbg_norounds_cap = 0, dbg_norounds_few = 0, dbg_dep = 0;
@@ -2408,8 +2447,8 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
 #else
 #define HMPC_DBG(x)
 #endif
-  if (RESUMABLE && resumed) {
-    if constexpr (RESUMABLE) {
+  if (VT::RESUMES && resumed) {
+    if constexpr (VT::RESUMES) {
       // ---- hand-over: the Goldfarb-Idnani state the fast variant stopped in (x minimises over the working set, u >= 0, E current)
       const uint32_t st0 = args.status[inst];
       q = uni((int)((st0 >> 20) & 0xfffu)), iters = uni((int)((st0 >> 8) & 0xfffu));
@@ -2439,23 +2478,12 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   }
   PROF_MARK(P_XU);
 
-  constexpr bool SAFE = SM::EGLOBAL || QCAP >= NMAX;  // the working set cannot overflow
-  // ... and of those, the variants hmpc_resolve_failed / the device-side repair launch (always cold): the only ones that ever run
-  // for hundreds of iterations (the 60-variable fast variants also have QCAP = NMAX, but are fast variants)
-  constexpr bool LONGRUN = SM::EGLOBAL || (QCAP >= NMAX && NMAX >= 120);
-  // Anti-cycling (the variants that run the hard instances: continuation and safe).  At a degenerate vertex -- several rows
-  // active with zero multipliers -- round-off can make the dual iteration drop and re-add the same rows with zero-length steps
-  // until the iteration bound (seen: 600 iterations on the continuation variant, 1 664 on the safe one, each the whole tail of
-  // its launch).  In exact arithmetic a row is added at most 3 times per solve in all but the genuinely cycling instances
-  // (scripts/dev/emulate_rounds.py, 6x and 10x the input ranges), so a row the single-row iteration has already added
-  // HMPC_READD_LIMIT times is set aside like a redundant row: the final KKT check looks at every row again and decides.
-  constexpr bool ANTICYCLE = (LONGRUN || CONT) && HMPC_READD_LIMIT > 0;
-  const int itmax_v = (SAFE || QCAP >= 140) ? 10 * m + 64 : 4 * m + 16;  // the safe variants may take as long as a cold qpOASES run (nWSR up to ~330 seen)
+  const int itmax_v = VT::ITER_LONG ? 10 * m + 64 : 4 * m + 16;
   int itmax = (args.iter_cap > 0 && args.iter_cap < itmax_v) ? args.iter_cap : itmax_v;
   bool budgeted = false, budget_hit = false;  // (continuation variant only)
   bool perturbed = false;                     // (anti-cycling variants: the bounds were moved outward in this pass)
   const int itmax_full = itmax;
-  if constexpr (CONT) {
+  if constexpr (VT::RESUMES) {
     // a resumed solve gets a budget of its own: in exact arithmetic the hardest instances need ~50 more changes from the hand-over
     // (scripts/dev/emulate_rounds.py); one that is still going after HMPC_CONT_ITER_BUDGET is cycling at a degenerate vertex -- the
     // safe pass's business (rebuilt E, relaxed bounds), not worth 600 iterations at the tail of this launch.  Such an instance usually
@@ -2618,27 +2646,13 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       k0 = uni(k0);
     };
     // Rounds.  Round 0 is the block start proper; while enough further rows are violated at the point it reaches
-    // (>= BLOCK_MIN_NEW of them: a round costs about as much as that many single-row iterations) another round takes the
+    // (>= VT::BLOCK_MIN_NEW of them: a round costs about as much as that many single-row iterations) another round takes the
     // current working set plus every row violated at the current x -- same independence rule -- and solves for all of them
     // at once.  Every round ends in a valid Goldfarb-Idnani state (x minimises over the working set, multipliers >= 0), so
     // the dual active-set iteration below finishes from wherever the rounds stop.
-    // walking: ~1.6 iterations per solve, nothing to gain; 120 variables: two rounds (a third one is worth <1 % there and its
-    // third copy of the phase tips the register allocation of the 168-VGPR variant over: 86 spilled registers, 1.43 -> 1.78 ms);
-    // three contacts: three (1.13 -> 1.18 M solves/s over two)
-    constexpr int BLOCK_ROUNDS = (NC == 3) ? BLOCK_ROUNDS_3C : ((NT >= 256) ? BLOCK_ROUNDS_2C : 1);
-    constexpr int CONT_ROUNDS = HMPC_CONT_ROUNDS;  // block rounds of a resumed solve (the continuation variant: 256 VGPRs, a loop fits)
-    constexpr bool BLOCK_FRICTION = NT >= 256;
-    constexpr int BLOCK_MIN_NEW = (NC == 3) ? BLOCK_MIN_NEW_3C : BLOCK_MIN_NEW_2C;
-    constexpr int EPT = (NC == 3 && NT < 512) ? EPT_3C : 5;  // packed-triangle entries per thread during the Schur inversion
-    constexpr int KBMAX_3C = (EPT_3C >= 8) ? 63 : ((EPT_3C == 7) ? 59 : 54);
-    // Schur matrix of the fast variants on the matrix cores (schur_invert): 3 x 3 tiles = 48 rows for the 120-variable variants,
-    // 4 x 4 = 64 rows with three contacts, 5 x 5 = 80 rows for the wide variant (eight waves)
-    constexpr int NTGS = (NT >= 512) ? 5 : (NC == 3 ? 4 : (CONT ? 6 : 3));  // (continuation variant: 6 x 6 tiles = its 96 rows)
-    // (not the 128-thread variants: measured slower there, profiles/r05/schur_128_ab.txt; not the safe variants: register budget)
-    constexpr bool SCHUR_MFMA = !LONGRUN && NT >= 256 && SM::QMAX >= 16 * NTGS;
-    constexpr int KBMAX = SCHUR_MFMA ? 16 * NTGS
-                                     : ((NT >= 512) ? 71 : ((NT >= 256) ? (NC == 3 ? (KBMAX_3C < SM::QMAX ? KBMAX_3C : SM::QMAX) : 45) : 34));  // KBMAX(KBMAX+1)/2 <= EPT*NT
-    static_assert((SCHUR_MFMA || KBMAX * (KBMAX + 1) / 2 <= EPT * NT) && KBMAX <= SM::QMAX, "block start capacity");
+    // (rows a block round takes.  A local on purpose: with no constant declared in this scope the 120-variable SAFE variants get another register
+    //  numbering for the same instructions, and scripts/isa_hash.py could not say "unchanged")
+    constexpr int KBMAX = VT::KBMAX;
     // (one round as a lambda instantiated once per round rather than a loop: with the loop the register allocator keeps
     //  ~50 more VGPRs alive across the whole phase -- measured 185 -> 244 on the unconstrained variants)
     // refresh (safe variants only): the round is there to REBUILD E for the current working set (plus whatever is violated) --
@@ -2657,7 +2671,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         fresh = viol && !partner;
         take = (ac != 0) || fresh;
       }
-      if constexpr (CONT) {
+      if constexpr (VT::RESUMES) {
         // One more independence rule, needed once the Fz cap (row 7) can be in the working set (it enters through single-row
         // iterations only, i.e. never before the fast variants' rounds, but before the continuation variant's): the moment parts
         // of the toe and heel rows 5 and 6 are parallel (+-t1), so their difference is a pure force row, and together with three
@@ -2674,11 +2688,11 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         }
       }
       count_candidates();
-      HMPC_DBG(if (k0 > (LONGRUN ? SM::QMAX : KBMAX)) ++dbg_norounds_cap; else if (!refresh && k0 - q < BLOCK_MIN_NEW) ++dbg_norounds_few;)
-      if constexpr (SPILLS) {
+      HMPC_DBG(if (k0 > (VT::LONGRUN ? SM::QMAX : KBMAX)) ++dbg_norounds_cap; else if (!refresh && k0 - q < VT::BLOCK_MIN_NEW) ++dbg_norounds_few;)
+      if constexpr (VT::SAVES) {
         if (k0 > KBMAX + HMPC_EARLY_HANDOVER_MARGIN) early_handover = true;
       }
-      if (ub((!refresh && k0 - q < BLOCK_MIN_NEW) || k0 > (LONGRUN ? SM::QMAX : KBMAX))) return false;  // not worth a round / does not fit: the iteration below goes on
+      if (ub((!refresh && k0 - q < VT::BLOCK_MIN_NEW) || k0 > (VT::LONGRUN ? SM::QMAX : KBMAX))) return false;  // not worth a round / does not fit: the iteration below goes on
       // (no barrier here: what follows writes act / slot / Wrow entries that nobody reads before the barrier behind the slot deal,
       //  and wcount is not written again before the release loop, several barriers on)
       ++iters;
@@ -2698,7 +2712,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     }
     if (!tick) {  // uniform.  Rows 4-6 violated at the unconstrained minimiser
       take = false;
-      if constexpr (BLOCK_FRICTION) {
+      if constexpr (VT::BLOCK_FRICTION) {
       // ... and a friction row (0-3) violated there whose partner on the same axis (0<->1, 2<->3) is not: at most one row
       // per axis, so that the rows taken from one leg-step stay linearly independent
       if (is_c && c_rr <= 6) {
@@ -2712,12 +2726,12 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       }
       count_candidates();
     }
-    const int rlo = (tick || BLOCK_FRICTION) ? 0 : 4, rhi = tick ? 7 : 6;
+    const int rlo = (tick || VT::BLOCK_FRICTION) ? 0 : 4, rhi = tick ? 7 : 6;
     bool bad_start = false;
-    if constexpr (SPILLS) {
+    if constexpr (VT::SAVES) {
       if (k0 > KBMAX + HMPC_EARLY_HANDOVER_MARGIN) early_handover = true;  // (uniform) far more candidates than this variant can take at once
     }
-    if (k0 > (LONGRUN ? SM::QMAX : KBMAX)) k0 = LONGRUN ? SM::QMAX : KBMAX;
+    if (k0 > (VT::LONGRUN ? SM::QMAX : KBMAX)) k0 = VT::LONGRUN ? SM::QMAX : KBMAX;
     if (is_c) {  // slots are dealt afresh every round (E is rebuilt from scratch)
       const bool in = take && base + below < k0;
       const int sl = in ? base + below : 0;
@@ -2768,35 +2782,35 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           }
         }
       }
-      if constexpr (SCHUR_MFMA) {  // (cleared before the barrier that ends the formation of S0: the mat-vec staging is free here)
-        if (tid == 0) reinterpret_cast<SchurPanel<NTGS> *>(&Q.ST[0][0])->pn.bad = 0;
+      if constexpr (VT::SCHUR_MFMA) {  // (cleared before the barrier that ends the formation of S0: the mat-vec staging is free here)
+        if (tid == 0) reinterpret_cast<SchurPanel<VT::NTGS> *>(&Q.ST[0][0])->pn.bad = 0;
       }
       __syncthreads();
       PROF_MARK(P_B_S0);
       // (c) inversion of the k0 x k0 Schur matrix by symmetric sweeps with the packed triangle spread over the threads'
-      //     registers (<= EPT entries each); the safe variants also take sets beyond that capacity, swept in place
+      //     registers (<= VT::EPT entries each); the safe variants also take sets beyond that capacity, swept in place
       //     (LDS, or global for the EGLOBAL variant), one pivot per two barriers -- slow, and only ever run for the handful of
       //     instances per thousand that need hundreds of working-set changes at many times the nominal input ranges
-      if constexpr (SCHUR_MFMA) {
+      if constexpr (VT::SCHUR_MFMA) {
         // 4 x 4 block pivots on v_mfma_f64_16x16x4_f64: S0 as 16 x 16 tiles in the accumulators (six tiles on four waves), the
         // pivot panels in the mat-vec staging (free here), E written back over S0 in the packed triangle
-        static_assert(sizeof(SchurPanel<NTGS>) <= sizeof(Q.ST), "the Schur panels live in the mat-vec staging");
-        SchurPanel<NTGS> &SP = *reinterpret_cast<SchurPanel<NTGS> *>(&Q.ST[0][0]);
-        schur_scale_exponents<NTGS>(k0, Ep, SP.kexp);  // (read again at the store, many barriers later; the tile loader takes its own from the diagonal)
+        static_assert(sizeof(SchurPanel<VT::NTGS>) <= sizeof(Q.ST), "the Schur panels live in the mat-vec staging");
+        SchurPanel<VT::NTGS> &SP = *reinterpret_cast<SchurPanel<VT::NTGS> *>(&Q.ST[0][0]);
+        schur_scale_exponents<VT::NTGS>(k0, Ep, SP.kexp);  // (read again at the store, many barriers later; the tile loader takes its own from the diagonal)
         switch (wv) {  // uniform: per-wave specialised code
-          case 0: schur_invert<NTGS, NW, 0>(SP, k0, Ep); break;
-          case 1: schur_invert<NTGS, NW, 1>(SP, k0, Ep); break;
-          case 2: schur_invert<NTGS, NW, (NW > 2 ? 2 : 0)>(SP, k0, Ep); break;  // (cases 2-3: not in the two-wave variants)
-          case 3: schur_invert<NTGS, NW, (NW > 2 ? 3 : 0)>(SP, k0, Ep); break;
-          case 4: schur_invert<NTGS, NW, (NW > 4 ? 4 : 0)>(SP, k0, Ep); break;  // (cases 4-7: eight-wave variants only)
-          case 5: schur_invert<NTGS, NW, (NW > 4 ? 5 : 0)>(SP, k0, Ep); break;
-          case 6: schur_invert<NTGS, NW, (NW > 4 ? 6 : 0)>(SP, k0, Ep); break;
-          default: schur_invert<NTGS, NW, (NW > 4 ? 7 : 0)>(SP, k0, Ep); break;
+          case 0: schur_invert<VT::NTGS, NW, 0>(SP, k0, Ep); break;
+          case 1: schur_invert<VT::NTGS, NW, 1>(SP, k0, Ep); break;
+          case 2: schur_invert<VT::NTGS, NW, (NW > 2 ? 2 : 0)>(SP, k0, Ep); break;  // (cases 2-3: not in the two-wave variants)
+          case 3: schur_invert<VT::NTGS, NW, (NW > 2 ? 3 : 0)>(SP, k0, Ep); break;
+          case 4: schur_invert<VT::NTGS, NW, (NW > 4 ? 4 : 0)>(SP, k0, Ep); break;  // (cases 4-7: eight-wave variants only)
+          case 5: schur_invert<VT::NTGS, NW, (NW > 4 ? 5 : 0)>(SP, k0, Ep); break;
+          case 6: schur_invert<VT::NTGS, NW, (NW > 4 ? 6 : 0)>(SP, k0, Ep); break;
+          default: schur_invert<VT::NTGS, NW, (NW > 4 ? 7 : 0)>(SP, k0, Ep); break;
         }
         __syncthreads();
         bad_start = SP.pn.bad != 0;
       } else
-      if (LONGRUN && (SM::EGLOBAL || ub(k0 > KBMAX))) {  // (EGLOBAL: always in place -- one inversion path less to hold registers for)
+      if (VT::LONGRUN && (VT::EGLOBAL || ub(k0 > KBMAX))) {  // (EGLOBAL: always in place -- one inversion path less to hold registers for)
         bad_start = false;
         const int ti = tid >> 4, tj = tid & 15;
         for (int sp = 0; sp < k0; ++sp) {
@@ -2826,10 +2840,10 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         const int npair = k0 * (k0 + 1) / 2;
         const int nept = (npair + NT - 1) / NT;
         bad_start = false;
-        double er[EPT];
-        int ei[EPT], ej[EPT];
+        double er[VT::EPT];
+        int ei[VT::EPT], ej[VT::EPT];
 #pragma unroll
-        for (int u = 0; u < EPT; ++u) {
+        for (int u = 0; u < VT::EPT; ++u) {
           const int t = tid + NT * u;
           int i = 0, j = 0;
           double v = 0.0;
@@ -2853,7 +2867,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           else if (i == c) buf[j] = v;
         };
 #pragma unroll
-        for (int u = 0; u < EPT; ++u) {
+        for (int u = 0; u < VT::EPT; ++u) {
           if (ei[u] >= 0) {
             publish(Q.col, 0, ei[u], ej[u], er[u]);
             publish(Q.z, 1, ei[u], ej[u], er[u]);
@@ -2873,7 +2887,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           idet = dfma(dfma(-det, idet, 1.0), idet, idet);
           const double g00 = a11 * idet, g01 = -a01 * idet, g11 = a00 * idet;
 #pragma unroll
-          for (int u = 0; u < EPT; ++u) {
+          for (int u = 0; u < VT::EPT; ++u) {
             if (u < nept) {  // uniform: only the register slots this k0 actually uses
               const int i = ei[u], j = ej[u];
               const int ic = i < 0 ? 0 : i, jc = j < 0 ? 0 : j;
@@ -2898,7 +2912,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           idv = dfma(dfma(-dv, idv, 1.0), idv, idv);
           idv = dfma(dfma(-dv, idv, 1.0), idv, idv);
 #pragma unroll
-          for (int u = 0; u < EPT; ++u) {
+          for (int u = 0; u < VT::EPT; ++u) {
             if (u < nept) {
               const int i = ei[u], j = ej[u];
               const double ci = cs[i < 0 ? 0 : i] * idv, cj = cs[j < 0 ? 0 : j];
@@ -2909,7 +2923,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           __syncthreads();
         }
 #pragma unroll
-        for (int u = 0; u < EPT; ++u)
+        for (int u = 0; u < VT::EPT; ++u)
           if (ei[u] >= 0) Ep[(unsigned)(tid + NT * u)] = -er[u];  // the sweeps leave -S0^-1
       }
       q = k0;
@@ -2948,7 +2962,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         bool cand = false;
         if (tid < q && um < -1e-12) {
           const int c = Q.Wrow[tid];
-          cand = ((c & 7) == 4) && (ANTICYCLE ? (Q.flpc[c] & 1) == 0 : Q.flpc[c] == 0);
+          cand = ((c & 7) == 4) && (VT::ANTICYCLE ? (Q.flpc[c] & 1) == 0 : Q.flpc[c] == 0);
         }
         const double wmin = wave_min(um);
         const unsigned long long b2 = __ballot(um == wmin);
@@ -2975,7 +2989,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
           if (cand) {
             const int c = Q.Wrow[tid];
             Q.act[c] = (signed char)(-Q.act[c]);
-            Q.flpc[c] = ANTICYCLE ? (unsigned char)(Q.flpc[c] | 1) : (unsigned char)1;
+            Q.flpc[c] = VT::ANTICYCLE ? (unsigned char)(Q.flpc[c] | 1) : (unsigned char)1;
           }
           __syncthreads();
           {
@@ -3017,42 +3031,42 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     }
     return !ub(k0 == 0 || q == 0);  // (nothing to build on otherwise)
     };  // block_round
-  if constexpr (CONT) {
+  if constexpr (VT::RESUMES) {
     // a resumed solve: the state handed over is a Goldfarb-Idnani state, so further ROUNDS apply as they stand -- the working set
     // plus every row violated at the point reached, all at once, up to this variant's capacity
     if (resumed) {
       // (instantiated one by one: written as a loop the phase keeps ~100 more registers alive -- 104 spilled at the 256 this variant has)
       bool more = true;
-      if constexpr (CONT_ROUNDS > 0) more = block_round(1, false);
-      if constexpr (CONT_ROUNDS > 1) {
+      if constexpr (VT::CONT_ROUNDS > 0) more = block_round(1, false);
+      if constexpr (VT::CONT_ROUNDS > 1) {
         if (more) more = block_round(2, false);
       }
-      if constexpr (CONT_ROUNDS > 2) {
+      if constexpr (VT::CONT_ROUNDS > 2) {
         if (more) more = block_round(3, false);
       }
-      if constexpr (CONT_ROUNDS > 3) {
+      if constexpr (VT::CONT_ROUNDS > 3) {
         if (more) more = block_round(4, false);
       }
-      static_assert(CONT_ROUNDS >= 0 && CONT_ROUNDS <= 4, "rounds are instantiated one by one");
+      static_assert(VT::CONT_ROUNDS >= 0 && VT::CONT_ROUNDS <= 4, "rounds are instantiated one by one");
     }
   }
   // (the safe variants as well since round 6: their first pass over a flagged instance starts from the block start like any other
   //  solve -- 40-60 iterations instead of the 150-250 of a cold run at 6x the input ranges, on ONE workgroup at the tail of the
   //  stream --; the last-resort passes with perturbed bounds stay cold)
-  if (args.warm && !(RESUMABLE && resumed)) {
+  if (args.warm && !(VT::RESUMES && resumed)) {
     bool more = block_round(0, false);
-    if constexpr (BLOCK_ROUNDS > 1) {
+    if constexpr (VT::BLOCK_ROUNDS > 1) {
       if (more) more = block_round(1, false);
     }
-    if constexpr (BLOCK_ROUNDS > 2) {
+    if constexpr (VT::BLOCK_ROUNDS > 2) {
       if (more) more = block_round(2, false);
     }
-    static_assert(BLOCK_ROUNDS <= 3, "rounds are instantiated one by one");
+    static_assert(VT::BLOCK_ROUNDS <= 3, "rounds are instantiated one by one");
   }
   PROF_MARK(P_BLOCK);
 
   // =============================== Q: dual active set (Goldfarb-Idnani, range-space form) ===============================
-  // Safe-pass variants (LONGRUN): E = (N_W M N_W')^-1 is kept current by rank-one updates (bordering / Schur downdates), whose round-off adds up
+  // Safe-pass variants (VT::LONGRUN): E = (N_W M N_W')^-1 is kept current by rank-one updates (bordering / Schur downdates), whose round-off adds up
   // over the hundreds of working-set changes a run at many times the nominal input ranges takes (measured: a 470-iteration
   // run ended 3.5 N off its constraints while every multiplier looked fine).  So every REFRESH_EVERY changes -- and once more
   // before the final refinement when enough have happened since -- E is REBUILT from the register blocks of M for the
@@ -3061,14 +3075,13 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
   constexpr int REFRESH_EVERY = 48, REFRESH_FINAL = 12;
   // (the continuation variant runs the hard instances -- dozens to hundreds of further working-set changes on top of the fast
   //  variant's -- and rebuilds E periodically as well: on the matrix cores, a refresh costs about four single-row iterations)
-  constexpr bool REFRESHES = LONGRUN;  // (the continuation variant: measured no difference at 6x, and a seventh instantiation of the round costs it 113 spilled registers)
   int since_refresh = 0;
-  for (int pass = 0; pass < (ANTICYCLE ? 8 : 3) && code == S_OK; ++pass) {
+  for (int pass = 0; pass < (VT::ANTICYCLE ? 8 : 3) && code == S_OK; ++pass) {
     const int iters_at_entry = uni(iters);  // (uniform: a scalar register)
-    if constexpr (ANTICYCLE) perturbed = false;
+    if constexpr (VT::ANTICYCLE) perturbed = false;
     // ---- main loop ----
     while (true) {
-      if constexpr (REFRESHES) {
+      if constexpr (VT::REFRESHES) {
         if (ub(since_refresh >= REFRESH_EVERY && q > 0)) {
           __syncthreads();
           (void)block_round(3, true);
@@ -3078,7 +3091,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       // (1) most violated constraint; the winning lane of each wave also publishes its constants
       double val = INF, raw = INF;
       int side = 1;
-      if constexpr (ANTICYCLE) {
+      if constexpr (VT::ANTICYCLE) {
         if (is_c && !c_ignored && Q.act[tid] == 0 && (Q.flpc[tid] >> 1) < HMPC_READD_LIMIT) val = my_slack(Q.x, side, raw);
       } else {
         if (is_c && !c_ignored && Q.act[tid] == 0) val = my_slack(Q.x, side, raw);
@@ -3110,13 +3123,13 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       }
       PROF_MARK(P_SEL);
       if (ub(!(pval < -FEAS_TOL))) break;
-      if constexpr (ANTICYCLE) {
+      if constexpr (VT::ANTICYCLE) {
         if (ub(pval < -1e8)) {  // the iterate has left the problem's scale (an ill-conditioned working set blew E up): flagged at once
           code = S_KKT;
           break;
         }
       }
-      if constexpr (ANTICYCLE) {
+      if constexpr (VT::ANTICYCLE) {
         // Degenerate vertices, handled where they occur (round 6; until then only the host's last-resort passes did this, after a
         // cold re-solve had burnt its whole iteration bound).  When the re-addition counter of a row reaches its limit, or a
         // resumed solve's budget runs out, the instance is cycling: every bound is moved outward by relax (1 + frac(0.618 row)) --
@@ -3127,7 +3140,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         // (safe variants only.  The continuation variant's long-runners were measured to run through every level's budget and end
         //  flagged all the same -- 512 instead of 128 iterations at the tail of its launch --: there the budget and the KKT check decide,
         //  and the safe pass, which starts cold, perturbs)
-        const bool cycling = LONGRUN && ub(S.pad0 != 0);
+        const bool cycling = VT::LONGRUN && ub(S.pad0 != 0);
         if (cycling) {
           const double rl = uni_d(S.relax);
           if (rl < 0.99e-5) {  // (uniform) another level left
@@ -3135,10 +3148,10 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
             if (tid == 0) S.relax = (rl == 0.0) ? 1e-7 : 10.0 * rl, S.pad0 = 0;
             for (int t = tid; t < SM::MMAX; t += NT) Q.flpc[t] = (unsigned char)(Q.flpc[t] & 1);
             __syncthreads();
-            if constexpr (!LAZY) {
+            if constexpr (!VT::LAZY) {
               if (is_c) c_ub_r = row_ub_calc();
             }
-            if constexpr (CONT) {  // (a resumed solve's budget starts afresh)
+            if constexpr (VT::RESUMES) {  // (a resumed solve's budget starts afresh)
               if (budgeted) itmax = (iters + HMPC_CONT_ITER_BUDGET < itmax_full) ? iters + HMPC_CONT_ITER_BUDGET : itmax_full;
             }
             perturbed = true;
@@ -3148,7 +3161,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         }
       }
       if (iters >= itmax) {
-        if constexpr (CONT) {
+        if constexpr (VT::RESUMES) {
           if (budgeted) {  // (uniform)
             budget_hit = true;
             HMPC_DBG(dbg_viol = -pval;)
@@ -3158,7 +3171,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         code = S_MAXITER;
         break;
       }
-      if constexpr (SPILLS) {
+      if constexpr (VT::SAVES) {
         // a violated row and a full working set: stop HERE, between two iterations, where (x, u, W, E) is a complete
         // Goldfarb-Idnani state that the continuation variant can take over (inside an iteration -- after partial steps for
         // the row being added -- it is not).  Conservative by at most one row: the step might have dropped a row first.
@@ -3304,7 +3317,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
             Q.Wrow[q] = (typename SM::Sol::row_t)p;
             Q.act[p] = (signed char)sgi;
             Q.slot[p] = (unsigned char)q;
-            if constexpr (ANTICYCLE) {
+            if constexpr (VT::ANTICYCLE) {
               const unsigned fc = Q.flpc[p];
               if ((fc >> 1) < 127u) Q.flpc[p] = (unsigned char)(fc + 2u);
               if ((fc >> 1) + 1u >= (unsigned)HMPC_READD_LIMIT) S.pad0 = 1;  // this row keeps coming back: the loop head reacts
@@ -3316,7 +3329,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
         } else {
           drop_slot(l);  // partial (or pure dual) step: slot l leaves
         }
-        if constexpr (REFRESHES) ++since_refresh;
+        if constexpr (VT::REFRESHES) ++since_refresh;
         PROF_MARK(P_UPD);
       }
       if (code != S_OK) break;
@@ -3324,8 +3337,8 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     if (code != S_OK || q == 0) break;
     // nothing happened in this pass: either the refined point of the previous pass is feasible, or (first pass) the block
     // start already is the optimum -- its x, u, E come straight from the inversion, there is nothing to refine
-    if (iters == iters_at_entry && !(CONT && budget_hit) && !(ANTICYCLE && perturbed)) break;
-    if constexpr (LONGRUN) {
+    if (iters == iters_at_entry && !(VT::RESUMES && budget_hit) && !(VT::ANTICYCLE && perturbed)) break;
+    if constexpr (VT::LONGRUN) {
       if (ub(since_refresh >= REFRESH_FINAL)) {  // the answer is read off a freshly built E; the loop above then confirms it
         __syncthreads();
         (void)block_round(3, true);
@@ -3339,7 +3352,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       // (the first correction takes its residual at the iterate the loop above left -- x was moved along with u
       //  step by step, and what the correction is there to remove is the drift of E's rank-one updates, orders of magnitude above
       //  the difference between that x and x(u) -- instead of recomputing x(u) first: one gather + one product with M less)
-      if (!(!LONGRUN && it == 0 && HMPC_REFINE > 0)) {
+      if (!(!VT::LONGRUN && it == 0 && HMPC_REFINE > 0)) {
       gather_w(Q.u, 1.0, 0.0);
       __syncthreads();
       rmatvec(Q.w);
@@ -3355,13 +3368,13 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
       __syncthreads();
     }
     PROF_MARK(P_POLISH);
-    if constexpr (CONT) {
+    if constexpr (VT::RESUMES) {
       if (budget_hit) break;  // (no further pass: the KKT check below decides)
     }
     // a refinement that moved x across another constraint sends us back into the main loop (rare)
   }
 
-  if constexpr (SPILLS) {
+  if constexpr (VT::SAVES) {
     if (args.spill_slot) {  // uniform
       int slot = -1;
       if (code == S_WORKSET && args.spill) {  // uniform: hand the live state over (SpillLayout)
@@ -3427,11 +3440,11 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     }
     // (no barrier behind the reads: the only other writer of the three arrays -- a second call in the last-resort pass -- comes
     //  after the barriers of that pass)
-    constexpr double KKT_TOL = LONGRUN ? 2e-5 : 2e-6;
+    constexpr double KKT_TOL = VT::LONGRUN ? 2e-5 : 2e-6;
     return !(val < -KKT_TOL * xmax || umin < -1e-6 * xmax);  // relative to the force scale
   };
   if (code == S_OK && !ub(kkt_ok())) code = S_KKT;  // (the reductions leave the same values in every lane: a scalar decision)
-  if ((ANTICYCLE ? ub(S.relax != 0.0) : ub(args.relax != 0.0)) && code == S_OK) {
+  if ((VT::ANTICYCLE ? ub(S.relax != 0.0) : ub(args.relax != 0.0)) && code == S_OK) {
     // Last-resort pass (bounds moved outward, hmpc_resolve_failed): the perturbation was only there to separate coinciding
     // vertices.  With the working set it ended on, the multipliers and the point are re-solved for the EXACT bounds
     // (x(u) is linear in u: one correction u += E (b_W - N_W x(u)) lands on the exact vertex) and the KKT check is repeated
@@ -3444,7 +3457,7 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     __syncthreads();
     if (tid == 0) S.relax = 0.0;
     __syncthreads();
-    if constexpr (!LAZY) {
+    if constexpr (!VT::LAZY) {
       if (is_c) c_ub_r = row_ub_calc();
     }
     active_residual(Q.x);
@@ -3477,8 +3490,8 @@ __global__ __launch_bounds__(NT, (NT < 512 && fits_three_waves<NMAX, HMAX, NT, Q
     // (an instance that ran into the CALLER'S iteration cap is the caller's answer: it is neither counted nor listed for the
     //  safe pass -- the device-side repair would otherwise re-solve it cold and overwrite its last iterate)
     const bool capped = (code == S_MAXITER) && (args.iter_cap > 0 && args.iter_cap < itmax_v);
-    if constexpr (REGULARISES) code = (args.reg_step == 1 && code == S_OK) ? (int)S_REG_STEP : code;  // x_1 of the regularised QP: one more step to go
-    stage_output<NMAX, HMAX, NT, QCAP, NC, BPT>(S, args, inst, h, n, q, iters, code, capped, RESUMABLE && resumed);
+    if constexpr (VT::REGULARISES) code = (args.reg_step == 1 && code == S_OK) ? (int)S_REG_STEP : code;  // x_1 of the regularised QP: one more step to go
+    stage_output<NMAX, HMAX, NT, QCAP, NC, BPT>(S, args, inst, h, n, q, iters, code, capped, VT::RESUMES && resumed);
 #ifdef HMPC_DEBUG_STATS
     if (tid == 0 && args.obj64) args.obj64[inst] = (dbg_viol > 0.0) ? -dbg_viol : (double)(dbg_bad + 10 * dbg_rounds + 1000 * dbg_norounds_cap + 10000 * dbg_norounds_few + 100000 * dbg_dep);
 #endif

@@ -1,10 +1,19 @@
 // hmpc_kernel_args.h -- what the host side needs to know of the fused kernel (hmpc_kernel.h): its argument block, the status
-// codes, the layout of the assembly debug dump.  Kept apart from the 2 900-line kernel template so that the host translation
+// codes, the layout of the assembly debug dump, the roles a variant can have.  Kept apart from the 3 500-line kernel header so that the host translation
 // units (hmpc_capi.hip, hmpc_group.hip) compile in seconds and the kernel family builds in parallel (hmpc_variants.hip).
 #pragma once
 #include <stdint.h>
 
+#ifndef HMPC_QCAP_CONT
+#define HMPC_QCAP_CONT 96  // working-set capacity of the CONTINUATION variant of the 120-variable shapes (70 KB LDS: two per CU): takes over the solves whose working set outgrew the fast variant's
+#endif
+
 namespace hmpc {
+
+// A variant's part in a solve (the ROLE column of hmpc_variants.h; what follows from it: VariantTraits in hmpc_kernel.h).  FAST: the first
+// pass of every solve (on the hand-over shape it saves a working set that outgrew it); CONT: resumes those; SAFE: re-solves what is
+// still flagged; SWEEP: command sweeps (a workgroup per chunk of instances sharing state and gait)
+enum class Role { FAST, CONT, SAFE, SWEEP };
 
 struct KernelArgs {
   const unsigned char *records;
@@ -67,8 +76,8 @@ struct KernelArgs {
   // Goldfarb-Idnani state -- point x, x_u, multipliers u, the working set (act / slot / Wrow), the packed Schur inverse E and the
   // 6 x 6 register blocks of M = H^-1 -- to the instance's own slot of `spill` (slot = instance index; spill_stride bytes each,
   // spill_cap slots; layout: SpillLayout in hmpc_kernel.h) and leaves the slot number in spill_slot[inst] (-1: nothing saved).
-  // The continuation -- the safe variant of the same shape, whose working set holds as many rows as there are variables,
-  // launched over the flagged list with `resume` set -- re-assembles the instance's constraint data (cheap, bit-identical),
+  // The continuation -- the CONT variant of the same shape, whose working set holds HMPC_QCAP_CONT rows, launched over the
+  // flagged list with `resume` set -- re-assembles the instance's constraint data (cheap, bit-identical),
   // takes M, E and the state from the slot instead of inverting H and starting cold, goes on with the iteration where the
   // fast variant stopped, and marks the slot consumed.  nullptr / 0 = off (a full working set is flagged S_WORKSET as before and
   // re-solved cold).
@@ -82,7 +91,7 @@ struct KernelArgs {
   // optional per-INSTANCE friction parameter (hmpc_set_instance_mu: terrain sweeps): mu_inst[inst] replaces mu; nullptr = off.  H does
   // not depend on it (only the friction rows of the constraint block do), so instances of one command-sweep group may differ in it
   const float *mu_inst;
-  // command sweeps (MODE 1 kernels, hmpc_solve_command_sweep): groups of sweep_k consecutive records that differ in the reference
+  // command sweeps (the SWEEP variants, hmpc_solve_command_sweep): groups of sweep_k consecutive records that differ in the reference
   // trajectory only; sweep_phase 0 = one workgroup per group forms M = H^-1 and writes it to sweep_m[group][36][NT], phase 1 =
   // one workgroup per instance solves with its group's M
   int sweep_k, sweep_phase;

@@ -8,28 +8,23 @@
 #ifndef HMPC_QCAP_FAST
 #define HMPC_QCAP_FAST 64  // working-set capacity of the fast 120-variable h <= 10 variant (49 KB LDS: three per CU)
 #endif
-#ifndef HMPC_QCAP_CONT
-#define HMPC_QCAP_CONT 96  // ... of the CONTINUATION variant of the 120-variable shapes (70 KB LDS: two per CU): takes over the solves whose working set outgrew the fast variant's
-#endif
+// (HMPC_QCAP_CONT, the capacity of the CONTINUATION variant of the same shapes: hmpc_kernel_args.h, which the kernel sees as well)
 // (not switches: each is pinned from both sides by the LDS budget and the staging areas that alias the solver state --
-//  static_asserts in hmpc_kernel.h / hmpc_variants.hip -- 152 rows are what 160 KB leave next to the wide variant's mat-vec staging,
+//  static_asserts of VariantTraits, hmpc_kernel.h -- 152 rows are what 160 KB leave next to the wide variant's mat-vec staging,
 //  96 what 80 KB, two workgroups per CU, leave the three-contact one)
 constexpr int HMPC_QCAP_WIDE = 152;  // ... of the 240-variable variant (double support over h = 11 .. 20)
 constexpr int HMPC_QCAP_3C = 96;     // ... of the fast three-contact variant (256 threads, two register blocks each, <= 80 KB LDS: two per CU)
 
 typedef void (*kernel_fn)(hmpc::KernelArgs);
-
-// FAST: the first pass of every solve (on the hand-over shape it saves a working set that outgrew it); CONT: resumes those; SAFE:
-// re-solves what is still flagged; SWEEP: command sweeps (kernel MODE 1: a workgroup per chunk of instances sharing state and gait)
-enum class Role { FAST, CONT, SAFE, SWEEP };
+using hmpc::Role;  // FAST, CONT, SAFE, SWEEP (hmpc_kernel_args.h); what follows from a row's role and shape: VariantTraits, hmpc_kernel.h
 struct Variant {
   int nmax, hmax, nt, qcap, nc;
   Role role;
+  bool e_global;  // the packed Schur inverse lives in KernelArgs::e_scratch, a slice per workgroup of the launch (VariantTraits::EGLOBAL)
   kernel_fn solve, assemble;  // assemble: the assembly-only debug kernel (FAST variants only, nullptr otherwise)
   size_t smem;
   int dbg_floats;
-  // bytes of one hand-over slot (KernelArgs::spill) when this variant SAVES its state (FAST on the hand-over shape), 0 otherwise
-  size_t spill_stride;
+  size_t spill_stride;  // bytes of one hand-over slot (KernelArgs::spill) when this variant SAVES its state (FAST on the hand-over shape), 0 otherwise
 };
 
 // index = position in hmpc_capi.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE), group = translation unit that builds it.

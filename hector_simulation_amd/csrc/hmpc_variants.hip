@@ -1,5 +1,5 @@
 // hmpc_variants.hip -- instantiates the kernel family of hmpc_kernel.h.  Built once per group (-DHMPC_VARIANT_GROUP=k,
-// hector_simulation_amd/build.py) into separate objects: the 2 900-line kernel template costs 5-20 s per instantiation, and
+// hector_simulation_amd/build.py) into separate objects: the kernel template (hmpc_kernel.h, 3 500 lines) costs 5-20 s per instantiation, and
 // the fifteen variants (21 kernels: a solve kernel each, an assembly-only one per fast variant) compile side by side instead of in
 // one long translation unit.
 #include <hip/hip_runtime.h>
@@ -14,19 +14,11 @@
 namespace {
 template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT, Role ROLE>
 Variant make_variant() {
-  using SM = hmpc::Smem<NMAX, HMAX, NT, QCAP, NC, BPT>;
-  static_assert(sizeof(SM) <= 160 * 1024, "LDS budget of a gfx950 CU");
-  static_assert(BPT == 1 || NT >= 512 || sizeof(SM) <= 80 * 1024, "two workgroups per CU");
-  // (the same shape test as SHAPE_HANDOVER / SPILLS / RESUMABLE in hmpc_kernel.h)
-  constexpr bool handover = NMAX == 120 && NT == 256 && NC == 2 && BPT == 1 && QCAP != 0;
-  static_assert(!handover || (QCAP < HMPC_QCAP_CONT) == (ROLE == Role::FAST || ROLE == Role::SWEEP), "hand-over: the fast variants save");
-  static_assert((ROLE == Role::CONT) == (handover && QCAP >= HMPC_QCAP_CONT && QCAP < NMAX), "hand-over: the continuation variants resume");
-  constexpr int MODE = ROLE == Role::SWEEP ? 1 : 0;
+  using VT = hmpc::VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, ROLE>;
   kernel_fn assemble = nullptr;  // (the assembly-only debug kernel: hmpc_debug_assemble launches the fast variant's)
-  if constexpr (ROLE == Role::FAST) assemble = hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, true, NC, BPT, 0>;
-  return Variant{NMAX, HMAX, NT, QCAP, NC, ROLE, hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, false, NC, BPT, MODE>, assemble, sizeof(SM),
-                 hmpc::DbgLayout<NMAX, NC>::TOTAL,
-                 (handover && ROLE == Role::FAST) ? hmpc::SpillLayout<SM, NT, BPT>::stride_for(QCAP) : 0};
+  if constexpr (ROLE == Role::FAST) assemble = hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, true, NC, BPT, ROLE>;
+  return Variant{NMAX, HMAX, NT, QCAP, NC, ROLE, VT::EGLOBAL, hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, false, NC, BPT, ROLE>, assemble,
+                 sizeof(typename VT::SM), hmpc::DbgLayout<NMAX, NC>::TOTAL, VT::SPILL_STRIDE};
 }
 }  // namespace
 

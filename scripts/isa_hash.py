@@ -6,7 +6,9 @@
 
 What a refactor of hmpc_kernel.h that must not change the product (macro removal, a stage moved into a function) is checked
 with: the kernel's instructions as llvm-objdump prints them (addresses and symbol-relative branch targets stripped), hashed
-per kernel symbol.  Two builds with the same hash run the same instructions."""
+per kernel symbol.  Two builds with the same hash run the same instructions.  --diff pairs kernels across a rename: an old
+row whose name is gone is matched to a new kernel with the same hash and instruction count; only what stays unmatched is
+CHANGED / NEW / MISSING."""
 import concurrent.futures
 import hashlib
 import os
@@ -90,8 +92,15 @@ def main():
         for line in open(diff_path):
             p = line.split(None, 2)
             if len(p) == 3:
-                old[p[2].strip()] = p[0]
-        changed = [k for k, (h, _) in hs.items() if k in old and old[k] != h]
+                old[p[2].strip()] = (p[0], int(p[1]))
+        # a rename (a template parameter changed its type or its name): an old row whose name is gone is the new kernel with
+        # the same hash and instruction count -- the hash does not depend on the symbol
+        for k in [k for k in hs if k not in old]:
+            gone = sorted(o for o in old if o not in hs and old[o] == hs[k])
+            if gone:
+                print("RENAMED", gone[0], "->", k)
+                old[k] = old.pop(gone[0])
+        changed = [k for k, (h, _) in hs.items() if k in old and old[k][0] != h]
         missing = [k for k in old if k not in hs and not groups]
         new = [k for k in hs if k not in old]
         for k in changed:

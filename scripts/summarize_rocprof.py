@@ -147,7 +147,7 @@ def variant_lines(dst):
         with open(ks) as fh:
             for r in csv.DictReader(fh):
                 if "hmpc_kernel" in r["Name"] and int(r["Calls"]) > calls:
-                    name, avg, calls = r["Name"].split("(")[0].replace("void hmpc::", ""), float(r["AverageNs"]) / 1e6, int(r["Calls"])
+                    name, avg, calls = r["Name"].rsplit("(", 1)[0].replace("void hmpc::", ""), float(r["AverageNs"]) / 1e6, int(r["Calls"])
         nb = int(case.split("_b")[-1])
         acc = defaultdict(list)
         if os.path.exists(pm):
@@ -190,17 +190,20 @@ def write_readme(dst, rnd, means, extra=()):
             if "hmpc_kernel" in r["Name"]:
                 avg_ms = float(r["AverageNs"]) / 1e6
                 lines.append("* `kernel_stats.csv`: `%s` -- %s calls, average **%.4f ms** per 8192-instance launch = %.3f M "
-                             "solves/s (kernel only)" % (r["Name"].split("(")[0], r["Calls"], avg_ms, 8192 / avg_ms / 1e3))
+                             "solves/s (kernel only)" % (r["Name"].rsplit("(", 1)[0], r["Calls"], avg_ms, 8192 / avg_ms / 1e3))
     bj = os.path.join(dst, "bench_standing.json")
     if os.path.exists(bj):
         try:
             b = json.loads(open(bj).read().strip().splitlines()[-1])
-            lines.append("* `bench_standing.json`: value %.4g %s, ms_per_step %.4f, HIP-event kernel_ms %.4f, roofline.frac %.3g, "
-                         "roofline_mfma.frac %.3g, fp64_valu_frac %.3g, iterations/solve %.2f; cpu_baseline (%s, %d cores) %.0f solves/s"
-                         % (b["value"], b["unit"], b["ms_per_step"], b["roofline"]["kernel_ms"], b["roofline"]["frac"],
-                            b["roofline_mfma"]["frac"], b.get("fp64_valu_frac", float("nan")), b.get("iterations_per_solve", float("nan")),
-                            b.get("cpu_baseline", {}).get("kind", "-"), b.get("cpu_baseline", {}).get("cores", 0),
-                            b.get("cpu_baseline", {}).get("value", float("nan"))))
+            if "roofline" not in b:  # a plain run (no --full): the headline figure and nothing else
+                lines.append("* `bench_standing.json` (plain run): value %.4g %s, ms_per_step %.4f" % (b["value"], b["unit"], b["ms_per_step"]))
+            else:
+                lines.append("* `bench_standing.json`: value %.4g %s, ms_per_step %.4f, HIP-event kernel_ms %.4f, roofline.frac %.3g, "
+                             "roofline_mfma.frac %.3g, fp64_valu_frac %.3g, iterations/solve %.2f; cpu_baseline (%s, %d cores) %.0f solves/s"
+                             % (b["value"], b["unit"], b["ms_per_step"], b["roofline"]["kernel_ms"], b["roofline"]["frac"],
+                                b["roofline_mfma"]["frac"], b.get("fp64_valu_frac", float("nan")), b.get("iterations_per_solve", float("nan")),
+                                b.get("cpu_baseline", {}).get("kind", "-"), b.get("cpu_baseline", {}).get("cores", 0),
+                                b.get("cpu_baseline", {}).get("value", float("nan"))))
         except Exception as exc:  # keep the README honest rather than failing the summary
             lines.append("* `bench_standing.json`: could not be parsed (%r)" % (exc,))
     tj = os.path.join(ROOT, "profiles", "hbm_traffic.json")
