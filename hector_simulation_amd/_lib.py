@@ -26,6 +26,8 @@ EXPORTS = [
     "hmpc_upload_records_strided_async", "hmpc_set_max_iterations", "hmpc_legacy_set_max_iterations", "hmpc_tick_solve_device", "hmpc_set_dispatch_order",
     "hmpc_set_handover", "hmpc_default_params", "hmpc_set_params", "hmpc_get_params", "hmpc_legacy_set_params", "hmpc_group_set_params",
     "hmpc_solve_command_sweep", "hmpc_set_instance_mu", "hmpc_group_solve_command_sweep", "hmpc_debug_handover_slots",
+    "hmpc_predict_states", "hmpc_set_device_prediction", "hmpc_get_device_prediction", "hmpc_download_prediction",
+    "hmpc_legacy_predicted_state",
 ]
 
 
@@ -173,6 +175,12 @@ def load():
     L.hmpc_group_last_error.restype = C.c_char_p
     L.hmpc_debug_phase_cycles.argtypes = [vp, vp]
     L.hmpc_debug_handover_slots.argtypes = [vp, vp]
+    L.hmpc_predict_states.argtypes = [vp, vp]
+    L.hmpc_set_device_prediction.argtypes = [vp, vp, vp]
+    L.hmpc_get_device_prediction.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.hmpc_download_prediction.argtypes = [vp, vp, vp]
+    L.hmpc_legacy_predicted_state.argtypes = [ci, ci]
+    L.hmpc_legacy_predicted_state.restype = cd
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

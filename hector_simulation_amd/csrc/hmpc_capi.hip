@@ -19,6 +19,7 @@
 #include "hmpc_kernel_args.h"
 #include "hmpc_variants.h"
 #include "hmpc_builder.h"
+#include "hmpc_predict.h"
 
 namespace {
 
@@ -137,6 +138,13 @@ struct hmpc_handle {
   hmpc_params params;  // robot / contact constants (hmpc_set_params; defaults = the reference's literals)
   const float *d_mu_inst;  // hmpc_set_instance_mu: per-instance friction parameter in HBM (caller-owned), nullptr = params.mu for all
   double *d_reg_rho;  // Hessians that are not positive definite: the pivot the safe variant found, then rho of hmpc_resolve_failed's regularisation steps, per instance (allocated with the first list launch)
+  // prediction (hmpc_predict_states): states [max_batch][horizon][13] binary32 and cost [max_batch][2] binary64; the handle's own buffers
+  // are allocated by the first call that needs them, d_pred_* = where the next prediction goes (the caller's, hmpc_set_device_prediction,
+  // or nullptr = the handle's own)
+  float *d_pred_states_own, *d_pred_states;
+  double *d_pred_cost_own, *d_pred_cost;
+  bool solve_enqueued;    // a solve of the CURRENT batch has been enqueued (cleared by everything that replaces the batch)
+  bool predict_enqueued;  // ... and a prediction behind it (cleared by every later solve as well: its forces are newer)
   double *d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
   size_t sweep_m_bytes;
 };
@@ -231,6 +239,22 @@ struct LaunchOpt {
 // HMPC_S_INDEFINITE; the two counters sit next to each other (one memset clears both)
 static int flag_list_cap(const hmpc_handle *h) { return h->max_batch < REPAIR_GRID_CAP ? h->max_batch : REPAIR_GRID_CAP; }
 
+// What stage A of a kernel reads of the handle: the batch, the problem shape and the robot / contact constants.  One place, so that the
+// prediction kernel (hmpc_predict_states) assembles from the very values the solve kernels do.
+static void set_problem_args(const hmpc_handle *h, hmpc::KernelArgs &a) {
+  a.records = h->d_records;
+  a.stride = (int)h->stride;
+  a.batch = h->batch;
+  a.horizon = h->setup.horizon;
+  a.dt = h->setup.dt;
+  a.f_max = h->setup.f_max;
+  a.forces = h->d_forces;
+  a.inv_mass = 1.0f / h->params.mass;  // (binary32 division, correctly rounded: the value the reference's 1.f / 9.f folds to for the default)
+  a.Ib[0] = h->params.inertia[0], a.Ib[1] = h->params.inertia[1], a.Ib[2] = h->params.inertia[2];
+  a.mu = h->params.mu, a.lt = h->params.lt, a.lh = h->params.lh, a.gravity = h->params.gravity;
+  a.mu_inst = h->d_mu_inst;
+}
+
 // One launch of variants()[vi].  A list launch of the CONTINUATION variant resumes the listed instances whose fast solve handed its
 // state over (KernelArgs::resume = 2) and leaves every other one alone; where nothing can have been handed over it launches nothing.
 static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
@@ -270,13 +294,6 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
     h->attrs_set[vi] = true;
   }
   hmpc::KernelArgs a;
-  a.records = h->d_records;
-  a.stride = (int)h->stride;
-  a.batch = h->batch;
-  a.horizon = h->setup.horizon;
-  a.dt = h->setup.dt;
-  a.f_max = h->setup.f_max;
-  a.forces = h->d_forces;
   a.status = h->d_status;
   a.x64 = h->d_x64;
   a.obj64 = h->d_obj64;
@@ -317,10 +334,7 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
   if (o.list_indefinite && h->d_flag_list && h->d_flag_count)
     a.reg_list = h->d_flag_list + flag_list_cap(h), a.reg_count = h->d_flag_count + 1, a.reg_cap = REG_LIST_CAP;
   a.sweep_k = o.sweep_k > 0 ? o.sweep_k : 1, a.sweep_phase = o.sweep_phase, a.sweep_m = h->d_sweep_m;
-  a.inv_mass = 1.0f / h->params.mass;  // (binary32 division, correctly rounded: the value the reference's 1.f / 9.f folds to for the default)
-  a.Ib[0] = h->params.inertia[0], a.Ib[1] = h->params.inertia[1], a.Ib[2] = h->params.inertia[2];
-  a.mu = h->params.mu, a.lt = h->params.lt, a.lh = h->params.lh, a.gravity = h->params.gravity;
-  a.mu_inst = h->d_mu_inst;
+  set_problem_args(h, a);
   for (int off = 0; off < grid_all; off += chunk) {
     const int grid = (grid_all - off < chunk) ? grid_all - off : chunk;
     if (off > 0) a.index_list = o.d_index_list + off;  // (only list launches are ever chunked)
@@ -372,6 +386,7 @@ static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes
     const int rc = launch(h, stream, l[k].vi, o);
     if (rc != HMPC_OK) return rc;
   }
+  h->solve_enqueued = true, h->predict_enqueued = false;  // (every solve of a batch starts here: hmpc_predict_states)
   return HMPC_OK;
 }
 
@@ -638,6 +653,8 @@ int hmpc_destroy(hmpc_handle *h) {
   if (h->d_reg_rho) hipFree(h->d_reg_rho);
   if (h->d_spill) hipFree(h->d_spill);
   if (h->d_spill_slot) hipFree(h->d_spill_slot);
+  if (h->d_pred_states_own) hipFree(h->d_pred_states_own);
+  if (h->d_pred_cost_own) hipFree(h->d_pred_cost_own);
   delete h;
   return HMPC_OK;
 }
@@ -658,6 +675,7 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
     HIP_TRY(hipMemcpy(h->d_records_own, host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice));
   h->d_records = h->d_records_own;
   h->batch = batch;
+  h->solve_enqueued = h->predict_enqueued = false;
   h->cls_valid = 0;
   // host-side scan of the gait tables: the widest reduced QP in the batch picks the kernel variant (LDS footprint)
   const int hz = h->setup.horizon;
@@ -708,6 +726,7 @@ int hmpc_set_device_records(hmpc_handle *h, const void *device_records, int batc
   if (batch > h->max_batch) return HMPC_E_BATCH;
   h->d_records = (const unsigned char *)device_records;
   h->batch = batch;
+  h->solve_enqueued = h->predict_enqueued = false;
   h->max_stance = -1;  // unknown: hmpc_solve counts the size classes on the device (or hmpc_set_max_reduced_vars tells)
   h->cls_valid = 0;
   return HMPC_OK;
@@ -1186,6 +1205,7 @@ int hmpc_build_records_device(hmpc_handle *h, const void *device_ticks, int batc
   }
   h->d_records = h->d_records_own;
   h->batch = batch;
+  h->solve_enqueued = h->predict_enqueued = false;
   h->max_stance = -1;  // the builder left every instance's size class on the device: hmpc_solve routes by it
   h->cls_valid = 1;
   h->last_stream = (hipStream_t)stream;
@@ -1345,6 +1365,71 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Prediction: the model's own state trajectory and tracking cost under the forces of the last solve (hmpc_predict.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next prediction goes: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int prediction_buffers(hmpc_handle *h, float **states, double **cost) {
+  if (!h->d_pred_states && !h->d_pred_states_own)
+    HIP_TRY(hipMalloc(&h->d_pred_states_own, (size_t)h->max_batch * h->setup.horizon * 13 * sizeof(float)));
+  if (!h->d_pred_cost && !h->d_pred_cost_own) HIP_TRY(hipMalloc(&h->d_pred_cost_own, (size_t)h->max_batch * 2 * sizeof(double)));
+  *states = h->d_pred_states ? h->d_pred_states : h->d_pred_states_own;
+  *cost = h->d_pred_cost ? h->d_pred_cost : h->d_pred_cost_own;
+  return HMPC_OK;
+}
+
+int hmpc_set_device_prediction(hmpc_handle *h, float *device_states, double *device_cost) {
+  if (!h) return HMPC_E_ARG;
+  h->d_pred_states = device_states, h->d_pred_cost = device_cost;
+  h->predict_enqueued = false;  // (whatever was predicted went elsewhere)
+  return HMPC_OK;
+}
+
+int hmpc_get_device_prediction(hmpc_handle *h, float **device_states, double **device_cost) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  float *s = nullptr;
+  double *c = nullptr;
+  const int rc = prediction_buffers(h, &s, &c);
+  if (rc != HMPC_OK) return rc;
+  if (device_states) *device_states = s;
+  if (device_cost) *device_cost = c;
+  return HMPC_OK;
+}
+
+int hmpc_predict_states(hmpc_handle *h, void *stream) {
+  if (!h || !h->solve_enqueued) return HMPC_E_ARG;  // no solve of the current batch: the force buffer holds another batch's forces, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  float *s = nullptr;
+  double *c = nullptr;
+  const int rc = prediction_buffers(h, &s, &c);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it)
+  set_problem_args(h, a);
+  a.mu_inst = nullptr;  // (friction shapes the constraint block only; the model does not depend on it)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_predict(h->nc, a, s, c, (hipStream_t)stream));
+  h->predict_enqueued = true;
+  return HMPC_OK;
+}
+
+int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->predict_enqueued) return HMPC_E_ARG;  // nothing predicted from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  float *s = nullptr;
+  double *c = nullptr;
+  const int rc = prediction_buffers(h, &s, &c);
+  if (rc != HMPC_OK) return rc;
+  if (states) HIP_TRY(hipMemcpy(states, s, (size_t)h->batch * h->setup.horizon * 13 * sizeof(float), hipMemcpyDeviceToHost));
+  if (cost) HIP_TRY(hipMemcpy(cost, c, (size_t)h->batch * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The reference's own interface (convexMPC_interface.cpp:42-118): process-global, single-threaded, blocking.
 // ------------------------------------------------------------------------------------------------------------------
 static problem_setup g_setup = {0.f, 0.f, 0.f, 0};
@@ -1356,6 +1441,8 @@ static int g_has_solved = 0;
 static uint32_t g_last_status = 0;
 static int g_setup_error = 0;
 static hmpc_params g_legacy_params = {9.0f, {0.5413f, 0.5200f, 0.0691f}, 2.0f, 0.09f, 0.06f, 9.81f};  // hmpc_legacy_set_params
+static float g_pred[13 * HMPC_MAX_HORIZON];  // hmpc_legacy_predicted_state: the last solve's predicted states, fetched on first use
+static int g_pred_valid = 0;
 static int g_legacy_iter_cap = 0;  // hmpc_legacy_set_max_iterations: explicit opt-in (update_solver_settings is inert, as in the reference)
 // one tick = one pinned staging buffer [record | 12h forces | status word] and one contiguous device output block, so that
 // a blocking tick costs one asynchronous H2D copy, one launch, one asynchronous D2H copy and a single synchronisation
@@ -1469,6 +1556,7 @@ static void solve_global(void) {
   if (code != HMPC_S_OK && code != HMPC_S_OK_RELAXED) printf("failed to solve!\n");
   for (int i = 0; i < 12 * hz; ++i) g_q_soln[i] = (double)forces[i];
   g_has_solved = 1;
+  g_pred_valid = 0;
 }
 
 void update_problem_data(double *p, double *v, double *q, double *w, double *r, double *joint_angles, double yaw,
@@ -1490,6 +1578,21 @@ double get_solution(int index) {
   if (!g_has_solved) return 0.0;  // convexMPC_interface.cpp:107
   if (index < 0 || index >= g_q_len) return 0.0;
   return g_q_soln[index];
+}
+
+double hmpc_legacy_predicted_state(int step, int component) {
+  if (!g_has_solved || !g_handle) return 0.0;  // as get_solution: 0 before the first solve and for out-of-range arguments
+  if (step < 0 || step >= g_setup.horizon || component < 0 || component >= 13) return 0.0;
+  if (!g_pred_valid) {  // once per solve, on first use: one launch and one small copy
+    int rc = hmpc_predict_states(g_handle, nullptr);
+    if (rc == HMPC_OK) rc = hmpc_download_prediction(g_handle, g_pred, nullptr);
+    if (rc != HMPC_OK) {
+      fprintf(stderr, "[hector_mpc_hip] prediction failed (%d): %s\n", rc, hmpc_last_hip_error());
+      return 0.0;
+    }
+    g_pred_valid = 1;
+  }
+  return (double)g_pred[13 * step + component];
 }
 
 void update_solver_settings(int max_iter, double rho, double sigma, double solver_alpha, double terminate,

@@ -58,6 +58,12 @@ def legacy_set_max_iterations(max_iter: int) -> None:
     _check(_lib.load().hmpc_legacy_set_max_iterations(int(max_iter)), "hmpc_legacy_set_max_iterations")
 
 
+def legacy_predicted_state(step: int, component: int) -> float:
+    """Component (0..12) of the state the process-global solver's model predicts for ``step`` (0..horizon-1) under its last solution
+    (include/hector_mpc.h hmpc_legacy_predicted_state); 0 before the first solve and for out-of-range arguments."""
+    return float(_lib.load().hmpc_legacy_predicted_state(int(step), int(component)))
+
+
 def last_status() -> int:
     return int(_lib.load().hmpc_last_status())
 
@@ -222,6 +228,27 @@ class BatchedMPC:
         obj = np.zeros(b, dtype=np.float64)
         _check(self.L.hmpc_download_f64(self.h, x.ctypes.data, obj.ctypes.data), "hmpc_download_f64")
         return x, obj
+
+    def predict_states(self, stream: int = 0) -> None:
+        """One launch behind the solve on ``stream``: the model's predicted states and tracking cost under the forces in the force buffer
+        (include/hector_mpc.h hmpc_predict_states).  Raises when no solve of the current batch has been enqueued."""
+        _check(self.L.hmpc_predict_states(self.h, C.c_void_p(stream)), "hmpc_predict_states")
+
+    def download_prediction(self):
+        """(states[batch, horizon, 13] float32: row i = the state after step i; cost[batch, 2] float64: tracking, force).  Waits; runs no
+        safe pass (``download()`` first, then ``predict_states()`` again, for repaired forces)."""
+        b = self.batch
+        states = np.zeros((b, self.horizon, 13), dtype=np.float32)
+        cost = np.zeros((b, 2), dtype=np.float64)
+        _check(self.L.hmpc_download_prediction(self.h, states.ctypes.data, cost.ctypes.data), "hmpc_download_prediction")
+        return states, cost
+
+    def set_device_prediction(self, states_ptr: int, cost_ptr: int, keepalive=None) -> None:
+        """Caller-owned device buffers for later predictions (float32[max_batch, horizon, 13], float64[max_batch, 2]; 0 / None = the
+        handle's own)."""
+        self._keep_pred = keepalive
+        _check(self.L.hmpc_set_device_prediction(self.h, C.c_void_p(int(states_ptr or 0)), C.c_void_p(int(cost_ptr or 0))),
+               "hmpc_set_device_prediction")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

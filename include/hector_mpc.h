@@ -372,6 +372,44 @@ int hmpc_leg_torques_device(hmpc_handle *h, const double *device_rBody, const do
  * the torques are computed from repaired forces.  Two-contact handles only. */
 int hmpc_tick_solve_device(hmpc_handle *h, const void *device_ticks, int batch, double dtMPC, double *device_wpd_out,
                            double *device_f_ff, double *device_tau, void *stream);
+/* ---- the predicted state trajectory and tracking cost of every instance ----
+ * The QP minimises over an h-step prediction of the body state; these calls return it.  Per instance, with U = 6 * contacts,
+ * x0[13], Acd[13][13], Bcd[13][U] THE binary32 values the solve kernel assembles for the record (hmpc_params included; the prediction
+ * kernel calls the solve kernel's own assembly stage) and u_i[U] step i of the handle's force buffer as it stands:
+ *   x_0 = x0;   x_{i+1}[s] = sum_{k<13} Acd[s][k] x_i[k] + sum_{c<U} Bcd[s][c] u_i[c],   i = 0 .. h-1,
+ * evaluated in binary64 as one ascending chain of fused multiply-adds started at +0 (state terms, then force terms; every term, the
+ * structural zeros too), each step taking the un-rounded x_i.  State order as the reference's (SolverMPC.cpp:420): roll pitch yaw,
+ * position, angular velocity, velocity, gravity constant.
+ *   states[batch][h][13]  binary32; row i = x_{i+1}, rounded once (column 12 is x0[12], the gravity constant, in every row)
+ *   cost[batch][2]        binary64, from the un-rounded states, in a fixed summation order:
+ *                         cost[0] = sum_{s<12} sum_i weights[s] (x_{i+1}[s] - traj[12 i + s])^2       (tracking)
+ *                         cost[1] = sum_{c<U} sum_i Alpha_K[c] u_i[c]^2                               (force)
+ * cost[0] + cost[1] is the reference's QP objective plus the constant the QP drops (the cost of applying no force).  The states are
+ * the model's own prediction; the binary32 matrix powers inside H and g (the reference's A_qp, B_qp) differ from it by their
+ * round-off, 5e-7 absolute on states of order 1.
+ * The prediction is a pure function of (record, hmpc_params, force buffer): it does not depend on launch shape, dispatch order or on
+ * which pass wrote the forces.  An instance whose status word is not HMPC_S_OK / HMPC_S_OK_RELAXED is predicted all the same, from
+ * whatever its slot of the force buffer holds -- the last iterate, or zeros (HMPC_S_TOO_LARGE, HMPC_S_SWEEP_MISMATCH,
+ * HMPC_S_INDEFINITE): check the status words.
+ *
+ * hmpc_predict_states enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing: put
+ * it on the solve's stream, behind the solve and the device-side repair (hmpc_set_device_repair) if that is on.  It reads the forces
+ * where the solve wrote them (hmpc_set_device_outputs is honoured).  HMPC_E_ARG, nothing enqueued, when no solve -- hmpc_solve,
+ * hmpc_solve_command_sweep, hmpc_tick_solve_device, hmpc_debug_solve_external_qp -- has been enqueued since the current batch was set.
+ * hmpc_set_device_prediction: caller-owned device buffers for later predictions (either may be NULL = the handle's own, which are
+ * allocated for max_batch by the first call that needs them; never inside hmpc_solve).  hmpc_get_device_prediction: where the next
+ * prediction goes.  hmpc_download_prediction waits for the stream of the last call, then copies (either pointer may be NULL);
+ * HMPC_E_ARG when nothing has been predicted since the last solve of the current batch.  It does NOT run the safe pass: for repaired
+ * forces call hmpc_download (or hmpc_resolve_failed) first, then hmpc_predict_states again.
+ * Device groups: per member, through hmpc_group_member. */
+int hmpc_predict_states(hmpc_handle *h, void *stream);
+int hmpc_set_device_prediction(hmpc_handle *h, float *device_states, double *device_cost);
+int hmpc_get_device_prediction(hmpc_handle *h, float **device_states, double **device_cost);
+int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost);
+/* ... of the process-global solver behind setup_problem / update_problem_data: component (0..12) of the state predicted for
+ * `step` (0..horizon-1: x_{step+1}) under the last solution.  Predicts lazily, once per solve, on first use (one launch, one
+ * copy).  0 before the first solve and for out-of-range arguments, as get_solution. */
+double hmpc_legacy_predicted_state(int step, int component);
 /* copies the current batch's packed records device -> host (parity hook for f1/f2) */
 int hmpc_download_records(hmpc_handle *h, void *host_records);
 
