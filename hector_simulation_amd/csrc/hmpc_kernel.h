@@ -185,6 +185,9 @@ struct Smem {
     Asm a;
     Sol s;
   } u;
+  // matrix-core sweeps of the 120-variable shape: address words of the sweep-order variables for the tile loader (mfs_load).  Behind the
+  // union: no other member moves
+  int2 hadr[MFS2 ? NMAX : 1];
 };
 
 // Layout of one hand-over slot (KernelArgs::spill): what a fast variant whose working set is full leaves for the continuation
@@ -553,50 +556,73 @@ __device__ __forceinline__ void mfs_scale_exponents(const int n, HDiag hdiag, si
 }
 
 // Tiles from the binary32 staging of H, code specialised per wave (the 120-variable variants: the whole matrix is staged at
-// once).  hinfo(i): what the staging needs to know about sweep-order variable i (one LDS read); hval(hinfo(i), hinfo(j)):
-// H(i, j) from the staging, symmetric in its arguments.
-template <int NTG, int NWV, int WV, class HInfo, class HVal>
-__device__ __forceinline__ void mfs_load(MfsAcc<NTG, NWV> &acc, const int n, HInfo hinfo, HVal hval, const signed char *kexp) {
+// once).  Where H(i, j) lies in the staging is a ROW part of the variable that comes first in the staging's order plus a COLUMN
+// part of the other one (plus, KM != 0, KM step_i step_j: the block-diagonal layout is quadratic in the steps, and the cross term
+// is symmetric), all in bytes.  hadr[i], sweep-order variable i < n (written by mfma_sweeps from the caller's hpart):
+//   .x  row part;   .y  order key << 16 | column part  (KM != 0: the horizon step is the key's high byte, bits 24-31)
+// so that comparing two .y words compares the keys.  hread(byte offset): the staged value.
+// The sweep order is sorted by horizon step and a step has at most 12 variables, so in a tile (I, J) with J >= I + 2 every row
+// precedes every column: row part + column part and one multiply-add per entry.  Only the diagonal tiles and those with
+// J = I + 1 compare keys (a same-step block holds its upper triangle in reference order, which is not the sweep order).
+// (Round 9 had one routine per entry -- unpack, two-key compare, five selects, the quadratic -- 27 VALU instructions per entry,
+// 970 per wave; profiles/r10/README.md has the counts before and after.)
+template <int NTG, int NWV, int WV, int KM, class HRead>
+__device__ __forceinline__ void mfs_load(MfsAcc<NTG, NWV> &acc, const int n, const int2 *hadr, HRead hread, const signed char *kexp) {
   constexpr MfsTiles<NTG, NWV, WV> T;
   constexpr int TPW = MfsGrid<NTG, NWV>::TPW;
   const int ln = threadIdx.x & 63, g = ln >> 4, c = ln & 15;
   // Two rounds of LDS reads, each issued back to back: first what the lane's four rows per tile row and its one column per
-  // tile ARE (horizon step and component, or the reference-order index), then the entries themselves; the address
-  // arithmetic in between is branch-free.
-  int cinf[TPW], rinf[TPW][4];
+  // tile ARE (address words and scaling exponent), then the entries themselves.  A row or column >= n reads the words of
+  // variable n - 1 (any address inside the staging will do: its value is replaced by the padding below).
+  const int nm1 = n > 0 ? n - 1 : 0;
+  int2 cw[TPW], rw[TPW][4];
+  int kc[TPW], kr[TPW][4];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     const int j = 16 * T.j[t] + c;
-    cinf[t] = hinfo(j < n ? j : 0);
+    cw[t] = hadr[j < nm1 ? j : nm1];
+    kc[t] = (int)kexp[j];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (t == 0 || T.i[t] != T.i[t - 1]) {  // compile time
         const int i = 16 * T.i[t] + g + 4 * r;
-        rinf[t][r] = hinfo(i < n ? i : 0);
+        rw[t][r] = hadr[i < nm1 ? i : nm1];
+        kr[t][r] = (int)kexp[i];
       } else {
-        rinf[t][r] = rinf[t - 1][r];
+        rw[t][r] = rw[t - 1][r], kr[t][r] = kr[t - 1][r];
       }
     }
   }
   float hv[TPW][4];
 #pragma unroll
-  for (int t = 0; t < TPW; ++t)
+  for (int t = 0; t < TPW; ++t) {
+    const int ccp = cw[t].y & 0xffff, cs = (int)((unsigned)cw[t].y >> 24);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      hv[t][r] = hval(rinf[t][r], cinf[t]);  // (symmetric in its arguments: the lower half of a diagonal tile reads the mirror)
+      const int rm = (KM != 0) ? (int)((unsigned)rw[t][r].y >> 24) * KM : 0;  // (once per tile row: the tiles of a row share rw)
+      int off;
+      if (T.j[t] >= T.i[t] + 2) {  // compile time: the row comes first
+        off = rw[t][r].x + ccp;
+      } else {
+        const int rcp = rw[t][r].y & 0xffff;
+        off = ((unsigned)rw[t][r].y > (unsigned)cw[t].y) ? cw[t].x + rcp : rw[t][r].x + ccp;  // (the lower half of a diagonal tile reads the mirror)
+      }
+      if (KM != 0) off += rm * cs;
+      hv[t][r] = hread(off);
     }
-  // scaled while still binary32: two multiplications by powers of two (exact; |H| <= 1e3 and |k| <= 12 keep clear of the
-  // binary32 range on both sides), the row factors shared by the tiles of a tile row
-  float srow[4] = {1.f, 1.f, 1.f, 1.f};
+  }
+  // Identity padding replaces the value while it is binary32 (above the diagonal tiles a valid column implies a valid row; the
+  // exponents of padding rows and columns are 0), then ONE scaling by 2^(k_i + k_j) on the converted value: exact, the same bits
+  // as the two binary32 multiplications by 2^k_i and 2^k_j that it replaces
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
-    const int j = 16 * T.j[t] + c;
-    const float scol = __uint_as_float((unsigned)(127 + (int)kexp[j]) << 23);
+    const bool cv = 16 * T.j[t] + c < n;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = 16 * T.i[t] + g + 4 * r;
-      if (t == 0 || T.i[t] != T.i[t - 1]) srow[r] = __uint_as_float((unsigned)(127 + (int)kexp[i]) << 23);  // compile time
-      acc[t][r] = (i < n && j < n) ? (double)((hv[t][r] * srow[r]) * scol) : ((i == j) ? 1.0 : 0.0);  // identity padding
+      const bool dg = T.i[t] == T.j[t];  // compile time
+      const bool valid = dg ? (cv && 16 * T.i[t] + g + 4 * r < n) : cv;
+      const float pad = (dg && g + 4 * r == c) ? 1.0f : 0.0f;
+      acc[t][r] = ldexp((double)(valid ? hv[t][r] : pad), kr[t][r] + kc[t]);
     }
   }
 }
@@ -876,6 +902,19 @@ __device__ __forceinline__ void mfs_relayout(double *stage, MfsAcc<NTG, NWV> &ac
           int kr[GS], kc[GS];
 #pragma unroll
           for (int k = 0; k < GS; ++k) kr[k] = (int)kexp[GS * e0[s] + k], kc[k] = (int)kexp[GS * e1[s] + k];
+          if constexpr (BPT == 1) {
+            // One block per thread: the mirror of a diagonal block's entry (ii, jj), ii > jj, lies (ii - jj) (SST - 1) doubles before the entry
+            // itself -- five lane-constant bases, every entry at a compile-time offset from one of them -- and the scaling is undone
+            // by one ldexp with k_i + k_j (a multiplication by a power of two: the same bits as the product it replaces).
+            const int mir = dg ? SST - 1 : 0;
+#pragma unroll
+            for (int ii = 0; ii < GS; ++ii)
+#pragma unroll
+              for (int jj = 0; jj < GS; ++jj) {
+                const double *src = (ii > jj) ? rowp - (ii - jj) * mir : rowp;
+                a[s][ii][jj] = ldexp(src[ii * SST + jj], kr[ii] + kc[jj]);  // M = 2^k M~ 2^k (exact)
+              }
+          } else
 #pragma unroll
           for (int ii = 0; ii < GS; ++ii) {
 #pragma unroll
@@ -916,13 +955,19 @@ __device__ __forceinline__ void mfs_move_blocks(double (&dst)[BPT][GS][GS], cons
 // 128 threads -- 4 x 4 tiles on two waves -- was built and measured in round 4: one workgroup's stage 20 % shorter, the kernel
 // 1.4 % SLOWER with six workgroups per CU behind each other's 64-cycle matrix instructions; removed in round 5,
 // profiles/r04/mfma_sweep_experiments.txt keeps the numbers.)
-template <int NTG, int NWV, int WV, int NV, int NT, class HInfo, class HVal>
-__device__ __forceinline__ void mfma_sweeps(MfsPanel<NTG> &PN, double *stage, const int n, HInfo hinfo, HVal hval, signed char *kexp, const int e0,
+template <int NTG, int NWV, int WV, int NV, int NT, int KM, class HPart, class HRead>
+__device__ __forceinline__ void mfma_sweeps(MfsPanel<NTG> &PN, double *stage, const int n, HPart hpart, HRead hread, int2 *hadr, signed char *kexp, const int e0,
                                             const int e1, const bool live, double (&a)[1][GS][GS]) {
-  mfs_scale_exponents<NTG>(n, [&](const int i) __attribute__((always_inline)) { const int inf = hinfo(i); return hval(inf, inf); }, kexp);
+  // thread i < n: the address words of variable i for the loader (mfs_load), and H_ii through them
+  mfs_scale_exponents<NTG>(n, [&](const int i) __attribute__((always_inline)) {
+    const int2 w = hpart(i);
+    hadr[i] = w;
+    const int s = (int)((unsigned)w.y >> 24);
+    return hread(w.x + (w.y & 0xffff) + ((KM != 0) ? KM * s * s : 0));
+  }, kexp);
   __syncthreads();
   MfsAcc<NTG, NWV> acc;
-  mfs_load<NTG, NWV, WV>(acc, n, hinfo, hval, kexp);
+  mfs_load<NTG, NWV, WV, KM>(acc, n, hadr, hread, kexp);
   __syncthreads();  // every tile is loaded before the panel (which aliases the staging of H) is written
   mfs_steps<NTG, NWV, WV>(PN, acc, n);
   const int e0a[1] = {e0}, e1a[1] = {e1};
@@ -2011,21 +2056,25 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
   } else
   if constexpr (VT::MFMA_SWEEP) {
     // ---- matrix-core sweeps (mfma_sweeps above): tiles from the staging of H, 4 x 4 block pivots, M back in the 6 x 6 blocks
-    auto hinfo = [&](const int i) __attribute__((always_inline)) -> int {  // i < n, sweep order
-      if constexpr (SM::FULLBLK) return (int)S.sinfo[i];  // horizon step | component << 8
-      else return (int)S.s2o[i];                          // reference-order index
-    };
-    auto hval = [&](const int vi, const int vj) __attribute__((always_inline)) -> float {  // H(i, j) from hinfo(i), hinfo(j)
+    // where the staging keeps H(i, j), as a row part of whichever variable the staging orders first plus a column part of the other (mfs_load)
+    constexpr int KM = SM::FULLBLK ? 4 * U * U : 0;
+    static_assert(U <= 16 && sizeof(A.Hs) < 65536, "mfs_load: a step fits a tile; byte offsets into the staging fit 16 bits");
+    auto hpart = [&](const int i) __attribute__((always_inline)) -> int2 {  // i < n, sweep order
       if constexpr (SM::FULLBLK) {
         // staged: every U x U block (a <= b) of the unreduced matrix, block (a, a + d) at hs_off(d) + a; a same-step block holds
-        // its upper triangle in reference (component) order
-        const int si = vi & 255, sj = vj & 255, ri = vi >> 8, rj = vj >> 8;
-        const bool sw = (si > sj) || (si == sj && ri > rj);
-        const int sa = sw ? sj : si, sb = sw ? si : sj, r = sw ? rj : ri, c = sw ? ri : rj, d = sb - sa;
-        return A.Hs[(SM::hs_off(d, h) + sa) * (U * U) + r * U + c];
+        // its upper triangle in reference (component) order.  With d = b - a:  hs_off(d, h) + a = [a - a h - a (a + 1) / 2] + [b h - b (b - 1) / 2] + a b
+        const int inf = (int)S.sinfo[i], s = inf & 255, cc = inf >> 8;  // horizon step | component << 8
+        const int rp = (U * U) * (s - s * h - ((s * (s + 1)) >> 1)) + U * cc, cp = (U * U) * (s * h - ((s * (s - 1)) >> 1)) + cc;
+        return make_int2(4 * rp, (s << 24) | (cc << 16) | (4 * cp));
       } else {
-        return A.Hs[hs_index<NMAX>(vi < vj ? vi : vj, vi < vj ? vj : vi)];
+        // staged: the folded upper triangle in reference order (hs_index): H(v, w), v <= w, at [row v] + w
+        const int v = (int)S.s2o[i];
+        const int rp = (2 * v < NMAX) ? v * NMAX : (NMAX - 1 - v) * (NMAX + 1) + 1;
+        return make_int2(4 * rp, (v << 16) | (4 * v));
       }
+    };
+    auto hread = [&](const int off) __attribute__((always_inline)) -> float {
+      return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(A.Hs) + off);
     };
     constexpr int NTG1 = (NMAX + 15) / 16;
     // the pivot panels live in LDS that the solver does not use yet: the mat-vec staging
@@ -2036,10 +2085,10 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
     const bool live0 = bo.owner_r[0] && bo.e1_r[0] < ng;
     static_assert(NW == 4, "per-wave code of the matrix-core sweeps: four waves");
     switch (wv) {  // uniform: per-wave specialised code
-      case 0: mfma_sweeps<NTG1, 4, 0, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
-      case 1: mfma_sweeps<NTG1, 4, 1, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
-      case 2: mfma_sweeps<NTG1, 4, 2, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
-      default: mfma_sweeps<NTG1, 4, 3, NMAX, NT>(PN, stage, n, hinfo, hval, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
+      case 0: mfma_sweeps<NTG1, 4, 0, NMAX, NT, KM>(PN, stage, n, hpart, hread, S.hadr, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
+      case 1: mfma_sweeps<NTG1, 4, 1, NMAX, NT, KM>(PN, stage, n, hpart, hread, S.hadr, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
+      case 2: mfma_sweeps<NTG1, 4, 2, NMAX, NT, KM>(PN, stage, n, hpart, hread, S.hadr, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
+      default: mfma_sweeps<NTG1, 4, 3, NMAX, NT, KM>(PN, stage, n, hpart, hread, S.hadr, S.kexp, bo.e0_r[0], bo.e1_r[0], live0, a); break;
     }
   } else if constexpr (VT::MFMA_SWEEP3) {
     // ---- the same on the tiles filled in stage A5

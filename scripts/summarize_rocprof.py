@@ -51,15 +51,15 @@ def main():
         ctr = {}
         if "SQ_WAVE_CYCLES" in means:
             wc = means["SQ_WAVE_CYCLES"]
-            ctr = {
-                "sq_wait_any_frac_of_wave_cycles": means.get("SQ_WAIT_ANY", 0) / wc,
-                "sq_active_inst_any_frac_of_wave_cycles": means.get("SQ_ACTIVE_INST_ANY", 0) / wc,
-                "valu_insts_per_solve": means.get("SQ_INSTS_VALU", 0) / batch,
-                "salu_insts_per_solve": means.get("SQ_INSTS_SALU", 0) / batch,
-                "lds_insts_per_solve": means.get("SQ_INSTS_LDS", 0) / batch,
-                "mfma_insts_per_solve": means.get("SQ_INSTS_MFMA", 0) / batch,
-                "lds_bank_conflict_frac_of_lds_active": means.get("SQ_LDS_BANK_CONFLICT", 0) / max(1.0, means.get("SQ_LDS_IDX_ACTIVE", 1.0)),
-            }
+            # a key is written only when its pass is there: a counter that was not collected is absent, never 0
+            for key, cnt, den in (("sq_wait_any_frac_of_wave_cycles", "SQ_WAIT_ANY", wc),
+                                  ("sq_active_inst_any_frac_of_wave_cycles", "SQ_ACTIVE_INST_ANY", wc),
+                                  ("valu_insts_per_solve", "SQ_INSTS_VALU", batch), ("salu_insts_per_solve", "SQ_INSTS_SALU", batch),
+                                  ("lds_insts_per_solve", "SQ_INSTS_LDS", batch), ("mfma_insts_per_solve", "SQ_INSTS_MFMA", batch)):
+                if cnt in means:
+                    ctr[key] = means[cnt] / den
+            if "SQ_LDS_BANK_CONFLICT" in means and means.get("SQ_LDS_IDX_ACTIVE", 0) > 0:
+                ctr["lds_bank_conflict_frac_of_lds_active"] = means["SQ_LDS_BANK_CONFLICT"] / means["SQ_LDS_IDX_ACTIVE"]
             if "GRBM_GUI_ACTIVE" in means and "SQ_VALU_MFMA_BUSY_CYCLES" in means:
                 cyc = means["GRBM_GUI_ACTIVE"] / 8.0  # summed over the 8 XCDs
                 ctr["kernel_cycles_per_launch"] = cyc
@@ -214,12 +214,15 @@ def write_readme(dst, rnd, means, extra=()):
                      "%.0f B/solve with the gfx950 x2 FETCH correction, against 1200 B/solve algorithmic"
                      % (t["FETCH_SIZE_KB_per_launch"], t["WRITE_SIZE_KB_per_launch"], t["bytes_per_solve_raw"], t["bytes_per_solve"]))
         if c:
-            lines.append("* per solve: %.0f VALU / %.0f SALU / %.0f LDS / %.0f MFMA wave-instructions; SQ_WAIT_ANY %.1f %% and "
-                         "SQ_ACTIVE_INST_ANY %.1f %% of wave cycles; LDS bank conflicts %.1f %% of LDS-active cycles"
-                         % (c.get("valu_insts_per_solve", 0), c.get("salu_insts_per_solve", 0), c.get("lds_insts_per_solve", 0),
-                            c.get("mfma_insts_per_solve", 0), 100 * c.get("sq_wait_any_frac_of_wave_cycles", 0),
-                            100 * c.get("sq_active_inst_any_frac_of_wave_cycles", 0),
-                            100 * c.get("lds_bank_conflict_frac_of_lds_active", 0)))
+            def fmt(key, pattern, scale=1.0):  # a figure whose pass was not collected is left out of the line
+                return [pattern % (scale * c[key])] if key in c else []
+
+            per = (fmt("valu_insts_per_solve", "%.0f VALU") + fmt("salu_insts_per_solve", "%.0f SALU") +
+                   fmt("lds_insts_per_solve", "%.0f LDS") + fmt("mfma_insts_per_solve", "%.0f MFMA"))
+            rest = (fmt("sq_wait_any_frac_of_wave_cycles", "SQ_WAIT_ANY %.1f %% of wave cycles", 100) +
+                    fmt("sq_active_inst_any_frac_of_wave_cycles", "SQ_ACTIVE_INST_ANY %.1f %% of wave cycles", 100) +
+                    fmt("lds_bank_conflict_frac_of_lds_active", "LDS bank conflicts %.1f %% of LDS-active cycles", 100))
+            lines.append("* per solve: " + "; ".join(([" / ".join(per) + " wave-instructions"] if per else []) + rest))
             if "valu_issue_frac" in c:
                 lines.append("* kernel %.0f cycles per launch; VALU issue occupancy (4 cycles per wave instruction / SIMD cycles) "
                              "%.1f %%; matrix pipe busy %.2f %%" % (c["kernel_cycles_per_launch"], 100 * c["valu_issue_frac"],
