@@ -28,6 +28,7 @@ EXPORTS = [
     "hmpc_solve_command_sweep", "hmpc_set_instance_mu", "hmpc_group_solve_command_sweep", "hmpc_debug_handover_slots",
     "hmpc_predict_states", "hmpc_set_device_prediction", "hmpc_get_device_prediction", "hmpc_download_prediction",
     "hmpc_legacy_predicted_state",
+    "hmpc_sweep_select", "hmpc_set_device_selection", "hmpc_get_device_selection", "hmpc_download_selection", "hmpc_tick_sweep_device",
 ]
 
 
@@ -49,6 +50,11 @@ class TickInputs(C.Structure):
                 ("yaw_rate_des", C.c_double), ("roll_des", C.c_double), ("pitch_des", C.c_double),
                 ("world_position_desired", C.c_double * 2), ("gait_offsets", C.c_int * 2),
                 ("gait_durations", C.c_int * 2), ("gait_iteration", C.c_int), ("flags", C.c_int)]
+
+
+class Command(C.Structure):
+    """include/hector_mpc.h struct hmpc_command (one candidate command of hmpc_tick_sweep_device)."""
+    _fields_ = [("v_des_robot", C.c_double * 2), ("yaw_rate_des", C.c_double), ("roll_des", C.c_double), ("pitch_des", C.c_double)]
 
 
 class UpdateData(C.Structure):
@@ -181,6 +187,11 @@ def load():
     L.hmpc_download_prediction.argtypes = [vp, vp, vp]
     L.hmpc_legacy_predicted_state.argtypes = [ci, ci]
     L.hmpc_legacy_predicted_state.restype = cd
+    L.hmpc_sweep_select.argtypes = [vp, ci, vp, vp]
+    L.hmpc_set_device_selection.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hmpc_get_device_selection.argtypes = [vp] + [C.POINTER(vp)] * 5 + [C.POINTER(ci)]
+    L.hmpc_download_selection.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hmpc_tick_sweep_device.argtypes = [vp, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

@@ -1,7 +1,7 @@
 """In-tree build of libhector_mpc_hip.so (hipcc, gfx950 only; cross-compiles without a GPU).
 
 The kernel family is compiled as HMPC_VARIANT_GROUPS translation units side by side (csrc/hmpc_variants.hip with
--DHMPC_VARIANT_GROUP=k) next to the two host-side ones and the prediction kernel (csrc/hmpc_predict.hip), then linked: ~25 s instead of the 60 s of one serial unit.
+-DHMPC_VARIANT_GROUP=k) next to the two host-side ones, the prediction kernel (csrc/hmpc_predict.hip) and the selection kernels (csrc/hmpc_select.hip), then linked: ~25 s instead of the 60 s of one serial unit.
 Staleness is decided by a content hash of the sources (kept next to the library), not by mtimes -- a snapshot copied to
 another box keeps the prebuilt library valid -- and builds are serialised by a file lock so that N ranks started by
 torchrun never compile into the same file at once."""
@@ -19,9 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhector_mpc_hip.so")
 VARIANT_GROUPS = 4  # = HMPC_VARIANT_GROUPS of csrc/hmpc_variants.h
-HOST_SOURCES = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_predict.hip"]  # (hmpc_predict.hip: the prediction kernel, a unit of its own)
+HOST_SOURCES = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_predict.hip", "hmpc_select.hip"]  # (hmpc_predict.hip, hmpc_select.hip: the prediction and selection kernels, units of their own)
 DEPS = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_variants.hip", "hmpc_variants.h", "hmpc_kernel_args.h", "hmpc_kernel.h",
-        "hmpc_math.h", "hmpc_builder.h", "hmpc_predict.hip", "hmpc_predict.h", os.path.join("..", "..", "include", "hector_mpc.h")]
+        "hmpc_math.h", "hmpc_builder.h", "hmpc_predict.hip", "hmpc_predict.h", "hmpc_select.hip", "hmpc_select.h", os.path.join("..", "..", "include", "hector_mpc.h")]
 # -ffp-contract=off is part of the numerical contract (HMPC-A1): every fused multiply-add in the source is explicit
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"]
 EXTRA = os.environ.get("HMPC_EXTRA_FLAGS", "").split()  # developer A/B switches, e.g. -DHMPC_MFMA_SWEEP=0 (same results, other code)

@@ -20,6 +20,7 @@
 #include "hmpc_variants.h"
 #include "hmpc_builder.h"
 #include "hmpc_predict.h"
+#include "hmpc_select.h"
 
 namespace {
 
@@ -145,6 +146,15 @@ struct hmpc_handle {
   double *d_pred_cost_own, *d_pred_cost;
   bool solve_enqueued;    // a solve of the CURRENT batch has been enqueued (cleared by everything that replaces the batch)
   bool predict_enqueued;  // ... and a prediction behind it (cleared by every later solve as well: its forces are newer)
+  // selection (hmpc_sweep_select): one row per sweep group; the handle's own buffers are allocated for max_batch groups by the first call
+  // that needs them, d_sel_* = where the next selection goes (the caller's, hmpc_set_device_selection, or nullptr = the handle's own)
+  int32_t *d_sel_index_own, *d_sel_index;
+  double *d_sel_score_own, *d_sel_score;
+  float *d_sel_forces_own, *d_sel_forces;
+  uint32_t *d_sel_status_own, *d_sel_status;
+  float *d_sel_states_own, *d_sel_states;
+  bool select_enqueued;  // ... and a selection behind that prediction (cleared wherever predict_enqueued is, and by every prediction)
+  int select_groups;     // groups of that selection
   double *d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
   size_t sweep_m_bytes;
 };
@@ -386,7 +396,7 @@ static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes
     const int rc = launch(h, stream, l[k].vi, o);
     if (rc != HMPC_OK) return rc;
   }
-  h->solve_enqueued = true, h->predict_enqueued = false;  // (every solve of a batch starts here: hmpc_predict_states)
+  h->solve_enqueued = true, h->predict_enqueued = h->select_enqueued = false;  // (every solve of a batch starts here: hmpc_predict_states)
   return HMPC_OK;
 }
 
@@ -655,6 +665,11 @@ int hmpc_destroy(hmpc_handle *h) {
   if (h->d_spill_slot) hipFree(h->d_spill_slot);
   if (h->d_pred_states_own) hipFree(h->d_pred_states_own);
   if (h->d_pred_cost_own) hipFree(h->d_pred_cost_own);
+  if (h->d_sel_index_own) hipFree(h->d_sel_index_own);
+  if (h->d_sel_score_own) hipFree(h->d_sel_score_own);
+  if (h->d_sel_forces_own) hipFree(h->d_sel_forces_own);
+  if (h->d_sel_status_own) hipFree(h->d_sel_status_own);
+  if (h->d_sel_states_own) hipFree(h->d_sel_states_own);
   delete h;
   return HMPC_OK;
 }
@@ -675,7 +690,7 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
     HIP_TRY(hipMemcpy(h->d_records_own, host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice));
   h->d_records = h->d_records_own;
   h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = false;
+  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
   h->cls_valid = 0;
   // host-side scan of the gait tables: the widest reduced QP in the batch picks the kernel variant (LDS footprint)
   const int hz = h->setup.horizon;
@@ -726,7 +741,7 @@ int hmpc_set_device_records(hmpc_handle *h, const void *device_records, int batc
   if (batch > h->max_batch) return HMPC_E_BATCH;
   h->d_records = (const unsigned char *)device_records;
   h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = false;
+  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
   h->max_stance = -1;  // unknown: hmpc_solve counts the size classes on the device (or hmpc_set_max_reduced_vars tells)
   h->cls_valid = 0;
   return HMPC_OK;
@@ -1205,7 +1220,7 @@ int hmpc_build_records_device(hmpc_handle *h, const void *device_ticks, int batc
   }
   h->d_records = h->d_records_own;
   h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = false;
+  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
   h->max_stance = -1;  // the builder left every instance's size class on the device: hmpc_solve routes by it
   h->cls_valid = 1;
   h->last_stream = (hipStream_t)stream;
@@ -1380,7 +1395,7 @@ static int prediction_buffers(hmpc_handle *h, float **states, double **cost) {
 int hmpc_set_device_prediction(hmpc_handle *h, float *device_states, double *device_cost) {
   if (!h) return HMPC_E_ARG;
   h->d_pred_states = device_states, h->d_pred_cost = device_cost;
-  h->predict_enqueued = false;  // (whatever was predicted went elsewhere)
+  h->predict_enqueued = h->select_enqueued = false;  // (whatever was predicted went elsewhere)
   return HMPC_OK;
 }
 
@@ -1410,7 +1425,7 @@ int hmpc_predict_states(hmpc_handle *h, void *stream) {
   a.mu_inst = nullptr;  // (friction shapes the constraint block only; the model does not depend on it)
   h->last_stream = (hipStream_t)stream;
   HIP_TRY(hmpc::launch_predict(h->nc, a, s, c, (hipStream_t)stream));
-  h->predict_enqueued = true;
+  h->predict_enqueued = true, h->select_enqueued = false;  // (a selection made before this prediction read an older one)
   return HMPC_OK;
 }
 
@@ -1426,6 +1441,128 @@ int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost) {
   if (rc != HMPC_OK) return rc;
   if (states) HIP_TRY(hipMemcpy(states, s, (size_t)h->batch * h->setup.horizon * 13 * sizeof(float), hipMemcpyDeviceToHost));
   if (cost) HIP_TRY(hipMemcpy(cost, c, (size_t)h->batch * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
+// ------------------------------------------------------------------------------------------------------------------
+struct SelectionBuffers {
+  int32_t *index;
+  double *score;
+  float *forces;
+  uint32_t *status;
+  float *states;
+};
+
+// where the next selection goes: the caller's buffers, else the handle's own (allocated here, for max_batch groups, on first need)
+static int selection_buffers(hmpc_handle *h, SelectionBuffers *b) {
+  const size_t mb = (size_t)h->max_batch, hz = (size_t)h->setup.horizon;
+  if (!h->d_sel_index && !h->d_sel_index_own) HIP_TRY(hipMalloc(&h->d_sel_index_own, mb * sizeof(int32_t)));
+  if (!h->d_sel_score && !h->d_sel_score_own) HIP_TRY(hipMalloc(&h->d_sel_score_own, mb * sizeof(double)));
+  if (!h->d_sel_forces && !h->d_sel_forces_own) HIP_TRY(hipMalloc(&h->d_sel_forces_own, mb * 6 * h->nc * hz * sizeof(float)));
+  if (!h->d_sel_status && !h->d_sel_status_own) HIP_TRY(hipMalloc(&h->d_sel_status_own, mb * sizeof(uint32_t)));
+  if (!h->d_sel_states && !h->d_sel_states_own) HIP_TRY(hipMalloc(&h->d_sel_states_own, mb * hz * 13 * sizeof(float)));
+  b->index = h->d_sel_index ? h->d_sel_index : h->d_sel_index_own;
+  b->score = h->d_sel_score ? h->d_sel_score : h->d_sel_score_own;
+  b->forces = h->d_sel_forces ? h->d_sel_forces : h->d_sel_forces_own;
+  b->status = h->d_sel_status ? h->d_sel_status : h->d_sel_status_own;
+  b->states = h->d_sel_states ? h->d_sel_states : h->d_sel_states_own;
+  return HMPC_OK;
+}
+
+int hmpc_set_device_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states) {
+  if (!h) return HMPC_E_ARG;
+  h->d_sel_index = index, h->d_sel_score = score, h->d_sel_forces = forces, h->d_sel_status = status, h->d_sel_states = states;
+  h->select_enqueued = false;  // (whatever was selected went elsewhere)
+  return HMPC_OK;
+}
+
+int hmpc_get_device_selection(hmpc_handle *h, int32_t **index, double **score, float **forces, uint32_t **status, float **states,
+                              int *n_groups) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  SelectionBuffers b;
+  const int rc = selection_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (index) *index = b.index;
+  if (score) *score = b.score;
+  if (forces) *forces = b.forces;
+  if (status) *status = b.status;
+  if (states) *states = b.states;
+  if (n_groups) *n_groups = h->select_enqueued ? h->select_groups : 0;
+  return HMPC_OK;
+}
+
+int hmpc_sweep_select(hmpc_handle *h, int group_size, const double *device_penalty, void *stream) {
+  if (!h || group_size < 1) return HMPC_E_ARG;
+  if (h->batch % group_size != 0) return HMPC_E_ARG;
+  if (!h->predict_enqueued) return HMPC_E_ARG;  // no prediction from the last solve of this batch: the cost buffer holds another solve's, or none
+  HIP_TRY(hipSetDevice(h->device));
+  float *ps = nullptr;
+  double *pc = nullptr;
+  int rc = prediction_buffers(h, &ps, &pc);
+  if (rc != HMPC_OK) return rc;
+  SelectionBuffers b;
+  rc = selection_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::SelectArgs a;
+  a.cost = pc, a.states = ps, a.status = h->d_status, a.forces = h->d_forces, a.penalty = device_penalty;
+  a.groups = h->batch / group_size, a.group_size = group_size;
+  a.force_words = 6 * h->nc * h->setup.horizon, a.state_words = 13 * h->setup.horizon;
+  a.index = b.index, a.score = b.score, a.out_forces = b.forces, a.out_status = b.status, a.out_states = b.states;
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_select(a, (hipStream_t)stream));
+  h->select_enqueued = true, h->select_groups = a.groups;
+  return HMPC_OK;
+}
+
+int hmpc_download_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states) {
+  if (!h || !h->select_enqueued) return HMPC_E_ARG;  // nothing selected from the last prediction
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  SelectionBuffers b;
+  const int rc = selection_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t g = (size_t)h->select_groups, hz = (size_t)h->setup.horizon;
+  if (index) HIP_TRY(hipMemcpy(index, b.index, g * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (score) HIP_TRY(hipMemcpy(score, b.score, g * sizeof(double), hipMemcpyDeviceToHost));
+  if (forces) HIP_TRY(hipMemcpy(forces, b.forces, g * 6 * h->nc * hz * sizeof(float), hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemcpy(status, b.status, g * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (states) HIP_TRY(hipMemcpy(states, b.states, g * hz * 13 * sizeof(float), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// One planning tick without leaving the device: n_ticks robot states x group_size candidate commands -> records -> sweep solve ->
+// prediction -> selection -> the joint torques of every state's best command.  Every stage is the entry point of its own name; new here
+// are the expansion of ticks x commands (hmpc_select.hip) and the torque launch over the compact winner rows.
+int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks, const struct hmpc_command *device_commands,
+                           int group_size, double dtMPC, const double *device_penalty, double *device_wpd_out, double *device_f_ff,
+                           double *device_tau, void *stream) {
+  if (!h || !device_ticks || !device_commands || !device_tau || n_ticks < 0 || group_size < 1) return HMPC_E_ARG;
+  if (h->nc != 2 || h->setup.horizon > 10) return HMPC_E_ARG;  // (the sweep's limits)
+  if ((long long)n_ticks * group_size > h->max_batch) return HMPC_E_BATCH;
+  const int batch = n_ticks * group_size;
+  if (batch == 0) return hmpc_build_records_device(h, device_ticks, 0, dtMPC, nullptr, stream);
+  HIP_TRY(hipSetDevice(h->device));
+  void *sp = nullptr;
+  int rc = scratch(h, sizeof(hmpc_tick_inputs) * (size_t)batch, &sp);
+  if (rc != HMPC_OK) return rc;
+  HIP_TRY(hmpc::launch_expand_ticks((const hmpc_tick_inputs *)device_ticks, n_ticks, device_commands, group_size, (hmpc_tick_inputs *)sp,
+                                    device_wpd_out, (hipStream_t)stream));
+  rc = hmpc_build_records_device(h, sp, batch, dtMPC, nullptr, stream);
+  if (rc == HMPC_OK) rc = hmpc_solve_command_sweep(h, group_size, stream);
+  if (rc == HMPC_OK) rc = hmpc_predict_states(h, stream);
+  if (rc == HMPC_OK) rc = hmpc_sweep_select(h, group_size, device_penalty, stream);
+  if (rc != HMPC_OK) return rc;
+  SelectionBuffers b;
+  rc = selection_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const int total = 2 * n_ticks;
+  hipLaunchKernelGGL(hmpc::leg_torque_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, b.forces, n_ticks,
+                     h->setup.horizon, (const double *)nullptr, (const double *)nullptr, device_f_ff, device_tau,
+                     (const hmpc_tick_inputs *)device_ticks);
+  HIP_TRY(hipGetLastError());
   return HMPC_OK;
 }
 

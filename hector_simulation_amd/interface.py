@@ -18,6 +18,10 @@ TICK_DTYPE = np.dtype([("position", "f8", 3), ("vWorld", "f8", 3), ("omegaWorld"
                        ("world_position_desired", "f8", 2), ("gait_offsets", "i4", 2), ("gait_durations", "i4", 2),
                        ("gait_iteration", "i4"), ("flags", "i4")], align=True)
 
+# struct hmpc_command: the five command fields of a tick, in their order (hmpc_tick_sweep_device)
+COMMAND_DTYPE = np.dtype([("v_des_robot", "f8", 2), ("yaw_rate_des", "f8"), ("roll_des", "f8"), ("pitch_des", "f8")], align=True)
+SELECT_NONE = 0xFFFFFFFF  # HMPC_SELECT_NONE: the status word of a group without a winner
+
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "too_large", 4: "kkt", 5: "working_set_full", 6: "ok_relaxed", 7: "sweep_mismatch", 8: "hessian_not_positive_definite", 9: "regularisation_step"}
 
 
@@ -249,6 +253,43 @@ class BatchedMPC:
         self._keep_pred = keepalive
         _check(self.L.hmpc_set_device_prediction(self.h, C.c_void_p(int(states_ptr or 0)), C.c_void_p(int(cost_ptr or 0))),
                "hmpc_set_device_prediction")
+
+    def sweep_select(self, group_size: int, penalty_ptr: int = 0, stream: int = 0) -> None:
+        """One launch behind the prediction on ``stream``: the eligible instance of smallest (cost[0] + cost[1]) + penalty in every group of
+        ``group_size`` consecutive instances (include/hector_mpc.h hmpc_sweep_select).  ``penalty_ptr``: float64[batch] in HBM, 0 = none.
+        Raises when no prediction has been enqueued since the last solve of the current batch."""
+        _check(self.L.hmpc_sweep_select(self.h, int(group_size), C.c_void_p(int(penalty_ptr or 0)), C.c_void_p(stream)), "hmpc_sweep_select")
+
+    def download_selection(self) -> dict:
+        """The last selection, one row per group: index int32[G] (-1 = no winner), score float64[G] (+inf), forces float32[G, nvar] and
+        states float32[G, horizon, 13] (bit copies of the winner's rows, or zeros), status uint32[G] (``SELECT_NONE``).  Waits; runs no
+        safe pass."""
+        g = C.c_int(0)
+        _check(self.L.hmpc_get_device_selection(self.h, None, None, None, None, None, C.byref(g)), "hmpc_get_device_selection")
+        n = int(g.value)
+        out = dict(index=np.zeros(n, dtype=np.int32), score=np.zeros(n, dtype=np.float64), forces=np.zeros((n, self.nvar), dtype=np.float32),
+                   status=np.zeros(n, dtype=np.uint32), states=np.zeros((n, self.horizon, 13), dtype=np.float32))
+        _check(self.L.hmpc_download_selection(self.h, *[out[k].ctypes.data for k in ("index", "score", "forces", "status", "states")]),
+               "hmpc_download_selection")
+        return out
+
+    def set_device_selection(self, index_ptr: int = 0, score_ptr: int = 0, forces_ptr: int = 0, status_ptr: int = 0, states_ptr: int = 0,
+                             keepalive=None) -> None:
+        """Caller-owned device buffers for later selections, one row per group (int32[G], float64[G], float32[G, nvar], uint32[G],
+        float32[G, horizon, 13]; 0 / None = the handle's own)."""
+        self._keep_sel = keepalive
+        _check(self.L.hmpc_set_device_selection(self.h, *[C.c_void_p(int(p or 0)) for p in (index_ptr, score_ptr, forces_ptr, status_ptr,
+                                                                                             states_ptr)]), "hmpc_set_device_selection")
+
+    def tick_sweep_device(self, ticks_ptr: int, n_ticks: int, commands_ptr: int, group_size: int, dt_mpc: float, tau_ptr: int,
+                          f_ff_ptr: int = 0, wpd_ptr: int = 0, penalty_ptr: int = 0, stream: int = 0) -> None:
+        """Ticks (``TICK_DTYPE[n_ticks]``) and candidate commands (``COMMAND_DTYPE[n_ticks, group_size]``) in HBM in, the best command's
+        torques in HBM out: records, sweep solve, prediction, selection and torques on one stream (include/hector_mpc.h
+        hmpc_tick_sweep_device).  Which command won: ``download_selection()``."""
+        _check(self.L.hmpc_tick_sweep_device(self.h, C.c_void_p(ticks_ptr), int(n_ticks), C.c_void_p(commands_ptr), int(group_size),
+                                             float(dt_mpc), C.c_void_p(int(penalty_ptr or 0)), C.c_void_p(int(wpd_ptr or 0)),
+                                             C.c_void_p(int(f_ff_ptr or 0)), C.c_void_p(tau_ptr), C.c_void_p(stream)),
+               "hmpc_tick_sweep_device")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

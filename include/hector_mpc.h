@@ -410,6 +410,66 @@ int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost);
  * `step` (0..horizon-1: x_{step+1}) under the last solution.  Predicts lazily, once per solve, on first use (one launch, one
  * copy).  0 before the first solve and for out-of-range arguments, as get_solution. */
 double hmpc_legacy_predicted_state(int step, int component);
+/* ---- the best command of every sweep group, picked on the device ----
+ * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
+ * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size
+ * CONSECUTIVE instances.  For instance i of group g, with U = 6 * contacts:
+ *   score_i = (cost[i][0] + cost[i][1]) + device_penalty[i]     two plain binary64 additions in that order; cost = the handle's current
+ *                                                               prediction; device_penalty = double[batch] in HBM, caller-owned: the
+ *                                                               caller's own term (e.g. the distance of a command from the operator's);
+ *                                                               NULL = only the first addition is made
+ *   eligible  <=>  the status code is HMPC_S_OK or HMPC_S_OK_RELAXED, and score_i is finite (a NaN or +-inf penalty masks a command)
+ *   winner     =   the eligible instance of smallest score; equal scores (==, so -0 equals +0) are broken by the lowest index
+ * Outputs per group:
+ *   index[g]            the winner's position in its group, 0 .. group_size-1, or -1 when the group has no winner
+ *   score[g]            the winner's score, or +inf
+ *   forces[g][U h]      a bit copy of the winner's slot of the force buffer, or +0
+ *   status[g]           the winner's status word, or HMPC_SELECT_NONE
+ *   states[g][h][13]    a bit copy of the winner's predicted states, or +0
+ * The result is a pure function of cost, states, status, forces, penalty and group_size: it does not depend on the workgroup size or
+ * on the order of the reduction (a lexicographic (score, index) minimum over the eligible instances; ineligible ones never enter a
+ * comparison).
+ *
+ * hmpc_sweep_select enqueues ONE launch on `stream` (a kernel of its own, one workgroup per group) and synchronises nothing.  Forces
+ * and status are read where the solve wrote them (hmpc_set_device_outputs is honoured), the prediction where the last prediction went.
+ * Any contact count and any horizon; it may follow hmpc_solve as well as a sweep (it only groups consecutive instances).  HMPC_E_ARG,
+ * nothing enqueued: group_size < 1, batch % group_size != 0, or no prediction enqueued since the last solve of the current batch (the
+ * rule of hmpc_download_prediction: a later solve, a new batch or hmpc_set_device_prediction each ask for a new prediction, and every
+ * new prediction for a new selection).
+ * hmpc_set_device_selection: caller-owned device buffers for later selections, each for as many groups as will be selected (any may
+ * be NULL = the handle's own, allocated for max_batch groups by the first call that needs them; never inside hmpc_solve).
+ * hmpc_get_device_selection: where the next selection goes, and *n_groups = the groups of the last selection (0 when nothing has been
+ * selected since the last prediction); any pointer may be NULL.  hmpc_download_selection waits for the stream of the last call, then
+ * copies (any pointer may be NULL); HMPC_E_ARG when nothing has been selected since the last prediction.  It does NOT run the safe pass.
+ * Device groups: per member, through hmpc_group_member (a sweep group never spans two members: hmpc_group_solve_command_sweep). */
+#define HMPC_SELECT_NONE 0xffffffffu
+int hmpc_sweep_select(hmpc_handle *h, int group_size, const double *device_penalty, void *stream);
+int hmpc_set_device_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states);
+int hmpc_get_device_selection(hmpc_handle *h, int32_t **index, double **score, float **forces, uint32_t **status, float **states,
+                              int *n_groups);
+int hmpc_download_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states);
+/* One candidate command: the five command fields of hmpc_tick_inputs, in their order. */
+struct hmpc_command {
+  double v_des_robot[2];
+  double yaw_rate_des;
+  double roll_des, pitch_des;
+};
+/* Ticks and candidate commands in HBM in, the best command's torques in HBM out -- hmpc_tick_solve_device for ONE robot state under K
+ * commands.  device_ticks: hmpc_tick_inputs[n_ticks]; device_commands: hmpc_command[n_ticks][group_size].  Instance g K + k of the new
+ * current batch (n_ticks * group_size instances) is built from ticks[g] with its five command fields replaced by commands[g][k],
+ * everything else copied: its record is bit for bit what hmpc_build_records_device builds from ticks expanded that way by the caller.
+ * Launches on the one stream, no host synchronisation: the expansion (into scratch of the handle) and the record builder; the sweep
+ * solve exactly as hmpc_solve_command_sweep enqueues it (per-class routing, and the device-side repair chain when
+ * hmpc_set_device_repair is on); the prediction; the selection with device_penalty[n_ticks * group_size] (or NULL); and the joint
+ * torques of hmpc_tick_solve_device over the n_ticks winner force rows, rBody and the joint angles read from device_ticks.
+ * Outputs: f_ff[n_ticks][2][6] (may be NULL), tau[n_ticks][2][5], device_wpd_out[n_ticks][2] (may be NULL): the clamped
+ * world_position_desired of each tick, the value hmpc_build_records returns for it (it does not depend on the command).  Which command
+ * won, its score, forces, status word and predicted states: hmpc_get_device_selection / hmpc_download_selection.  A tick with no
+ * eligible command gets index -1, and f_ff and tau computed from zero forces.
+ * HMPC_E_ARG for a three-contact handle or a horizon above 10 (the sweep's limits); HMPC_E_BATCH when n_ticks * group_size > max_batch. */
+int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks, const struct hmpc_command *device_commands,
+                           int group_size, double dtMPC, const double *device_penalty, double *device_wpd_out, double *device_f_ff,
+                           double *device_tau, void *stream);
 /* copies the current batch's packed records device -> host (parity hook for f1/f2) */
 int hmpc_download_records(hmpc_handle *h, void *host_records);
 

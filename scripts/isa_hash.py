@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Per-kernel hash of the gfx950 machine code of every kernel variant (hipcc cross-compiles: no GPU needed).
 
-    python scripts/isa_hash.py [--out FILE] [--group 0..3 ...] [extra hipcc flags]
+    python scripts/isa_hash.py [--out FILE] [--group 0..3 ...] [--unit FILE.hip ...] [extra hipcc flags]
     python scripts/isa_hash.py --diff profiles/r06/isa_hash_before.txt      # exit code 1 when any kernel's code changed
 
 What a refactor of hmpc_kernel.h that must not change the product (macro removal, a stage moved into a function) is checked
 with: the kernel's instructions as llvm-objdump prints them (addresses and symbol-relative branch targets stripped), hashed
 per kernel symbol.  Two builds with the same hash run the same instructions.  --diff pairs kernels across a rename: an old
 row whose name is gone is matched to a new kernel with the same hash and instruction count; only what stays unmatched is
-CHANGED / NEW / MISSING."""
+CHANGED / NEW / MISSING.  --unit adds the kernels of another translation unit of csrc/ (hmpc_predict.hip, hmpc_select.hip,
+the builder kernels inside hmpc_capi.hip) to the listing."""
 import concurrent.futures
 import hashlib
 import os
@@ -24,16 +25,19 @@ from hector_simulation_amd import build as hip_build  # noqa: E402
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def kernel_hashes(groups=None, extra=()):
+def kernel_hashes(groups=None, extra=(), units=()):
     groups = list(range(hip_build.VARIANT_GROUPS)) if not groups else groups
+    groups = groups + list(units)  # (a unit of its own is compiled like a group, without the group's define)
     out = {}
     with tempfile.TemporaryDirectory(prefix="hmpc_isa_") as td:
         def one(g):
             co = os.path.join(td, f"g{g}.bundle")
             elf = os.path.join(td, f"g{g}.elf")
+            unit = isinstance(g, str)
+            src = os.path.join(hip_build.CSRC, g if unit else "hmpc_variants.hip")
             subprocess.check_call(["/opt/rocm/bin/hipcc"] + hip_build.CFLAGS + list(extra) +
-                                  [f"-DHMPC_VARIANT_GROUP={g}", "--cuda-device-only", "-c",
-                                   os.path.join(hip_build.CSRC, "hmpc_variants.hip"), "-o", co], stderr=subprocess.DEVNULL)
+                                  ([] if unit else [f"-DHMPC_VARIANT_GROUP={g}"]) + ["--cuda-device-only", "-c", src, "-o", co],
+                                  stderr=subprocess.DEVNULL)
             subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={co}",
                                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={elf}"])
             dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", elf],
@@ -69,7 +73,7 @@ def kernel_hashes(groups=None, extra=()):
 def main():
     args = sys.argv[1:]
     out_path = diff_path = None
-    groups, extra = [], []
+    groups, extra, units = [], [], []
     i = 0
     while i < len(args):
         if args[i] == "--out":
@@ -78,9 +82,11 @@ def main():
             diff_path = args[i + 1]; i += 2
         elif args[i] == "--group":
             groups.append(int(args[i + 1])); i += 2
+        elif args[i] == "--unit":
+            units.append(args[i + 1]); i += 2
         else:
             extra.append(args[i]); i += 1
-    hs = kernel_hashes(groups, extra)
+    hs = kernel_hashes(groups, extra, units)
     lines = [f"{h} {n:7d} {k}" for k, (h, n) in sorted(hs.items())]
     text = "\n".join(lines) + "\n"
     if out_path:
@@ -101,7 +107,7 @@ def main():
                 print("RENAMED", gone[0], "->", k)
                 old[k] = old.pop(gone[0])
         changed = [k for k, (h, _) in hs.items() if k in old and old[k][0] != h]
-        missing = [k for k in old if k not in hs and not groups]
+        missing = [k for k in old if k not in hs and not groups and (units or "hmpc_kernel<" in k)]
         new = [k for k in hs if k not in old]
         for k in changed:
             print("CHANGED", k)
