@@ -13,9 +13,11 @@
 
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/hector_mpc.h"
+#include "hmpc_device_buffer.h"
 #include "hmpc_kernel_args.h"
 #include "hmpc_variants.h"
 #include "hmpc_builder.h"
@@ -78,85 +80,81 @@ size_t record_stride(int h, int nc = 2) { return (size_t)(((fixed_floats(nc) + 1
 
 }  // namespace
 
-struct hmpc_handle {
-  problem_setup setup;
-  int nc;  // contacts per horizon step: 2 (reference) or 3 (hand-contact extension)
-  int max_batch, device, batch;
-  size_t stride;
-  unsigned char *d_records_own;
-  const unsigned char *d_records;
-  float *d_forces_own, *d_forces;
-  uint32_t *d_status_own, *d_status;
-  double *d_x64, *d_obj64;
-  float *d_dbg_f;
-  int *d_dbg_i;
-  long long *d_prof;
-  int warm;        // block warm start of the working set (default on)
-  signed char *d_wset;  // working sets carried from tick to tick (hmpc_set_tick_warm_start), [max_batch][8 nc h]
-  int tick_warm, tick_shift;
-  int auto_resolve;  // hmpc_download re-solves flagged instances with the safe variant (default on)
-  int max_stance;  // max reduced variables of the current batch (known only for host-uploaded records; else -1)
-  hipStream_t last_stream;
-  bool attrs_set[N_VARIANTS];
-  // persistent device scratch for the host-pointer convenience entry points (grown on demand, freed in hmpc_destroy):
-  // no hipMalloc/hipFree per call and nothing to leak on an early error return
-  void *d_scratch;
-  size_t scratch_bytes;
+struct __attribute__((visibility("hidden"))) hmpc_handle {  // (opaque to callers: its constructor and destructor are not exported)
+  problem_setup setup{};
+  int nc = 2;  // contacts per horizon step: 2 (reference) or 3 (hand-contact extension)
+  int max_batch = 0, device = 0, batch = 0;
+  size_t stride = 0;
+  DeviceBuffer<unsigned char> d_record_store;    // the handle's own records (uploads, the record builder)
+  const unsigned char *d_records = nullptr;      // the current batch's: d_record_store, or the caller's (hmpc_set_device_records)
+  OutputBuffer<float> d_forces;                  // the caller's, hmpc_set_device_outputs, else the handle's own (allocated at create)
+  OutputBuffer<uint32_t> d_status;
+  DeviceBuffer<double> d_x64, d_obj64;
+  DeviceBuffer<float> d_dbg_f;
+  DeviceBuffer<int> d_dbg_i;
+  DeviceBuffer<long long> d_prof;
+  int warm = 1;    // block warm start of the working set (default on)
+  DeviceBuffer<signed char> d_wset;  // working sets carried from tick to tick (hmpc_set_tick_warm_start), [max_batch][8 nc h]
+  int tick_warm = 0, tick_shift = 0;
+  int auto_resolve = 1;  // hmpc_download re-solves flagged instances with the safe variant (default on)
+  int max_stance = -1;  // max reduced variables of the current batch (known only for host-uploaded records; else -1)
+  hipStream_t last_stream = nullptr;
+  bool attrs_set[N_VARIANTS] = {};
+  // persistent device scratch for the host-pointer convenience entry points (grown on demand): no allocation per call and nothing to
+  // leak on an early error return
+  DeviceBuffer<unsigned char> d_scratch;
   // number of instances the solve kernels have flagged (working set full / max-iter / infeasible / KKT) since the handle
   // was created; monotonically increasing device counter, hmpc_download compares it with the value it saw last and
   // skips the status scan of the safe pass when nothing new was flagged
-  unsigned int *d_flagged;
-  unsigned int flagged_seen;
+  DeviceBuffer<unsigned int> d_flagged;
+  unsigned int flagged_seen = 0;
   // device-side safe pass (hmpc_set_device_repair): list of the instances the last fast launch flagged + its counter
-  int device_repair;
-  int *d_flag_list;
-  unsigned int *d_flag_count;
+  int device_repair = 0;
+  DeviceBuffer<int> d_flag_list;
+  DeviceBuffer<unsigned int> d_flag_count;
   // parity hook (hmpc_debug_solve_external_qp): device copies of caller-supplied QP data, only set during that call
-  const float *d_ext_H, *d_ext_g, *d_ext_Fc;
-  int ext_ld;
-  int iter_cap;  // hmpc_set_max_iterations: cap on the active-set iterations of every solve (0 = the variant's own bound)
+  const float *d_ext_H = nullptr, *d_ext_g = nullptr, *d_ext_Fc = nullptr;
+  int ext_ld = 0;
+  int iter_cap = 0;  // hmpc_set_max_iterations: cap on the active-set iterations of every solve (0 = the variant's own bound)
   // hmpc_set_dispatch_order: 1 = workgroups take the instances longest-previous-solve first (d_order, rebuilt at the head of
   // every solve from the status words the previous solve of a batch of the same size left; order_batch = that size, 0 = none)
-  int dispatch_order, order_batch;
-  bool order_valid;
-  int *d_order;
-  unsigned char *d_keys;  // predicted cost bucket per instance (cold-handle order), allocated on first use
+  int dispatch_order = 1, order_batch = 0;
+  bool order_valid = false;
+  DeviceBuffer<int> d_order;
+  DeviceBuffer<unsigned char> d_keys;  // predicted cost bucket per instance (cold-handle order), allocated on first use
   // size classes of a device-resident batch whose widest reduced QP the host was not told (hmpc_set_max_reduced_vars < 0):
   // stance leg-steps per instance, written on the device by the record builder (cls_valid) or, for records handed in by
   // pointer, by classify_records_kernel at the head of every solve
-  unsigned char *d_cls;
-  int cls_valid;
+  DeviceBuffer<unsigned char> d_cls;
+  int cls_valid = 0;
   // packed Schur inverses of the EGLOBAL safe variants: [e_slices][nmax (nmax + 1) / 2] doubles, grown on demand
-  double *d_escratch;
-  size_t e_bytes;
+  DeviceBuffer<double> d_escratch;
   // hand-over of full working sets (KernelArgs::spill): one slot per instance (slot = instance index), allocated on the first
   // launch of a variant that saves its state; spill_stride = bytes per slot of the allocation, spill_cap = slots
-  unsigned char *d_spill;
-  int *d_spill_slot;
-  size_t spill_stride;
-  int spill_cap;
-  int handover;  // hmpc_set_handover (default on)
-  hmpc_params params;  // robot / contact constants (hmpc_set_params; defaults = the reference's literals)
-  const float *d_mu_inst;  // hmpc_set_instance_mu: per-instance friction parameter in HBM (caller-owned), nullptr = params.mu for all
-  double *d_reg_rho;  // Hessians that are not positive definite: the pivot the safe variant found, then rho of hmpc_resolve_failed's regularisation steps, per instance (allocated with the first list launch)
-  // prediction (hmpc_predict_states): states [max_batch][horizon][13] binary32 and cost [max_batch][2] binary64; the handle's own buffers
-  // are allocated by the first call that needs them, d_pred_* = where the next prediction goes (the caller's, hmpc_set_device_prediction,
-  // or nullptr = the handle's own)
-  float *d_pred_states_own, *d_pred_states;
-  double *d_pred_cost_own, *d_pred_cost;
-  bool solve_enqueued;    // a solve of the CURRENT batch has been enqueued (cleared by everything that replaces the batch)
-  bool predict_enqueued;  // ... and a prediction behind it (cleared by every later solve as well: its forces are newer)
-  // selection (hmpc_sweep_select): one row per sweep group; the handle's own buffers are allocated for max_batch groups by the first call
-  // that needs them, d_sel_* = where the next selection goes (the caller's, hmpc_set_device_selection, or nullptr = the handle's own)
-  int32_t *d_sel_index_own, *d_sel_index;
-  double *d_sel_score_own, *d_sel_score;
-  float *d_sel_forces_own, *d_sel_forces;
-  uint32_t *d_sel_status_own, *d_sel_status;
-  float *d_sel_states_own, *d_sel_states;
-  bool select_enqueued;  // ... and a selection behind that prediction (cleared wherever predict_enqueued is, and by every prediction)
-  int select_groups;     // groups of that selection
-  double *d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
-  size_t sweep_m_bytes;
+  DeviceBuffer<unsigned char> d_spill;
+  DeviceBuffer<int> d_spill_slot;
+  size_t spill_stride = 0;
+  int spill_cap = 0;
+  int handover = 1;  // hmpc_set_handover (default on)
+  hmpc_params params{};  // robot / contact constants (hmpc_set_params; defaults = the reference's literals)
+  const float *d_mu_inst = nullptr;  // hmpc_set_instance_mu: per-instance friction parameter in HBM (caller-owned), nullptr = params.mu for all
+  DeviceBuffer<double> d_reg_rho;  // Hessians that are not positive definite: the pivot the safe variant found, then rho of hmpc_resolve_failed's regularisation steps, per instance (allocated with the first list launch)
+  // prediction (hmpc_predict_states): states [max_batch][horizon][13] binary32 and cost [max_batch][2] binary64, to the caller's buffers
+  // (hmpc_set_device_prediction) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<float> d_pred_states;
+  OutputBuffer<double> d_pred_cost;
+  bool solve_enqueued = false;    // a solve of the CURRENT batch has been enqueued (cleared by everything that replaces the batch)
+  bool predict_enqueued = false;  // ... and a prediction behind it (cleared by every later solve as well: its forces are newer)
+  // selection (hmpc_sweep_select): one row per sweep group, to the caller's buffers (hmpc_set_device_selection) or the handle's own,
+  // allocated for max_batch groups by the first call that needs them
+  OutputBuffer<int32_t> d_sel_index;
+  OutputBuffer<double> d_sel_score;
+  OutputBuffer<float> d_sel_forces;
+  OutputBuffer<uint32_t> d_sel_status;
+  OutputBuffer<float> d_sel_states;
+  bool select_enqueued = false;  // ... and a selection behind that prediction (cleared wherever predict_enqueued is, and by every prediction)
+  int select_groups = 0;         // groups of that selection
+  DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 // longest-first dispatch (hmpc_set_dispatch_order, on by default): only where a launch has a tail to shorten -- more instances
 // than the ~512-1536 workgroup slots of the chip -- and not beyond what the one-workgroup sort handles in a few microseconds
@@ -169,26 +167,11 @@ constexpr int DEVICE_REG_MIN_HORIZON = 10;  // device-side chain: the regularisa
 constexpr int REG_LIST_CAP = 256;  // device-side chain: instances per solve whose Hessian is not positive definite that get the regularisation launches (the rest: hmpc_resolve_failed)
 constexpr int REPAIR_GRID_CAP_WIDE = 4096;  // ... of the wide variant's, whose safe pass keeps 231 KB per workgroup in global memory (0.95 GB of 288: the list mixes size classes, so a small cap could leave a wide instance behind 256 others unrepaired -- ADVICE round 5)
 
-// grows a device buffer of the handle to at least `bytes` (contents undefined).  The old buffer is freed only once nothing can still
-// be using it: its users' stream is synchronised first, or the whole device when they may be on any stream (whole_device).
-template <class T>
-static int grow(T **buf, size_t *have, size_t bytes, hipStream_t stream, bool whole_device) {
-  if (*buf && bytes <= *have) return HMPC_OK;
-  if (*buf) {
-    HIP_TRY(whole_device ? hipDeviceSynchronize() : hipStreamSynchronize(stream));
-    HIP_TRY(hipFree(*buf));
-    *buf = nullptr, *have = 0;
-  }
-  HIP_TRY(hipMalloc((void **)buf, bytes));
-  *have = bytes;
-  return HMPC_OK;
-}
-
-// returns a device buffer of at least `bytes` owned by the handle (contents undefined)
+// returns a device buffer of at least `bytes` owned by the handle (contents undefined); its earlier users may be on any stream
 static int scratch(hmpc_handle *h, size_t bytes, void **out) {
-  const int rc = grow(&h->d_scratch, &h->scratch_bytes, (bytes + 4095) & ~(size_t)4095, nullptr, /*whole_device=*/true);
-  *out = h->d_scratch;
-  return rc;
+  HIP_TRY(h->d_scratch.reserve((bytes + 4095) & ~(size_t)4095, nullptr, /*whole_device=*/true));
+  *out = h->d_scratch.get();
+  return HMPC_OK;
 }
 
 // RAII for the two timing events of hmpc_time_solve
@@ -237,8 +220,8 @@ struct LaunchOpt {
   bool carry_wset = true;  // false keeps a repeated launch of the same batch from consuming/advancing the tick-to-tick working sets
   const unsigned int *d_list_count = nullptr;
   bool record_flagged = false;
-  bool longest_first = false;  // workgroup b takes instance h->d_order[b] (enqueue_solve, hmpc_set_dispatch_order)
-  int cls_lo = 0, cls_hi = -1;  // cls_hi >= 0: only instances whose size class lies in [cls_lo, cls_hi] (h->d_cls)
+  bool longest_first = false;  // workgroup b takes instance h->d_order.get()[b] (enqueue_solve, hmpc_set_dispatch_order)
+  int cls_lo = 0, cls_hi = -1;  // cls_hi >= 0: only instances whose size class lies in [cls_lo, cls_hi] (h->d_cls.get())
   int skip_ok = 0;         // list launch: instances an earlier pass over the same list solved are left alone (1: ok / ok-relaxed, 2: ok only)
   int sweep_k = 0, sweep_phase = 0;  // command sweep: group size; phase 0 = one workgroup per group forms M, 1 = one per instance solves with it (a SWEEP variant)
   bool list_indefinite = false;  // device-side chain, safe launch: instances ended as HMPC_S_INDEFINITE are appended to the handle's short list
@@ -258,7 +241,7 @@ static void set_problem_args(const hmpc_handle *h, hmpc::KernelArgs &a) {
   a.horizon = h->setup.horizon;
   a.dt = h->setup.dt;
   a.f_max = h->setup.f_max;
-  a.forces = h->d_forces;
+  a.forces = h->d_forces.get();
   a.inv_mass = 1.0f / h->params.mass;  // (binary32 division, correctly rounded: the value the reference's 1.f / 9.f folds to for the default)
   a.Ib[0] = h->params.inertia[0], a.Ib[1] = h->params.inertia[1], a.Ib[2] = h->params.inertia[2];
   a.mu = h->params.mu, a.lt = h->params.lt, a.lh = h->params.lh, a.gravity = h->params.gravity;
@@ -275,10 +258,8 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
   // safe pass over thousands of flagged instances goes through the list in chunks that reuse one bounded buffer (stream order
   // keeps the chunks apart).  The device-driven pass (d_list_count) is one launch, capped by its caller.
   const int chunk = (v.e_global && o.d_index_list && !o.d_list_count && grid_all > EGLOBAL_CHUNK) ? EGLOBAL_CHUNK : grid_all;
-  if (v.e_global) {  // one slice of packed triangle per workgroup of this launch
-    const int rc = grow(&h->d_escratch, &h->e_bytes, (size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double), stream, false);
-    if (rc != HMPC_OK) return rc;
-  }
+  if (v.e_global)  // one slice of packed triangle per workgroup of this launch
+    HIP_TRY(h->d_escratch.reserve((size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double), stream, /*whole_device=*/false));
   // hand-over slots: allocated on the first launch of a variant that saves its state (one slot per instance of the handle).
   // The per-instance slot table is written by EVERY ordinary launch of such a variant (-1 where nothing was saved), also when
   // saving itself is off for the launch, so that a later safe pass never meets an entry of an earlier batch.
@@ -286,15 +267,10 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
   if ((v.role == Role::SWEEP) != (o.sweep_k > 0)) return HMPC_E_ARG;
   const bool can_save = v.spill_stride > 0 && !o.assemble_only && !o.d_index_list;
   const bool saves = can_save && h->handover && !h->d_ext_H;
-  if (can_save && !h->d_spill_slot) {
-    HIP_TRY(hipMalloc(&h->d_spill_slot, (size_t)h->max_batch * sizeof(int)));
-    HIP_TRY(hipMemset(h->d_spill_slot, 0xff, (size_t)h->max_batch * sizeof(int)));
-  }
-  if (saves && (!h->d_spill || h->spill_stride < v.spill_stride)) {
+  if (can_save && !h->d_spill_slot.get()) HIP_TRY(h->d_spill_slot.alloc_filled((size_t)h->max_batch, 0xff));
+  if (saves && (!h->d_spill.get() || h->spill_stride < v.spill_stride)) {
     const int cap = h->max_batch < SPILL_SLOT_CAP ? h->max_batch : SPILL_SLOT_CAP;
-    size_t have = h->d_spill ? (size_t)h->spill_cap * h->spill_stride : 0;
-    const int rc = grow(&h->d_spill, &have, (size_t)cap * v.spill_stride, stream, /*whole_device=*/true);
-    if (rc != HMPC_OK) return rc;
+    HIP_TRY(h->d_spill.reserve((size_t)cap * v.spill_stride, stream, /*whole_device=*/true));
     h->spill_stride = v.spill_stride, h->spill_cap = cap;
   }
   kernel_fn fn = o.assemble_only ? v.assemble : v.solve;
@@ -304,46 +280,46 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
     h->attrs_set[vi] = true;
   }
   hmpc::KernelArgs a;
-  a.status = h->d_status;
-  a.x64 = h->d_x64;
-  a.obj64 = h->d_obj64;
+  a.status = h->d_status.get();
+  a.x64 = h->d_x64.get();
+  a.obj64 = h->d_obj64.get();
   a.dbg_index = o.dbg_index;
-  a.dbg_f = h->d_dbg_f;
-  a.dbg_i = h->d_dbg_i;
-  a.prof = h->d_prof;
+  a.dbg_f = h->d_dbg_f.get();
+  a.dbg_i = h->d_dbg_i.get();
+  a.prof = h->d_prof.get();
   a.warm = (o.warm < 0) ? h->warm : o.warm;
   a.index_list = o.d_index_list;
-  if (!o.d_index_list && !o.assemble_only && o.longest_first) a.index_list = h->d_order;
-  a.wset = (h->tick_warm && !o.assemble_only && o.carry_wset) ? h->d_wset : nullptr;
-  a.flagged = h->d_flagged;
+  if (!o.d_index_list && !o.assemble_only && o.longest_first) a.index_list = h->d_order.get();
+  a.wset = (h->tick_warm && !o.assemble_only && o.carry_wset) ? h->d_wset.get() : nullptr;
+  a.flagged = h->d_flagged.get();
   a.wset_shift = h->tick_shift;
   a.relax = o.relax;
-  a.flag_list = o.record_flagged ? h->d_flag_list : nullptr;
-  a.flag_count = o.record_flagged ? h->d_flag_count : nullptr;
+  a.flag_list = o.record_flagged ? h->d_flag_list.get() : nullptr;
+  a.flag_count = o.record_flagged ? h->d_flag_count.get() : nullptr;
   a.flag_cap = o.record_flagged ? flag_list_cap(h) : 0;
   a.list_count = o.d_list_count;
   a.ext_H = h->d_ext_H, a.ext_g = h->d_ext_g, a.ext_Fc = h->d_ext_Fc, a.ext_ld = h->ext_ld;
   a.iter_cap = h->iter_cap;
-  a.cls = (o.cls_hi >= 0) ? h->d_cls : nullptr;
+  a.cls = (o.cls_hi >= 0) ? h->d_cls.get() : nullptr;
   a.cls_lo = o.cls_lo, a.cls_hi = o.cls_hi;
-  a.e_scratch = h->d_escratch;
+  a.e_scratch = h->d_escratch.get();
   a.spill = nullptr, a.spill_stride = 0, a.spill_cap = 0, a.spill_slot = nullptr, a.resume = 0;
   if (can_save) {
-    a.spill_slot = h->d_spill_slot;
-    if (saves) a.spill = h->d_spill, a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap;
+    a.spill_slot = h->d_spill_slot.get();
+    if (saves) a.spill = h->d_spill.get(), a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap;
   } else if (v.role == Role::CONT) {
     // nothing was handed over (hand-over off / no slots), or the pass is one that must not resume: nothing to do
-    if (!o.d_index_list || !h->handover || !h->d_spill || !h->d_spill_slot || o.relax != 0.0 || h->d_ext_H) return HMPC_OK;
-    a.spill = h->d_spill, a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap, a.spill_slot = h->d_spill_slot;
+    if (!o.d_index_list || !h->handover || !h->d_spill.get() || !h->d_spill_slot.get() || o.relax != 0.0 || h->d_ext_H) return HMPC_OK;
+    a.spill = h->d_spill.get(), a.spill_stride = h->spill_stride, a.spill_cap = h->spill_cap, a.spill_slot = h->d_spill_slot.get();
     a.resume = 2;
   }
   a.skip_ok = o.skip_ok;
-  if (o.d_index_list && !h->d_reg_rho) HIP_TRY(hipMalloc(&h->d_reg_rho, (size_t)h->max_batch * sizeof(double)));  // (safe variants: where a pivot that is not positive is left)
-  a.reg_step = o.reg_step, a.reg_rho = h->d_reg_rho;
+  if (o.d_index_list && !h->d_reg_rho.get()) HIP_TRY(h->d_reg_rho.alloc((size_t)h->max_batch));  // (safe variants: where a pivot that is not positive is left)
+  a.reg_step = o.reg_step, a.reg_rho = h->d_reg_rho.get();
   a.reg_list = nullptr, a.reg_count = nullptr, a.reg_cap = 0;
-  if (o.list_indefinite && h->d_flag_list && h->d_flag_count)
-    a.reg_list = h->d_flag_list + flag_list_cap(h), a.reg_count = h->d_flag_count + 1, a.reg_cap = REG_LIST_CAP;
-  a.sweep_k = o.sweep_k > 0 ? o.sweep_k : 1, a.sweep_phase = o.sweep_phase, a.sweep_m = h->d_sweep_m;
+  if (o.list_indefinite && h->d_flag_list.get() && h->d_flag_count.get())
+    a.reg_list = h->d_flag_list.get() + flag_list_cap(h), a.reg_count = h->d_flag_count.get() + 1, a.reg_cap = REG_LIST_CAP;
+  a.sweep_k = o.sweep_k > 0 ? o.sweep_k : 1, a.sweep_phase = o.sweep_phase, a.sweep_m = h->d_sweep_m.get();
   set_problem_args(h, a);
   for (int off = 0; off < grid_all; off += chunk) {
     const int grid = (grid_all - off < chunk) ? grid_all - off : chunk;
@@ -356,7 +332,7 @@ static int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o
 
 // the size classes of a two-contact batch whose widest reduced QP only the device knows (records built on the device or handed in by
 // pointer): every variant of the family runs over the whole batch, a workgroup whose instance belongs to another one leaving at once
-static bool by_class(const hmpc_handle *h) { return h->nc == 2 && h->max_stance < 0 && h->d_cls; }
+static bool by_class(const hmpc_handle *h) { return h->nc == 2 && h->max_stance < 0 && h->d_cls.get(); }
 
 // The fast pass of one solve: one launch of variant `vi` over the batch, or (by_class) the size-class launches --
 //  * ordinary solves (variants(): [0] <60,10,128>, [1] <120,10,256>, [2] <60,20,128>, [3] <120,20,256>, V2_WIDE <240,20,512>):
@@ -377,11 +353,11 @@ static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes
   } else if (classes) {
     l[0] = {long_h ? 2 : 0, 0, 10}, l[1] = {long_h ? 3 : 1, 11, long_h ? 20 : 255}, l[2] = {V2_WIDE, 21, 255}, n = long_h ? 3 : 2;
   }
-  if ((n > 1 || variants()[l[0].vi].spill_stride == 0) && h->d_spill_slot && h->batch > 0)
-    HIP_TRY(hipMemsetAsync(h->d_spill_slot, 0xff, (size_t)h->batch * sizeof(int), stream));
+  if ((n > 1 || variants()[l[0].vi].spill_stride == 0) && h->d_spill_slot.get() && h->batch > 0)
+    HIP_TRY(hipMemsetAsync(h->d_spill_slot.get(), 0xff, (size_t)h->batch * sizeof(int), stream));
   if (classes && !h->cls_valid) {
     hipLaunchKernelGGL(hmpc::classify_records_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, stream, h->d_records,
-                       (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls);
+                       (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls.get());
     HIP_TRY(hipGetLastError());
   }
   const bool record_flagged = o.record_flagged;
@@ -406,7 +382,7 @@ static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes
 //     96 rows and block rounds of its own (two per CU).  *taken = whether the step applies (the safe pass behind it then leaves
 //     alone what it solved), also when the launch finds nothing to resume.
 static int continuation_pass(hmpc_handle *h, hipStream_t stream, const LaunchOpt &s, bool *taken) {
-  *taken = h->nc == 2 && h->handover && h->d_spill;
+  *taken = h->nc == 2 && h->handover && h->d_spill.get();
   return *taken ? launch(h, stream, repair_variant(h, Role::CONT), s) : HMPC_OK;
 }
 
@@ -442,8 +418,8 @@ static int reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
 // whose safe pass keeps 231 KB of global scratch per workgroup); workgroups beyond the flagged count leave at once
 static LaunchOpt device_list(const hmpc_handle *h) {
   LaunchOpt s;
-  s.d_index_list = h->d_flag_list;
-  s.d_list_count = h->d_flag_count;
+  s.d_index_list = h->d_flag_list.get();
+  s.d_list_count = h->d_flag_count.get();
   s.n_list = h->batch < REPAIR_GRID_CAP ? h->batch : REPAIR_GRID_CAP;
   if (pick_variant(h) == V2_WIDE && s.n_list > REPAIR_GRID_CAP_WIDE) s.n_list = REPAIR_GRID_CAP_WIDE;
   return s;
@@ -457,8 +433,8 @@ static LaunchOpt device_list(const hmpc_handle *h) {
 // 10x -- 20 000 instances).  A shorter-horizon handle would leave such an instance HMPC_S_INDEFINITE for hmpc_resolve_failed.
 static int device_reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
   if (h->setup.horizon <= DEVICE_REG_MIN_HORIZON) return HMPC_OK;
-  s.d_index_list = h->d_flag_list + flag_list_cap(h);
-  s.d_list_count = h->d_flag_count + 1;
+  s.d_index_list = h->d_flag_list.get() + flag_list_cap(h);
+  s.d_list_count = h->d_flag_count.get() + 1;
   s.n_list = h->batch < REG_LIST_CAP ? h->batch : REG_LIST_CAP;
   return reg_steps(h, stream, s);
 }
@@ -475,7 +451,7 @@ static int device_reg_steps(hmpc_handle *h, hipStream_t stream, LaunchOpt s) {
 //    counter belong to the handle, two solves of one handle in flight on two streams would race on them.
 static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
   const bool repair = h->device_repair != 0;
-  if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count, 0, 2 * sizeof(unsigned int), stream));
+  if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count.get(), 0, 2 * sizeof(unsigned int), stream));
   // longest-first dispatch: only where the tail of a launch matters (small and medium batches).  Keyed by the iteration counts
   // of the previous solve when that was of a batch of this size (the caller's contract: instance i of this tick is instance i
   // of the last one); otherwise -- a cold handle, another batch size, mode 2 -- by the cost predicted from the records themselves
@@ -484,17 +460,17 @@ static int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset) {
   // (... and not for batches known to hold single-support QPs only: those solve in one or two iterations, there is nothing to
   //  sort and the extra launch costs a walking batch 1-4 %)
   const bool small_qps_only = h->nc == 2 && h->max_stance >= 0 && h->max_stance <= 60;
-  if (h->dispatch_order != 0 && h->d_order && h->batch > DISPATCH_ORDER_MIN_BATCH && h->batch <= DISPATCH_ORDER_MAX_BATCH &&
+  if (h->dispatch_order != 0 && h->d_order.get() && h->batch > DISPATCH_ORDER_MIN_BATCH && h->batch <= DISPATCH_ORDER_MAX_BATCH &&
       !small_qps_only && !h->d_ext_H) {
     const bool from_previous = h->dispatch_order == 1 && h->order_batch == h->batch;
     if (!from_previous) {
-      if (!h->d_keys) HIP_TRY(hipMalloc(&h->d_keys, (size_t)h->max_batch));
+      if (!h->d_keys.get()) HIP_TRY(h->d_keys.alloc((size_t)h->max_batch));
       hipLaunchKernelGGL(hmpc::predicted_cost_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, stream, h->d_records, (int)h->stride,
-                         h->batch, h->setup.horizon, h->nc, h->d_keys);
+                         h->batch, h->setup.horizon, h->nc, h->d_keys.get());
       HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(hmpc::dispatch_order_kernel, dim3(1), dim3(1024), 0, stream, h->d_status, h->batch, h->d_order,
-                       from_previous ? (const unsigned char *)nullptr : h->d_keys);
+    hipLaunchKernelGGL(hmpc::dispatch_order_kernel, dim3(1), dim3(1024), 0, stream, h->d_status.get(), h->batch, h->d_order.get(),
+                       from_previous ? (const unsigned char *)nullptr : h->d_keys.get());
     HIP_TRY(hipGetLastError());
     h->order_valid = true;
   }
@@ -595,46 +571,23 @@ int hmpc_create_ex(hmpc_handle **out, const struct problem_setup *setup, int max
   HIP_TRY(hipSetDevice(device));
   hmpc_handle *h = new (std::nothrow) hmpc_handle();
   if (!h) return HMPC_E_ARG;
-  memset(h, 0, sizeof(*h));
   h->setup = *setup;
   h->max_batch = max_batch;
   h->device = device;
   h->nc = n_contacts;
   h->stride = record_stride(setup->horizon, n_contacts);
-  h->max_stance = -1;
-  h->warm = 1;
-  h->auto_resolve = 1;
-  h->handover = 1;
   hmpc_default_params(&h->params);
-  const size_t nf = (size_t)max_batch * 6 * n_contacts * setup->horizon;
-  if (hipMalloc(&h->d_records_own, (size_t)max_batch * h->stride) != hipSuccess ||
-      hipMalloc(&h->d_forces_own, nf * sizeof(float)) != hipSuccess ||
-      hipMalloc(&h->d_status_own, (size_t)max_batch * sizeof(uint32_t)) != hipSuccess) {
+  const size_t mb = (size_t)max_batch, nf = mb * 6 * n_contacts * setup->horizon;
+  const bool ok = h->d_record_store.alloc(mb * h->stride) == hipSuccess && h->d_forces.ensure(nf) == hipSuccess &&
+                  h->d_status.ensure(mb) == hipSuccess && h->d_flagged.alloc_filled(1, 0) == hipSuccess &&
+                  (n_contacts != 2 || h->d_cls.alloc_filled(mb, 0) == hipSuccess) &&
+                  (max_batch <= DISPATCH_ORDER_MIN_BATCH || (h->d_order.alloc(mb) == hipSuccess && h->d_keys.alloc(mb) == hipSuccess));
+  if (!ok) {
     g_hip_err = "hipMalloc failed in hmpc_create";
-    hmpc_destroy(h);
+    delete h;
     return HMPC_E_HIP;
   }
-  if (hipMalloc(&h->d_flagged, sizeof(unsigned int)) != hipSuccess ||
-      hipMemset(h->d_flagged, 0, sizeof(unsigned int)) != hipSuccess) {
-    g_hip_err = "hipMalloc failed in hmpc_create";
-    hmpc_destroy(h);
-    return HMPC_E_HIP;
-  }
-  if (n_contacts == 2 && (hipMalloc(&h->d_cls, (size_t)max_batch) != hipSuccess || hipMemset(h->d_cls, 0, (size_t)max_batch) != hipSuccess)) {
-    g_hip_err = "hipMalloc failed in hmpc_create";
-    hmpc_destroy(h);
-    return HMPC_E_HIP;
-  }
-  h->dispatch_order = 1;
-  if (max_batch > DISPATCH_ORDER_MIN_BATCH && (hipMalloc(&h->d_order, (size_t)max_batch * sizeof(int)) != hipSuccess ||
-                                               hipMalloc(&h->d_keys, (size_t)max_batch) != hipSuccess)) {
-    g_hip_err = "hipMalloc failed in hmpc_create";
-    hmpc_destroy(h);
-    return HMPC_E_HIP;
-  }
-  h->d_records = h->d_records_own;
-  h->d_forces = h->d_forces_own;
-  h->d_status = h->d_status_own;
+  h->d_records = h->d_record_store.get();
   *out = h;
   return HMPC_OK;
 }
@@ -642,36 +595,18 @@ int hmpc_create_ex(hmpc_handle **out, const struct problem_setup *setup, int max
 int hmpc_destroy(hmpc_handle *h) {
   if (!h) return HMPC_E_ARG;
   hipSetDevice(h->device);
-  if (h->d_records_own) hipFree(h->d_records_own);
-  if (h->d_forces_own) hipFree(h->d_forces_own);
-  if (h->d_status_own) hipFree(h->d_status_own);
-  if (h->d_x64) hipFree(h->d_x64);
-  if (h->d_obj64) hipFree(h->d_obj64);
-  if (h->d_dbg_f) hipFree(h->d_dbg_f);
-  if (h->d_dbg_i) hipFree(h->d_dbg_i);
-  if (h->d_prof) hipFree(h->d_prof);
-  if (h->d_wset) hipFree(h->d_wset);
-  if (h->d_keys) hipFree(h->d_keys);
-  if (h->d_scratch) hipFree(h->d_scratch);
-  if (h->d_flagged) hipFree(h->d_flagged);
-  if (h->d_flag_list) hipFree(h->d_flag_list);
-  if (h->d_flag_count) hipFree(h->d_flag_count);
-  if (h->d_cls) hipFree(h->d_cls);
-  if (h->d_order) hipFree(h->d_order);
-  if (h->d_escratch) hipFree(h->d_escratch);
-  if (h->d_sweep_m) hipFree(h->d_sweep_m);
-  if (h->d_reg_rho) hipFree(h->d_reg_rho);
-  if (h->d_spill) hipFree(h->d_spill);
-  if (h->d_spill_slot) hipFree(h->d_spill_slot);
-  if (h->d_pred_states_own) hipFree(h->d_pred_states_own);
-  if (h->d_pred_cost_own) hipFree(h->d_pred_cost_own);
-  if (h->d_sel_index_own) hipFree(h->d_sel_index_own);
-  if (h->d_sel_score_own) hipFree(h->d_sel_score_own);
-  if (h->d_sel_forces_own) hipFree(h->d_sel_forces_own);
-  if (h->d_sel_status_own) hipFree(h->d_sel_status_own);
-  if (h->d_sel_states_own) hipFree(h->d_sel_states_own);
-  delete h;
+  delete h;  // (every device buffer of the handle frees itself)
   return HMPC_OK;
+}
+
+// The handle now holds another batch: everything enqueued for the one before no longer counts.  max_stance = its widest reduced QP where
+// the host knows it (else -1), cls_valid = whether the device already holds its size classes.
+static void replace_batch(hmpc_handle *h, const unsigned char *records, int batch, int max_stance, int cls_valid) {
+  h->d_records = records;
+  h->batch = batch;
+  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
+  h->max_stance = max_stance;
+  h->cls_valid = cls_valid;
 }
 
 // pitch = bytes between consecutive records of the batch in host memory (h->stride: a packed array)
@@ -683,15 +618,11 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
   HIP_TRY(hipSetDevice(h->device));
   if (pitch != h->stride) {
     if (batch > 0)
-      HIP_TRY(hipMemcpy2DAsync(h->d_records_own, h->stride, host_records, pitch, h->stride, (size_t)batch, hipMemcpyHostToDevice, stream));
+      HIP_TRY(hipMemcpy2DAsync(h->d_record_store.get(), h->stride, host_records, pitch, h->stride, (size_t)batch, hipMemcpyHostToDevice, stream));
   } else if (async)
-    HIP_TRY(hipMemcpyAsync(h->d_records_own, host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(h->d_record_store.get(), host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice, stream));
   else
-    HIP_TRY(hipMemcpy(h->d_records_own, host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice));
-  h->d_records = h->d_records_own;
-  h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
-  h->cls_valid = 0;
+    HIP_TRY(hipMemcpy(h->d_record_store.get(), host_records, (size_t)batch * h->stride, hipMemcpyHostToDevice));
   // host-side scan of the gait tables: the widest reduced QP in the batch picks the kernel variant (LDS footprint)
   const int hz = h->setup.horizon;
   int mx = 0;
@@ -709,7 +640,7 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
     }
     if (cnt > mx) mx = cnt;
   }
-  h->max_stance = 6 * mx;
+  replace_batch(h, h->d_record_store.get(), batch, 6 * mx, /*cls_valid=*/0);
   return HMPC_OK;
 }
 
@@ -730,20 +661,17 @@ int hmpc_download_async(hmpc_handle *h, float *forces, uint32_t *status, void *s
   HIP_TRY(hipSetDevice(h->device));
   const size_t nf = (size_t)h->batch * 6 * h->nc * h->setup.horizon;
   if (forces && nf)
-    HIP_TRY(hipMemcpyAsync(forces, h->d_forces, nf * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(forces, h->d_forces.get(), nf * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
   if (status && h->batch)
-    HIP_TRY(hipMemcpyAsync(status, h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(status, h->d_status.get(), (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
   return HMPC_OK;
 }
 
 int hmpc_set_device_records(hmpc_handle *h, const void *device_records, int batch) {
   if (!h || !device_records || batch < 0) return HMPC_E_ARG;
   if (batch > h->max_batch) return HMPC_E_BATCH;
-  h->d_records = (const unsigned char *)device_records;
-  h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
-  h->max_stance = -1;  // unknown: hmpc_solve counts the size classes on the device (or hmpc_set_max_reduced_vars tells)
-  h->cls_valid = 0;
+  // (widest reduced QP unknown: hmpc_solve counts the size classes on the device, or hmpc_set_max_reduced_vars tells)
+  replace_batch(h, (const unsigned char *)device_records, batch, /*max_stance=*/-1, /*cls_valid=*/0);
   return HMPC_OK;
 }
 
@@ -755,13 +683,10 @@ int hmpc_set_max_reduced_vars(hmpc_handle *h, int n_reduced) {
 
 int hmpc_set_dispatch_order(hmpc_handle *h, int mode) {
   if (!h || (mode != 0 && mode != 1 && mode != 2)) return HMPC_E_ARG;
-  if (mode != 0 && !h->d_order && h->max_batch > DISPATCH_ORDER_MIN_BATCH) {
+  if (mode != 0 && h->max_batch > DISPATCH_ORDER_MIN_BATCH && (!h->d_order.get() || !h->d_keys.get())) {
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMalloc(&h->d_order, (size_t)h->max_batch * sizeof(int)));
-  }
-  if (mode != 0 && !h->d_keys && h->max_batch > DISPATCH_ORDER_MIN_BATCH) {
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMalloc(&h->d_keys, (size_t)h->max_batch));
+    if (!h->d_order.get()) HIP_TRY(h->d_order.alloc((size_t)h->max_batch));
+    if (!h->d_keys.get()) HIP_TRY(h->d_keys.alloc((size_t)h->max_batch));
   }
   h->dispatch_order = mode;
   h->order_batch = 0;  // the next solve is ordered by the predictor (mode 1, 2) and leaves the iteration counts the one after it sorts by (mode 1)
@@ -833,11 +758,7 @@ int hmpc_set_warm_start(hmpc_handle *h, int on) {
 int hmpc_set_tick_warm_start(hmpc_handle *h, int on, int horizon_shift) {
   if (!h || horizon_shift < 0) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  if (on && !h->d_wset) {
-    const size_t nb = (size_t)h->max_batch * 8 * h->nc * h->setup.horizon;
-    HIP_TRY(hipMalloc(&h->d_wset, nb));
-    HIP_TRY(hipMemset(h->d_wset, 0, nb));
-  }
+  if (on && !h->d_wset.get()) HIP_TRY(h->d_wset.alloc_filled((size_t)h->max_batch * 8 * h->nc * h->setup.horizon, 0));
   h->tick_warm = on ? 1 : 0;
   h->tick_shift = horizon_shift;
   return HMPC_OK;
@@ -845,17 +766,16 @@ int hmpc_set_tick_warm_start(hmpc_handle *h, int on, int horizon_shift) {
 
 int hmpc_reset_tick_warm_start(hmpc_handle *h) {
   if (!h) return HMPC_E_ARG;
-  if (!h->d_wset) return HMPC_OK;
+  if (!h->d_wset.get()) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
-  HIP_TRY(hipMemset(h->d_wset, 0, (size_t)h->max_batch * 8 * h->nc * h->setup.horizon));
+  HIP_TRY(hipMemset(h->d_wset.get(), 0, (size_t)h->max_batch * 8 * h->nc * h->setup.horizon));
   return HMPC_OK;
 }
 
 int hmpc_set_device_outputs(hmpc_handle *h, float *device_forces, uint32_t *device_status) {
   if (!h) return HMPC_E_ARG;
-  h->d_forces = device_forces ? device_forces : h->d_forces_own;
-  h->d_status = device_status ? device_status : h->d_status_own;
+  h->d_forces.set_caller(device_forces), h->d_status.set_caller(device_status);
   return HMPC_OK;
 }
 
@@ -884,14 +804,13 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   // differs from its group's first record's may land in the other launch: it is reported there, never solved)
   const int vi = small ? V2_SWEEP_60 : V2_SWEEP_120;
   const size_t need = (size_t)(h->batch / group_size) * 36 * (size_t)variants()[vi].nt * sizeof(double);  // (V2_SWEEP_120 has the wider workgroups)
-  int rc = grow(&h->d_sweep_m, &h->sweep_m_bytes, need, st, /*whole_device=*/false);
-  if (rc != HMPC_OK) return rc;
+  HIP_TRY(h->d_sweep_m.reserve(need, st, /*whole_device=*/false));
   const bool repair = h->device_repair != 0;
-  if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count, 0, 2 * sizeof(unsigned int), st));
+  if (repair) HIP_TRY(hipMemsetAsync(h->d_flag_count.get(), 0, 2 * sizeof(unsigned int), st));
   h->order_valid = false, h->order_batch = 0;  // (natural order inside a sweep; the next ordinary solve starts from the predictor)
   LaunchOpt o;
   o.sweep_k = group_size, o.record_flagged = repair;
-  rc = enqueue_fast(h, st, vi, by_class(h), o);
+  int rc = enqueue_fast(h, st, vi, by_class(h), o);
   if (rc != HMPC_OK || !repair) return rc;
   // whatever a sweep flags is repaired as an independent instance (its record is complete): the cold safe pass (sweeps save nothing:
   // no continuation), also under device-repair mode 2
@@ -905,21 +824,15 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
 int hmpc_set_device_repair(hmpc_handle *h, int on) {
   if (!h) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  if (on && (!h->d_flag_list || !h->d_flag_count)) {
+  if (on && (!h->d_flag_list.get() || !h->d_flag_count.get())) {
     // both buffers or neither: they are committed to the handle only once both exist and are cleared
-    const int cap = flag_list_cap(h);
-    int *list = nullptr;
-    unsigned int *count = nullptr;
-    if (hipMalloc(&list, (size_t)(cap + REG_LIST_CAP) * sizeof(int)) != hipSuccess || hipMalloc(&count, 2 * sizeof(unsigned int)) != hipSuccess ||
-        hipMemset(list, 0, (size_t)(cap + REG_LIST_CAP) * sizeof(int)) != hipSuccess || hipMemset(count, 0, 2 * sizeof(unsigned int)) != hipSuccess) {
-      if (list) (void)hipFree(list);
-      if (count) (void)hipFree(count);
+    DeviceBuffer<int> list;
+    DeviceBuffer<unsigned int> count;
+    if (list.alloc_filled((size_t)(flag_list_cap(h) + REG_LIST_CAP), 0) != hipSuccess || count.alloc_filled(2, 0) != hipSuccess) {
       g_hip_err = "hipMalloc failed in hmpc_set_device_repair";
       return HMPC_E_HIP;
     }
-    if (h->d_flag_list) (void)hipFree(h->d_flag_list);
-    if (h->d_flag_count) (void)hipFree(h->d_flag_count);
-    h->d_flag_list = list, h->d_flag_count = count;
+    h->d_flag_list = std::move(list), h->d_flag_count = std::move(count);
   }
   h->device_repair = (on == 2) ? 2 : (on ? 1 : 0);
   return HMPC_OK;
@@ -938,7 +851,7 @@ int hmpc_resolve_failed(hmpc_handle *h, int *n_resolved) {
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
   std::vector<uint32_t> st(h->batch);
-  HIP_TRY(hipMemcpy(st.data(), h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st.data(), h->d_status.get(), (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<int> idx;
   for (int i = 0; i < h->batch; ++i) {
     const uint32_t c = HMPC_STATUS_CODE(st[i]);
@@ -980,7 +893,7 @@ int hmpc_resolve_failed(hmpc_handle *h, int *n_resolved) {
   // them (a copy of `so` with that list), synchronise; *ran = whether anything was kept
   auto rerun = [&](auto keep, auto pass, bool *ran) -> int {
     std::vector<int> sub;
-    HIP_TRY(hipMemcpy(st.data(), h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(st.data(), h->d_status.get(), (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int i : idx)
       if (keep(st[i])) sub.push_back(i);
     *ran = !sub.empty();
@@ -1031,11 +944,11 @@ int hmpc_resolve_failed(hmpc_handle *h, int *n_resolved) {
 // the status words need to be scanned at all (they almost never do: nominal inputs flag nothing)
 static int resolve_if_flagged(hmpc_handle *h) {
   unsigned int now = 0;
-  HIP_TRY(hipMemcpy(&now, h->d_flagged, sizeof(now), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&now, h->d_flagged.get(), sizeof(now), hipMemcpyDeviceToHost));
   if (now == h->flagged_seen) return HMPC_OK;
   const int rc = hmpc_resolve_failed(h, nullptr);
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipMemcpy(&now, h->d_flagged, sizeof(now), hipMemcpyDeviceToHost));  // the safe pass may have flagged again
+  HIP_TRY(hipMemcpy(&now, h->d_flagged.get(), sizeof(now), hipMemcpyDeviceToHost));  // the safe pass may have flagged again
   h->flagged_seen = now;
   return HMPC_OK;
 }
@@ -1049,16 +962,16 @@ int hmpc_download(hmpc_handle *h, float *forces, uint32_t *status) {
     if (rc != HMPC_OK) return rc;
   }
   const size_t nf = (size_t)h->batch * 6 * h->nc * h->setup.horizon;
-  if (forces && nf) HIP_TRY(hipMemcpy(forces, h->d_forces, nf * sizeof(float), hipMemcpyDeviceToHost));
+  if (forces && nf) HIP_TRY(hipMemcpy(forces, h->d_forces.get(), nf * sizeof(float), hipMemcpyDeviceToHost));
   if (status && h->batch)
-    HIP_TRY(hipMemcpy(status, h->d_status, (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status, h->d_status.get(), (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
 
 int hmpc_get_device_outputs(hmpc_handle *h, float **device_forces, uint32_t **device_status) {
   if (!h) return HMPC_E_ARG;
-  if (device_forces) *device_forces = h->d_forces;
-  if (device_status) *device_status = h->d_status;
+  if (device_forces) *device_forces = h->d_forces.get();
+  if (device_status) *device_status = h->d_status.get();
   return HMPC_OK;
 }
 
@@ -1096,11 +1009,9 @@ int hmpc_debug_assemble(hmpc_handle *h, int index, int *n, int *m, int *var_ind,
   HIP_TRY(hipSetDevice(h->device));
   const int vi = pick_variant(h);
   const Variant &v = variants()[vi];
-  if (!h->d_dbg_f) {
-    HIP_TRY(hipMalloc(&h->d_dbg_f, sizeof(float) * (size_t)DBG_FLOATS_MAX));
-    HIP_TRY(hipMalloc(&h->d_dbg_i, sizeof(int) * (2 + MAX_VARS_ANY)));
-  }
-  HIP_TRY(hipMemset(h->d_dbg_i, 0, sizeof(int) * (2 + MAX_VARS_ANY)));
+  if (!h->d_dbg_f.get()) HIP_TRY(h->d_dbg_f.alloc((size_t)DBG_FLOATS_MAX));
+  if (!h->d_dbg_i.get()) HIP_TRY(h->d_dbg_i.alloc(2 + MAX_VARS_ANY));
+  HIP_TRY(hipMemset(h->d_dbg_i.get(), 0, sizeof(int) * (2 + MAX_VARS_ANY)));
   LaunchOpt ao;
   ao.assemble_only = true, ao.dbg_index = index;
   int rc = launch(h, 0, vi, ao);
@@ -1108,8 +1019,8 @@ int hmpc_debug_assemble(hmpc_handle *h, int index, int *n, int *m, int *var_ind,
   HIP_TRY(hipDeviceSynchronize());
   std::vector<float> hf(v.dbg_floats);
   std::vector<int> hi(2 + MAX_VARS_ANY);
-  HIP_TRY(hipMemcpy(hf.data(), h->d_dbg_f, sizeof(float) * hf.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hi.data(), h->d_dbg_i, sizeof(int) * hi.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hf.data(), h->d_dbg_f.get(), sizeof(float) * hf.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hi.data(), h->d_dbg_i.get(), sizeof(int) * hi.size(), hipMemcpyDeviceToHost));
   const int nn = hi[0], mm = hi[1], hz = h->setup.horizon;
   if (n) *n = nn;
   if (m) *m = mm;
@@ -1144,14 +1055,9 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
   const size_t nb = (size_t)h->batch, nfc = (size_t)8 * h->nc * 6 * h->nc;
-  const size_t bytes = sizeof(float) * nb * ((size_t)ld * ld + ld + nfc);
-  float *d = nullptr;
-  HIP_TRY(hipMalloc(&d, bytes));
-  struct Free {
-    float *p;
-    ~Free() { (void)hipFree(p); }
-  } guard{d};
-  float *dH = d, *dg = dH + nb * ld * ld, *dF = dg + nb * ld;
+  DeviceBuffer<float> ext;  // (freed on every return path)
+  HIP_TRY(ext.alloc(nb * ((size_t)ld * ld + ld + nfc)));
+  float *dH = ext.get(), *dg = dH + nb * ld * ld, *dF = dg + nb * ld;
   HIP_TRY(hipMemcpy(dH, H, sizeof(float) * nb * ld * ld, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dg, g, sizeof(float) * nb * ld, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dF, Fc, sizeof(float) * nb * nfc, hipMemcpyHostToDevice));
@@ -1172,11 +1078,11 @@ int hmpc_debug_handover_slots(hmpc_handle *h, int *slots) {
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
-  if (!h->d_spill_slot) {  // (no saving variant has run on this handle: nothing was ever handed over)
+  if (!h->d_spill_slot.get()) {  // (no saving variant has run on this handle: nothing was ever handed over)
     for (int i = 0; i < h->batch; ++i) slots[i] = -1;
     return HMPC_OK;
   }
-  HIP_TRY(hipMemcpy(slots, h->d_spill_slot, (size_t)h->batch * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(slots, h->d_spill_slot.get(), (size_t)h->batch * sizeof(int), hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
 
@@ -1190,15 +1096,14 @@ int hmpc_debug_phase_cycles(hmpc_handle *h, long long *cycles /*[batch][NPROF = 
   if (!h || !cycles) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nb = (size_t)h->max_batch * hmpc::NPROF * sizeof(long long);
-  if (!h->d_prof) HIP_TRY(hipMalloc(&h->d_prof, nb));
-  HIP_TRY(hipMemset(h->d_prof, 0, nb));
+  if (!h->d_prof.get()) HIP_TRY(h->d_prof.alloc((size_t)h->max_batch * hmpc::NPROF));
+  HIP_TRY(hipMemset(h->d_prof.get(), 0, nb));
   // (with the device-side repair on, the whole chain: an instance's slot then holds the numbers of the LAST variant that ran it)
   int rc = h->device_repair ? enqueue_solve(h, h->last_stream, false) : launch(h, h->last_stream, pick_variant(h), LaunchOpt());
   if (rc != HMPC_OK) return rc;
   HIP_TRY(hipStreamSynchronize(h->last_stream));
-  HIP_TRY(hipMemcpy(cycles, h->d_prof, (size_t)h->batch * hmpc::NPROF * sizeof(long long), hipMemcpyDeviceToHost));
-  HIP_TRY(hipFree(h->d_prof));
-  h->d_prof = nullptr;
+  HIP_TRY(hipMemcpy(cycles, h->d_prof.get(), (size_t)h->batch * hmpc::NPROF * sizeof(long long), hipMemcpyDeviceToHost));
+  h->d_prof.reset();
   return HMPC_OK;
 #endif
 }
@@ -1214,15 +1119,12 @@ int hmpc_build_records_device(hmpc_handle *h, const void *device_ticks, int batc
     const int nwords = (int)h->stride / 4;
     const int bs = ((nwords + 63) / 64) * 64 > 256 ? 256 : ((nwords + 63) / 64) * 64;
     hipLaunchKernelGGL(hmpc::build_records_kernel, dim3(batch), dim3(bs), 0, (hipStream_t)stream,
-                       (const hmpc_tick_inputs *)device_ticks, batch, h->setup.horizon, dtMPC, h->d_records_own,
-                       (int)h->stride, device_wpd_out, h->setup.f_max, h->d_cls);
+                       (const hmpc_tick_inputs *)device_ticks, batch, h->setup.horizon, dtMPC, h->d_record_store.get(),
+                       (int)h->stride, device_wpd_out, h->setup.f_max, h->d_cls.get());
     HIP_TRY(hipGetLastError());
   }
-  h->d_records = h->d_records_own;
-  h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
-  h->max_stance = -1;  // the builder left every instance's size class on the device: hmpc_solve routes by it
-  h->cls_valid = 1;
+  // (the builder left every instance's size class on the device: hmpc_solve routes by it)
+  replace_batch(h, h->d_record_store.get(), batch, /*max_stance=*/-1, /*cls_valid=*/1);
   h->last_stream = (hipStream_t)stream;
   return HMPC_OK;
 }
@@ -1252,7 +1154,7 @@ int hmpc_body_wrench_device(hmpc_handle *h, const double *device_rBody, double *
   HIP_TRY(hipSetDevice(h->device));
   if (h->batch > 0) {
     const int total = 12 * h->batch;
-    hipLaunchKernelGGL(hmpc::body_wrench_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces,
+    hipLaunchKernelGGL(hmpc::body_wrench_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces.get(),
                        h->batch, h->setup.horizon, device_rBody, device_f_ff);
     HIP_TRY(hipGetLastError());
   }
@@ -1284,7 +1186,7 @@ int hmpc_leg_torques_device(hmpc_handle *h, const double *device_rBody, const do
   HIP_TRY(hipSetDevice(h->device));
   if (h->batch > 0) {
     const int total = 2 * h->batch;
-    hipLaunchKernelGGL(hmpc::leg_torque_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces,
+    hipLaunchKernelGGL(hmpc::leg_torque_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces.get(),
                        h->batch, h->setup.horizon, device_rBody, device_leg_q, device_f_ff, device_tau,
                        (const hmpc_tick_inputs *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -1326,7 +1228,7 @@ int hmpc_tick_solve_device(hmpc_handle *h, const void *device_ticks, int batch, 
   rc = enqueue_solve(h, (hipStream_t)stream, /*carry_wset=*/true);
   if (rc != HMPC_OK) return rc;
   const int total = 2 * batch;
-  hipLaunchKernelGGL(hmpc::leg_torque_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces, batch,
+  hipLaunchKernelGGL(hmpc::leg_torque_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->d_forces.get(), batch,
                      h->setup.horizon, (const double *)nullptr, (const double *)nullptr, device_f_ff, device_tau,
                      (const hmpc_tick_inputs *)device_ticks);
   HIP_TRY(hipGetLastError());
@@ -1343,16 +1245,16 @@ int hmpc_download_records(hmpc_handle *h, void *host_records) {
 
 int hmpc_enable_f64_output(hmpc_handle *h) {
   if (!h) return HMPC_E_ARG;
-  if (h->d_x64) return HMPC_OK;
+  if (h->d_x64.get()) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nf = (size_t)h->max_batch * 6 * h->nc * h->setup.horizon;
-  HIP_TRY(hipMalloc(&h->d_x64, nf * sizeof(double)));
-  if (hipMalloc(&h->d_obj64, (size_t)h->max_batch * sizeof(double)) != hipSuccess) {
-    hipFree(h->d_x64);
-    h->d_x64 = nullptr;
+  // both buffers or neither
+  DeviceBuffer<double> x, obj;
+  HIP_TRY(x.alloc((size_t)h->max_batch * 6 * h->nc * h->setup.horizon));
+  if (obj.alloc((size_t)h->max_batch) != hipSuccess) {
     g_hip_err = "hipMalloc failed in hmpc_enable_f64_output";
     return HMPC_E_HIP;
   }
+  h->d_x64 = std::move(x), h->d_obj64 = std::move(obj);
   return HMPC_OK;
 }
 
@@ -1360,7 +1262,7 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj) {
   if (!h) return HMPC_E_ARG;
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  if (!h->d_x64) {
+  if (!h->d_x64.get()) {
     // the copy-out was not enabled before the solve: enable it and run the current batch once more -- without consuming
     // the tick-to-tick working sets a second time -- then give flagged instances the same safe pass hmpc_download gives
     int rc = hmpc_enable_f64_output(h);
@@ -1374,8 +1276,8 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj) {
     if (rc != HMPC_OK) return rc;
   }
   const size_t nb = (size_t)h->batch * 6 * h->nc * h->setup.horizon;
-  if (x && nb) HIP_TRY(hipMemcpy(x, h->d_x64, nb * sizeof(double), hipMemcpyDeviceToHost));
-  if (obj && h->batch) HIP_TRY(hipMemcpy(obj, h->d_obj64, (size_t)h->batch * sizeof(double), hipMemcpyDeviceToHost));
+  if (x && nb) HIP_TRY(hipMemcpy(x, h->d_x64.get(), nb * sizeof(double), hipMemcpyDeviceToHost));
+  if (obj && h->batch) HIP_TRY(hipMemcpy(obj, h->d_obj64.get(), (size_t)h->batch * sizeof(double), hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
 
@@ -1384,17 +1286,15 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj) {
 // ------------------------------------------------------------------------------------------------------------------
 // where the next prediction goes: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
 static int prediction_buffers(hmpc_handle *h, float **states, double **cost) {
-  if (!h->d_pred_states && !h->d_pred_states_own)
-    HIP_TRY(hipMalloc(&h->d_pred_states_own, (size_t)h->max_batch * h->setup.horizon * 13 * sizeof(float)));
-  if (!h->d_pred_cost && !h->d_pred_cost_own) HIP_TRY(hipMalloc(&h->d_pred_cost_own, (size_t)h->max_batch * 2 * sizeof(double)));
-  *states = h->d_pred_states ? h->d_pred_states : h->d_pred_states_own;
-  *cost = h->d_pred_cost ? h->d_pred_cost : h->d_pred_cost_own;
+  HIP_TRY(h->d_pred_states.ensure((size_t)h->max_batch * h->setup.horizon * 13));
+  HIP_TRY(h->d_pred_cost.ensure((size_t)h->max_batch * 2));
+  *states = h->d_pred_states.get(), *cost = h->d_pred_cost.get();
   return HMPC_OK;
 }
 
 int hmpc_set_device_prediction(hmpc_handle *h, float *device_states, double *device_cost) {
   if (!h) return HMPC_E_ARG;
-  h->d_pred_states = device_states, h->d_pred_cost = device_cost;
+  h->d_pred_states.set_caller(device_states), h->d_pred_cost.set_caller(device_cost);
   h->predict_enqueued = h->select_enqueued = false;  // (whatever was predicted went elsewhere)
   return HMPC_OK;
 }
@@ -1458,22 +1358,19 @@ struct SelectionBuffers {
 // where the next selection goes: the caller's buffers, else the handle's own (allocated here, for max_batch groups, on first need)
 static int selection_buffers(hmpc_handle *h, SelectionBuffers *b) {
   const size_t mb = (size_t)h->max_batch, hz = (size_t)h->setup.horizon;
-  if (!h->d_sel_index && !h->d_sel_index_own) HIP_TRY(hipMalloc(&h->d_sel_index_own, mb * sizeof(int32_t)));
-  if (!h->d_sel_score && !h->d_sel_score_own) HIP_TRY(hipMalloc(&h->d_sel_score_own, mb * sizeof(double)));
-  if (!h->d_sel_forces && !h->d_sel_forces_own) HIP_TRY(hipMalloc(&h->d_sel_forces_own, mb * 6 * h->nc * hz * sizeof(float)));
-  if (!h->d_sel_status && !h->d_sel_status_own) HIP_TRY(hipMalloc(&h->d_sel_status_own, mb * sizeof(uint32_t)));
-  if (!h->d_sel_states && !h->d_sel_states_own) HIP_TRY(hipMalloc(&h->d_sel_states_own, mb * hz * 13 * sizeof(float)));
-  b->index = h->d_sel_index ? h->d_sel_index : h->d_sel_index_own;
-  b->score = h->d_sel_score ? h->d_sel_score : h->d_sel_score_own;
-  b->forces = h->d_sel_forces ? h->d_sel_forces : h->d_sel_forces_own;
-  b->status = h->d_sel_status ? h->d_sel_status : h->d_sel_status_own;
-  b->states = h->d_sel_states ? h->d_sel_states : h->d_sel_states_own;
+  HIP_TRY(h->d_sel_index.ensure(mb));
+  HIP_TRY(h->d_sel_score.ensure(mb));
+  HIP_TRY(h->d_sel_forces.ensure(mb * 6 * h->nc * hz));
+  HIP_TRY(h->d_sel_status.ensure(mb));
+  HIP_TRY(h->d_sel_states.ensure(mb * hz * 13));
+  *b = {h->d_sel_index.get(), h->d_sel_score.get(), h->d_sel_forces.get(), h->d_sel_status.get(), h->d_sel_states.get()};
   return HMPC_OK;
 }
 
 int hmpc_set_device_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states) {
   if (!h) return HMPC_E_ARG;
-  h->d_sel_index = index, h->d_sel_score = score, h->d_sel_forces = forces, h->d_sel_status = status, h->d_sel_states = states;
+  h->d_sel_index.set_caller(index), h->d_sel_score.set_caller(score), h->d_sel_forces.set_caller(forces);
+  h->d_sel_status.set_caller(status), h->d_sel_states.set_caller(states);
   h->select_enqueued = false;  // (whatever was selected went elsewhere)
   return HMPC_OK;
 }
@@ -1507,7 +1404,7 @@ int hmpc_sweep_select(hmpc_handle *h, int group_size, const double *device_penal
   rc = selection_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
   hmpc::SelectArgs a;
-  a.cost = pc, a.states = ps, a.status = h->d_status, a.forces = h->d_forces, a.penalty = device_penalty;
+  a.cost = pc, a.states = ps, a.status = h->d_status.get(), a.forces = h->d_forces.get(), a.penalty = device_penalty;
   a.groups = h->batch / group_size, a.group_size = group_size;
   a.force_words = 6 * h->nc * h->setup.horizon, a.state_words = 13 * h->setup.horizon;
   a.index = b.index, a.score = b.score, a.out_forces = b.forces, a.out_status = b.status, a.out_states = b.states;

@@ -96,6 +96,8 @@ def main():
     if diff_path:
         old = {}
         for line in open(diff_path):
+            if line.startswith("#"):  # (a committed listing carries comment lines; of a kernel listed twice the last row counts)
+                continue
             p = line.split(None, 2)
             if len(p) == 3:
                 old[p[2].strip()] = (p[0], int(p[1]))
