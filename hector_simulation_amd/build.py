@@ -20,8 +20,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhector_mpc_hip.so")
 VARIANT_GROUPS = 4  # = HMPC_VARIANT_GROUPS of csrc/hmpc_variants.h
 HOST_SOURCES = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_predict.hip", "hmpc_select.hip"]  # (hmpc_predict.hip, hmpc_select.hip: the prediction and selection kernels, units of their own)
-DEPS = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_variants.hip", "hmpc_variants.h", "hmpc_kernel_args.h", "hmpc_kernel.h",
-        "hmpc_math.h", "hmpc_builder.h", "hmpc_predict.hip", "hmpc_predict.h", "hmpc_select.hip", "hmpc_select.h", os.path.join("..", "..", "include", "hector_mpc.h")]
+# every header and unit of csrc/, so that a new header can never be left out of the staleness hash
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join("..", "..", "include", "hector_mpc.h")]
 # -ffp-contract=off is part of the numerical contract (HMPC-A1): every fused multiply-add in the source is explicit
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"]
 EXTRA = os.environ.get("HMPC_EXTRA_FLAGS", "").split()  # developer A/B switches, e.g. -DHMPC_MFMA_SWEEP=0 (same results, other code)

@@ -14,17 +14,19 @@
 
 #include "../../include/hector_mpc.h"
 #include "hmpc_math.h"
+#include "hmpc_record.h"
 
 namespace hmpc {
 
 // One workgroup per instance; thread t produces 32-bit word t of the packed record (coalesced 720-B burst out).
 // cls (optional): the instance's stance leg-step count -- the size class hmpc_solve routes it by (KernelArgs::cls), counted
-// with the solver's own criterion (|f_max * gait| >= 1e-4, SolverMPC.cpp:589-637).
+// with the solver's own criterion (stance() of hmpc_record.h).
 __global__ __launch_bounds__(256) void build_records_kernel(const hmpc_tick_inputs *ticks, int batch, int h, double dtMPC,
                                                             unsigned char *records, int stride, double *wpd_out, float f_max,
                                                             unsigned char *cls) {
   const int inst = blockIdx.x;
   if (inst >= batch) return;
+  using RL = RecLayout<2>;
   const hmpc_tick_inputs &tk = ticks[inst];
   const int nwords = stride >> 2, ntraj = 12 * h;
   uint32_t *out = reinterpret_cast<uint32_t *>(records + (size_t)inst * stride);
@@ -51,24 +53,23 @@ __global__ __launch_bounds__(256) void build_records_kernel(const hmpc_tick_inpu
       const int i = gi >> 1, j = gi & 1;
       int progress = (i + tk.gait_iteration) % h - tk.gait_offsets[j];
       if (progress < 0) progress += h;
-      const float ubc = f_max * (float)((progress < tk.gait_durations[j]) ? 1 : 0);
-      cnt += !(ubc < 0.0001 && ubc > -.0001);
+      cnt += stance(f_max, (progress < tk.gait_durations[j]) ? 1 : 0);
     }
     cls[inst] = (unsigned char)cnt;
   }
   for (int t = threadIdx.x; t < nwords; t += blockDim.x) {
     uint32_t word = 0;
-    if (t < 54 + ntraj) {
+    if (t < RL::NF + ntraj) {
       double v;
-      if (t < 3) v = p[t];
-      else if (t < 6) v = tk.vWorld[t - 3];
-      else if (t < 10) v = tk.orientation[t - 6];
-      else if (t < 13) v = tk.omegaWorld[t - 10];
-      else if (t < 19) {
-        const int i = t - 13;
+      if (t < RL::V) v = p[t - RL::P];
+      else if (t < RL::Q) v = tk.vWorld[t - RL::V];
+      else if (t < RL::W) v = tk.orientation[t - RL::Q];
+      else if (t < RL::R) v = tk.omegaWorld[t - RL::W];
+      else if (t < RL::JA) {
+        const int i = t - RL::R;
         v = tk.pFoot[3 * (i % 2) + i / 2] - p[i / 2];
-      } else if (t < 29) {
-        const int i = t - 19, k = i % 5;
+      } else if (t < RL::YAW) {
+        const int i = t - RL::JA, k = i % 5;
         double a = tk.leg_q[i];
         if (tk.flags & HMPC_TICK_LEG_Q_MOTOR) {  // LegController.cpp:111-113 mutates data[leg].q before the MPC reads it
           if (k == 2 || k == 4) a = a + 0.3 * 3.14159;
@@ -77,15 +78,15 @@ __global__ __launch_bounds__(256) void build_records_kernel(const hmpc_tick_inpu
         if (k == 2 || k == 4) a += 0.3 * PI;
         if (k == 3) a -= 0.6 * PI;
         v = (__builtin_fabs(a) < PI2) ? a : fmod(a, PI2);  // fmod(x,y) == x exactly when |x| < y
-      } else if (t == 29) v = tk.rpy[2];
-      else if (t < 42) {
-        const int i = t - 30;
+      } else if (t == RL::YAW) v = tk.rpy[2];
+      else if (t < RL::AL) {
+        const int i = t - RL::WT;
         v = (i < 2) ? 100.0 : (i == 2 ? 250.0 : (i < 5 ? 200.0 : (i == 5 ? 300.0 : 1.0)));
-      } else if (t < 54) {
-        const int i = t - 42;
+      } else if (t < RL::NF) {
+        const int i = t - RL::AL;
         v = (i >= 6) ? 1e-2 : ((i == 2 || i == 5) ? 5e-4 : 1e-4);
       } else {
-        const int i = (t - 54) / 12, j = (t - 54) % 12;
+        const int i = (t - RL::NF) / 12, j = (t - RL::NF) % 12;
         // trajInitial (ConvexMPCLocomotion.cpp:351-362)
         double ti;
         switch (j) {
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void build_records_kernel(const hmpc_tick_inpu
       word = __float_as_uint((float)v);
     } else {
       // gait bytes (GaitGenerator.cpp:85-103), four per word
-      const int b0 = 4 * (t - 54 - ntraj);
+      const int b0 = 4 * (t - RL::NF - ntraj);
 #pragma unroll
       for (int bb = 0; bb < 4; ++bb) {
         const int gi = b0 + bb;
@@ -137,12 +138,7 @@ __global__ __launch_bounds__(256) void classify_records_kernel(const unsigned ch
                                                                float f_max, unsigned char *cls) {
   const int inst = blockIdx.x * blockDim.x + threadIdx.x;
   if (inst >= batch) return;
-  const unsigned char *g = records + (size_t)inst * stride + 4 * (54 + 12 * h);
-  int cnt = 0;
-  for (int i = 0; i < 2 * h; ++i) {
-    const float ubc = f_max * (float)g[i];
-    cnt += !(ubc < 0.0001 && ubc > -.0001);
-  }
+  const int cnt = rec_stance_count(records + (size_t)inst * stride, 2, h, f_max);
   cls[inst] = (unsigned char)(cnt > 255 ? 255 : cnt);
 }
 
@@ -156,10 +152,10 @@ __global__ __launch_bounds__(256) void classify_records_kernel(const unsigned ch
 // counting sort below uses in place of the previous solve's iteration count.
 __device__ __forceinline__ int predicted_cost_bucket(const unsigned char *rec, int h, int nc) {
   const float *f = reinterpret_cast<const float *>(rec);
-  const int nf = (nc == 3) ? 73 : 54;
-  const float vx = f[3], qw = f[6], qx = f[7], qy = f[8], qz = f[9];
-  const float mrx = 0.5f * (f[13] + f[14]);            // r_feet(axis, contact) = r[nc * axis + contact]: x of the two feet
-  const float vcmd = f[nf + 9];                        // reference trajectory, step 0, v_x (ConvexMPCLocomotion.cpp:330-406)
+  using RL = RecLayout<2>;  // (the fields read here lie before the first offset that depends on nc)
+  const float vx = f[RL::V], qw = f[RL::Q], qx = f[RL::Q + 1], qy = f[RL::Q + 2], qz = f[RL::Q + 3];
+  const float mrx = 0.5f * (f[RL::R] + f[RL::R + 1]);  // r_feet(axis, contact) = r[nc * axis + contact]: x of the two feet
+  const float vcmd = f[rec_fixed_floats(nc) + 9];      // reference trajectory, step 0, v_x (ConvexMPCLocomotion.cpp:330-406)
   const float sr = 2.0f * (qw * qx + qy * qz), sp = 2.0f * (qw * qy - qx * qz);  // ~ roll, pitch (their sines)
   const float u = (vcmd - vx) + 2.0f * mrx;
   const float score = (u > 0.0f ? u : -0.05f * u) + 0.5f * (fabsf(sr) + fabsf(sp));

@@ -19,6 +19,7 @@
 #include "../../include/hector_mpc.h"
 #include "hmpc_device_buffer.h"
 #include "hmpc_kernel_args.h"
+#include "hmpc_record.h"
 #include "hmpc_variants.h"
 #include "hmpc_builder.h"
 #include "hmpc_predict.h"
@@ -74,9 +75,6 @@ constexpr int MAX_VARS_ANY = 240;
 constexpr int DBG_FLOATS_MAX = hmpc::DbgLayout<240, 2>::TOTAL > hmpc::DbgLayout<180, 3>::TOTAL
                                    ? hmpc::DbgLayout<240, 2>::TOTAL
                                    : hmpc::DbgLayout<180, 3>::TOTAL;
-
-int fixed_floats(int nc) { return nc == 3 ? 73 : 54; }
-size_t record_stride(int h, int nc = 2) { return (size_t)(((fixed_floats(nc) + 12 * h) * 4 + nc * h + 15) / 16 * 16); }
 
 }  // namespace
 
@@ -505,8 +503,8 @@ extern "C" {
 const char *hmpc_last_hip_error(void) { return g_hip_err.c_str(); }
 const char *hmpc_version(void) { return "hector_mpc_hip 0.1 (gfx950)"; }
 
-size_t hmpc_record_stride(int horizon) { return record_stride(horizon); }
-size_t hmpc_record_stride_ex(int horizon, int n_contacts) { return record_stride(horizon, n_contacts == 3 ? 3 : 2); }
+size_t hmpc_record_stride(int horizon) { return (size_t)hmpc::rec_stride(2, horizon); }
+size_t hmpc_record_stride_ex(int horizon, int n_contacts) { return (size_t)hmpc::rec_stride(n_contacts == 3 ? 3 : 2, horizon); }
 
 int hmpc_pack_record_ex(void *record, int horizon, int n_contacts, const double *p, const double *v, const double *q,
                         const double *w, const double *r, const double *joint_angles, double yaw, const double *weights,
@@ -518,19 +516,8 @@ int hmpc_pack_record_ex(void *record, int horizon, int n_contacts, const double 
   if (!record || !p || !v || !q || !w || !r || !joint_angles || !weights || !state_trajectory || !Alpha_K || !gait || !Rhand)
     return HMPC_E_ARG;
   if (horizon < 1 || horizon > 10) return HMPC_E_HORIZON;
-  memset(record, 0, record_stride(horizon, 3));
-  float *f = (float *)record;
-  for (int i = 0; i < 3; ++i) f[0 + i] = (float)p[i], f[3 + i] = (float)v[i], f[10 + i] = (float)w[i];
-  for (int i = 0; i < 4; ++i) f[6 + i] = (float)q[i];
-  for (int i = 0; i < 9; ++i) f[13 + i] = (float)r[i], f[63 + i] = (float)Rhand[i];
-  for (int i = 0; i < 10; ++i) f[22 + i] = (float)joint_angles[i];
-  f[32] = (float)yaw;
-  for (int i = 0; i < 12; ++i) f[33 + i] = (float)weights[i];
-  for (int i = 0; i < 18; ++i) f[45 + i] = (float)Alpha_K[i];
-  f[72] = (float)f_max_hand;
-  for (int i = 0; i < 12 * horizon; ++i) f[73 + i] = (float)state_trajectory[i];
-  unsigned char *g = (unsigned char *)record + 4 * (73 + 12 * horizon);
-  for (int i = 0; i < 3 * horizon; ++i) g[i] = (unsigned char)gait[i];
+  hmpc::pack_record<3>(record, horizon, hmpc::RecSource<double, int>{p, v, q, w, r, joint_angles, yaw, weights, state_trajectory, Alpha_K,
+                                                                      gait, Rhand, f_max_hand});
   return HMPC_OK;
 }
 
@@ -540,17 +527,7 @@ int hmpc_pack_record(void *record, int horizon, const double *p, const double *v
   if (!record || !p || !v || !q || !w || !r || !joint_angles || !weights || !state_trajectory || !Alpha_K || !gait)
     return HMPC_E_ARG;
   if (horizon < 1 || horizon > HMPC_MAX_HORIZON) return HMPC_E_HORIZON;
-  memset(record, 0, record_stride(horizon));
-  float *f = (float *)record;
-  for (int i = 0; i < 3; ++i) f[0 + i] = (float)p[i], f[3 + i] = (float)v[i], f[10 + i] = (float)w[i];
-  for (int i = 0; i < 4; ++i) f[6 + i] = (float)q[i];
-  for (int i = 0; i < 6; ++i) f[13 + i] = (float)r[i];
-  for (int i = 0; i < 10; ++i) f[19 + i] = (float)joint_angles[i];
-  f[29] = (float)yaw;
-  for (int i = 0; i < 12; ++i) f[30 + i] = (float)weights[i], f[42 + i] = (float)Alpha_K[i];
-  for (int i = 0; i < 12 * horizon; ++i) f[54 + i] = (float)state_trajectory[i];
-  unsigned char *g = (unsigned char *)record + 4 * (54 + 12 * horizon);
-  for (int i = 0; i < 2 * horizon; ++i) g[i] = (unsigned char)gait[i];
+  hmpc::pack_record<2>(record, horizon, hmpc::RecSource<double, int>{p, v, q, w, r, joint_angles, yaw, weights, state_trajectory, Alpha_K, gait});
   return HMPC_OK;
 }
 
@@ -575,7 +552,7 @@ int hmpc_create_ex(hmpc_handle **out, const struct problem_setup *setup, int max
   h->max_batch = max_batch;
   h->device = device;
   h->nc = n_contacts;
-  h->stride = record_stride(setup->horizon, n_contacts);
+  h->stride = (size_t)hmpc::rec_stride(n_contacts, setup->horizon);
   hmpc_default_params(&h->params);
   const size_t mb = (size_t)max_batch, nf = mb * 6 * n_contacts * setup->horizon;
   const bool ok = h->d_record_store.alloc(mb * h->stride) == hipSuccess && h->d_forces.ensure(nf) == hipSuccess &&
@@ -627,17 +604,8 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
   const int hz = h->setup.horizon;
   int mx = 0;
   const unsigned char *rec = (const unsigned char *)host_records;
-  const int nc = h->nc, nfix = fixed_floats(nc);
   for (int b = 0; b < batch; ++b) {
-    const unsigned char *rb = rec + (size_t)b * pitch;
-    const unsigned char *g = rb + 4 * (nfix + 12 * hz);
-    float hand_cap = 0.f;
-    if (nc == 3) memcpy(&hand_cap, rb + 4 * 72, 4);
-    int cnt = 0;
-    for (int i = 0; i < nc * hz; ++i) {
-      float ub = ((i % nc) == 2 ? hand_cap : h->setup.f_max) * (float)g[i];
-      if (!(ub < 0.0001 && ub > -.0001)) ++cnt;
-    }
+    const int cnt = hmpc::rec_stance_count(rec + (size_t)b * pitch, h->nc, hz, h->setup.f_max);
     if (cnt > mx) mx = cnt;
   }
   replace_batch(h, h->d_record_store.get(), batch, 6 * mx, /*cls_valid=*/0);
@@ -1521,7 +1489,7 @@ void setup_problem(double dt, int horizon, double mu, double f_max) {
       g_setup_error = rc;
       return;
     }
-    g_pin_rec_bytes = (record_stride(horizon) + 63) & ~(size_t)63;
+    g_pin_rec_bytes = ((size_t)hmpc::rec_stride(2, horizon) + 63) & ~(size_t)63;
     const size_t out_bytes = sizeof(float) * 12 * horizon + sizeof(uint32_t);
     if (hipHostMalloc((void **)&g_pin, g_pin_rec_bytes + out_bytes, hipHostMallocDefault) != hipSuccess ||
         hipMalloc((void **)&g_dev_out, out_bytes) != hipSuccess ||
@@ -1548,14 +1516,8 @@ static void solve_global(void) {
   }
   const int hz = g_setup.horizon;
   unsigned char *rec = g_pin;
-  memset(rec, 0, record_stride(hz));
-  float *f = (float *)rec;
-  memcpy(f + 0, g_update.p, 12), memcpy(f + 3, g_update.v, 12), memcpy(f + 6, g_update.q, 16);
-  memcpy(f + 10, g_update.w, 12), memcpy(f + 13, g_update.r, 24), memcpy(f + 19, g_update.joint_angles, 40);
-  f[29] = g_update.yaw;
-  memcpy(f + 30, g_update.weights, 48), memcpy(f + 42, g_update.Alpha_K, 48);
-  memcpy(f + 54, g_update.traj, sizeof(float) * 12 * hz);
-  memcpy(rec + 4 * (54 + 12 * hz), g_update.gait, 2 * hz);
+  const update_data_t &u = g_update;
+  hmpc::pack_record<2>(rec, hz, hmpc::RecSource<float, unsigned char>{u.p, u.v, u.q, u.w, u.r, u.joint_angles, u.yaw, u.weights, u.traj, u.Alpha_K, u.gait});
   const float *forces = (const float *)(g_pin + g_pin_rec_bytes);
   const uint32_t *pst = (const uint32_t *)(forces + 12 * hz);
   const size_t out_bytes = sizeof(float) * 12 * hz + sizeof(uint32_t);

@@ -41,6 +41,7 @@
 #include "hmpc_math.h"
 
 #include "hmpc_kernel_args.h"
+#include "hmpc_record.h"  // RecLayout (RL:: below), stance()
 
 namespace hmpc {
 // per-phase shader-clock profile of developer builds (-DHMPC_PROFILE, scripts/phase_profile.py); an empty object otherwise
@@ -74,15 +75,6 @@ struct Prof {};
 
 namespace hmpc {
 
-// record field offsets in floats (hector_simulation_amd/records.py).  NC = 2 is the reference's update_data_t; NC = 3 is
-// the extension record with a hand contact (its frame Rhand and force cap travel in the record).
-template <int NC>
-struct RecLayout {
-  static constexpr int P = 0, V = 3, Q = 6, W = 10, R = 13, JA = R + 3 * NC, YAW = JA + 10, WT = YAW + 1, AL = WT + 12,
-                       RH = AL + 6 * NC, FMH = RH + 9, NF = (NC == 2) ? RH : FMH + 1;
-};
-
-
 constexpr int GS = 6;  // variables per stance leg-step: force (3) then moment (3)
 
 
@@ -102,7 +94,7 @@ struct Smem {
   static constexpr bool EGLOBAL = (QCAP == 0);  // (the one place that reads QCAP == 0: everything else asks EGLOBAL)
   static constexpr int QMAX = EGLOBAL ? NMAX : QCAP;
   static constexpr int EP_LDS = EGLOBAL ? 1 : QMAX * (QMAX + 1) / 2;
-  static constexpr int RECW = ((RecLayout<NC>::NF + 12 * HMAX) * 4 + NC * HMAX + 15) / 16 * 4;  // record words
+  static constexpr int RECW = rec_stride(NC, HMAX) / 4;  // record words
   static constexpr bool FULLBLK = (HMAX <= 10 && NMAX >= 120);  // staging layout of H (struct Asm)
   // FULLBLK staging passes: pass p holds the blocks of the block-diagonals d in [hs_dlo(p), hs_dlo(p+1))
   static constexpr int HSP = (NC == 3 && BPT == 2) ? 2 : 1;
@@ -1181,8 +1173,7 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
         int bits = 0, nst = 0;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          const float ubc = fz_cap(c) * (float)gait[NC * i + c];
-          const bool st = !(ubc < 0.0001 && ubc > -.0001);
+          const bool st = stance(fz_cap(c), gait[NC * i + c]);
           bits |= st ? (1 << c) : 0;
           nst += (int)st;
         }

@@ -1,6 +1,7 @@
 // hmpc_kernel_args.h -- what the host side needs to know of the fused kernel (hmpc_kernel.h): its argument block, the status
 // codes, the layout of the assembly debug dump, the roles a variant can have.  Kept apart from the 3 500-line kernel header so that the host translation
 // units (hmpc_capi.hip, hmpc_group.hip) compile in seconds and the kernel family builds in parallel (hmpc_variants.hip).
+// The record KernelArgs::records points at -- field offsets, sizes, the stance rule -- is defined in hmpc_record.h, for both sides.
 #pragma once
 #include <stdint.h>
 

@@ -19,6 +19,7 @@ workgroup fetches its instance with a single coalesced burst:
     then 2h bytes   gait         gait[2*step + leg], 1 = stance
 
 Record stride = (54 + 12h)*4 + 2h rounded up to 16 bytes (720 B at h = 10; 716 B of payload).
+The definition the library is compiled from is csrc/hmpc_record.h; tests/test_record_layout.py holds these tables and the packer to it.
 
 Extension record (``contacts=3``: two feet + one hand, BASELINE config 5 -- no reference code, include/hector_mpc.h):
 

@@ -56,6 +56,20 @@ def test_record_helpers_agree_with_python():
         assert rc == 0
         np.testing.assert_array_equal(buf, rec[k])
     assert L.hmpc_pack_record(None, 10, *([None] * 6), 0.0, *([None] * 4)) == -1
+    # the extension record: two feet and a hand, h = 10
+    assert L.hmpc_record_stride_ex(10, 3) == records.record_stride(10, 3)
+    f3 = synthetic.make_batch3(3, 10, "walking", seed=8, phase="random", hand="window")
+    rec3 = records.pack_records(f3, 10, contacts=3)
+    for k in range(3):
+        buf = np.zeros(records.record_stride(10, 3), dtype=np.uint8)
+        a64 = {key: np.ascontiguousarray(np.asarray(f3[key])[k], dtype=np.float64)
+               for key in ("p", "v", "q", "w", "r", "joint_angles", "weights", "traj", "Alpha_K", "Rhand")}
+        gait = np.ascontiguousarray(np.asarray(f3["gait"])[k], dtype=np.int32)
+        rc = L.hmpc_pack_record_ex(buf.ctypes.data, 10, 3, *[a64[key].ctypes.data for key in ("p", "v", "q", "w", "r", "joint_angles")],
+                                   float(f3["yaw"][k]), *[a64[key].ctypes.data for key in ("weights", "traj", "Alpha_K")],
+                                   gait.ctypes.data, a64["Rhand"].ctypes.data, float(np.asarray(f3["f_max_hand"])[k]))
+        assert rc == 0
+        np.testing.assert_array_equal(buf, rec3[k])
 
 
 def test_legacy_entry_points_do_not_throw():
@@ -133,7 +147,8 @@ def test_developer_switches_cannot_reach_the_product_library():
         os.environ.pop("HMPC_ALLOW_DEV_BUILD", None)
         if saved_env is not None:
             os.environ["HMPC_ALLOW_DEV_BUILD"] = saved_env
-    ksrc = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_kernel.h")).read()
+    csrc = os.path.join(ROOT, "hector_simulation_amd", "csrc")
+    ksrc = "".join(open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith(".h"))  # every header
     for gone in ("HMPC_MFS_NO_", "HMPC_MFS_ONLY_WAVE", "HMPC_DEV_TIMING", "HMPC_MFMA_SWEEP1", "HMPC_FLIP4", "HMPC_PIN_SWEEP", "HMPC_S0_ACTIVE_ROWS"):
         assert gone not in ksrc, gone
 

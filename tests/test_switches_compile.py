@@ -24,8 +24,9 @@ def _syntax_only(group: int, flags: list) -> subprocess.CompletedProcess:
 
 def test_the_switch_list_is_what_the_sources_have():
     macros = set()
-    for fn in ("hmpc_kernel.h", "hmpc_variants.h", "hmpc_kernel_args.h"):
-        txt = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", fn)).read()
+    csrc = os.path.dirname(SRC)
+    for fn in sorted(f for f in os.listdir(csrc) if f.endswith(".h")):  # every header: a new one cannot hide a switch
+        txt = open(os.path.join(csrc, fn)).read()
         macros |= set(re.findall(r"^#ifndef (HMPC_[A-Z0-9_]+)\n#define \1 ", txt, flags=re.M))
     macros -= {"HMPC_QCAP_CONT"}  # (the continuation variant's capacity: fixed by the hand-over layout, 96 = 6 tiles of 16 rows)
     assert macros == set(SWITCHES), (sorted(macros), sorted(SWITCHES))
