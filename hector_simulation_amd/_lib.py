@@ -29,6 +29,8 @@ EXPORTS = [
     "hmpc_predict_states", "hmpc_set_device_prediction", "hmpc_get_device_prediction", "hmpc_download_prediction",
     "hmpc_legacy_predicted_state",
     "hmpc_sweep_select", "hmpc_set_device_selection", "hmpc_get_device_selection", "hmpc_download_selection", "hmpc_tick_sweep_device",
+    "hmpc_constraint_margins", "hmpc_set_device_margins", "hmpc_get_device_margins", "hmpc_download_margins", "hmpc_margin_penalty",
+    "hmpc_set_sweep_margin_floor", "hmpc_legacy_constraint_slack",
 ]
 
 
@@ -192,6 +194,14 @@ def load():
     L.hmpc_get_device_selection.argtypes = [vp] + [C.POINTER(vp)] * 5 + [C.POINTER(ci)]
     L.hmpc_download_selection.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hmpc_tick_sweep_device.argtypes = [vp, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp]
+    L.hmpc_constraint_margins.argtypes = [vp, vp]
+    L.hmpc_set_device_margins.argtypes = [vp, vp, vp, vp]
+    L.hmpc_get_device_margins.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.hmpc_download_margins.argtypes = [vp, vp, vp, vp]
+    L.hmpc_margin_penalty.argtypes = [vp, vp, vp, vp, vp]
+    L.hmpc_set_sweep_margin_floor.argtypes = [vp, vp]
+    L.hmpc_legacy_constraint_slack.argtypes = [ci, ci, ci]
+    L.hmpc_legacy_constraint_slack.restype = cd
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

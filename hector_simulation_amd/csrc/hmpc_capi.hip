@@ -22,6 +22,7 @@
 #include "hmpc_record.h"
 #include "hmpc_variants.h"
 #include "hmpc_builder.h"
+#include "hmpc_margins.h"
 #include "hmpc_predict.h"
 #include "hmpc_select.h"
 
@@ -152,6 +153,15 @@ struct __attribute__((visibility("hidden"))) hmpc_handle {  // (opaque to caller
   OutputBuffer<float> d_sel_states;
   bool select_enqueued = false;  // ... and a selection behind that prediction (cleared wherever predict_enqueued is, and by every prediction)
   int select_groups = 0;         // groups of that selection
+  // constraint margins (hmpc_constraint_margins): slack [max_batch][horizon][nc][10] and summary [max_batch][6] binary64, where
+  // [max_batch][6], to the caller's buffers (hmpc_set_device_margins) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<double> d_mar_slack, d_mar_summary;
+  OutputBuffer<int32_t> d_mar_where;
+  bool margins_enqueued = false;  // margins of the last solve of the current batch have been enqueued (cleared wherever solve_enqueued changes)
+  // hmpc_set_sweep_margin_floor: hmpc_tick_sweep_device masks the commands whose margins miss the floor (penalty: scratch of the handle)
+  bool sweep_floor_on = false;
+  double sweep_floor[hmpc::MARGIN_CLASSES] = {};
+  DeviceBuffer<double> d_sweep_penalty;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 // longest-first dispatch (hmpc_set_dispatch_order, on by default): only where a launch has a tail to shorten -- more instances
@@ -370,7 +380,7 @@ static int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes
     const int rc = launch(h, stream, l[k].vi, o);
     if (rc != HMPC_OK) return rc;
   }
-  h->solve_enqueued = true, h->predict_enqueued = h->select_enqueued = false;  // (every solve of a batch starts here: hmpc_predict_states)
+  h->solve_enqueued = true, h->predict_enqueued = h->select_enqueued = h->margins_enqueued = false;  // (every solve of a batch starts here: hmpc_predict_states)
   return HMPC_OK;
 }
 
@@ -581,7 +591,7 @@ int hmpc_destroy(hmpc_handle *h) {
 static void replace_batch(hmpc_handle *h, const unsigned char *records, int batch, int max_stance, int cls_valid) {
   h->d_records = records;
   h->batch = batch;
-  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = false;
+  h->solve_enqueued = h->predict_enqueued = h->select_enqueued = h->margins_enqueued = false;
   h->max_stance = max_stance;
   h->cls_valid = cls_valid;
 }
@@ -1313,6 +1323,95 @@ int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Constraint margins: how far the forces of the last solve are from every limit the QP was solved under (hmpc_margins.hip).
+// ------------------------------------------------------------------------------------------------------------------
+struct MarginBuffers {
+  double *slack, *summary;
+  int32_t *where;
+};
+
+// where the next margins go: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int margin_buffers(hmpc_handle *h, MarginBuffers *b) {
+  const size_t mb = (size_t)h->max_batch;
+  HIP_TRY(h->d_mar_slack.ensure(mb * h->setup.horizon * h->nc * 10));
+  HIP_TRY(h->d_mar_summary.ensure(mb * hmpc::MARGIN_CLASSES));
+  HIP_TRY(h->d_mar_where.ensure(mb * hmpc::MARGIN_CLASSES));
+  *b = {h->d_mar_slack.get(), h->d_mar_summary.get(), h->d_mar_where.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_margins(hmpc_handle *h, double *device_slack, double *device_summary, int32_t *device_where) {
+  if (!h) return HMPC_E_ARG;
+  h->d_mar_slack.set_caller(device_slack), h->d_mar_summary.set_caller(device_summary), h->d_mar_where.set_caller(device_where);
+  h->margins_enqueued = false;  // (whatever was computed went elsewhere)
+  return HMPC_OK;
+}
+
+int hmpc_get_device_margins(hmpc_handle *h, double **device_slack, double **device_summary, int32_t **device_where) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  MarginBuffers b;
+  const int rc = margin_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_slack) *device_slack = b.slack;
+  if (device_summary) *device_summary = b.summary;
+  if (device_where) *device_where = b.where;
+  return HMPC_OK;
+}
+
+int hmpc_constraint_margins(hmpc_handle *h, void *stream) {
+  if (!h || !h->solve_enqueued) return HMPC_E_ARG;  // no solve of the current batch: the force buffer holds another batch's forces, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  MarginBuffers b;
+  const int rc = margin_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_margins(h->nc, a, b.slack, b.summary, b.where, (hipStream_t)stream));
+  h->margins_enqueued = true;
+  return HMPC_OK;
+}
+
+int hmpc_download_margins(hmpc_handle *h, double *slack, double *summary, int32_t *where) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->margins_enqueued) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  MarginBuffers b;
+  const int rc = margin_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch;
+  if (slack) HIP_TRY(hipMemcpy(slack, b.slack, n * h->setup.horizon * h->nc * 10 * sizeof(double), hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, n * hmpc::MARGIN_CLASSES * sizeof(double), hipMemcpyDeviceToHost));
+  if (where) HIP_TRY(hipMemcpy(where, b.where, n * hmpc::MARGIN_CLASSES * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+int hmpc_margin_penalty(hmpc_handle *h, const double floor[6], const double *device_penalty_in, double *device_penalty_out, void *stream) {
+  if (!h || !floor || !device_penalty_out) return HMPC_E_ARG;
+  if (!h->margins_enqueued) return HMPC_E_ARG;  // no margins of the last solve of this batch: the summary holds another solve's, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  MarginBuffers b;
+  const int rc = margin_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_margin_penalty(b.summary, floor, device_penalty_in, device_penalty_out, h->batch, (hipStream_t)stream));
+  return HMPC_OK;
+}
+
+int hmpc_set_sweep_margin_floor(hmpc_handle *h, const double floor[6]) {
+  if (!h) return HMPC_E_ARG;
+  h->sweep_floor_on = floor != nullptr;
+  for (int k = 0; k < hmpc::MARGIN_CLASSES; ++k) h->sweep_floor[k] = floor ? floor[k] : 0.0;
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {
@@ -1418,6 +1517,12 @@ int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks
   rc = hmpc_build_records_device(h, sp, batch, dtMPC, nullptr, stream);
   if (rc == HMPC_OK) rc = hmpc_solve_command_sweep(h, group_size, stream);
   if (rc == HMPC_OK) rc = hmpc_predict_states(h, stream);
+  if (rc == HMPC_OK && h->sweep_floor_on) {  // commands whose margins miss the floor are masked: margins, then the penalty into scratch of the handle
+    HIP_TRY(h->d_sweep_penalty.reserve((size_t)h->max_batch * sizeof(double), (hipStream_t)stream, /*whole_device=*/true));
+    rc = hmpc_constraint_margins(h, stream);
+    if (rc == HMPC_OK) rc = hmpc_margin_penalty(h, h->sweep_floor, device_penalty, h->d_sweep_penalty.get(), stream);
+    device_penalty = h->d_sweep_penalty.get();
+  }
   if (rc == HMPC_OK) rc = hmpc_sweep_select(h, group_size, device_penalty, stream);
   if (rc != HMPC_OK) return rc;
   SelectionBuffers b;
@@ -1445,6 +1550,8 @@ static int g_setup_error = 0;
 static hmpc_params g_legacy_params = {9.0f, {0.5413f, 0.5200f, 0.0691f}, 2.0f, 0.09f, 0.06f, 9.81f};  // hmpc_legacy_set_params
 static float g_pred[13 * HMPC_MAX_HORIZON];  // hmpc_legacy_predicted_state: the last solve's predicted states, fetched on first use
 static int g_pred_valid = 0;
+static double g_slack[10 * 2 * HMPC_MAX_HORIZON];  // hmpc_legacy_constraint_slack: the last solve's slacks, fetched on first use
+static int g_slack_valid = 0;
 static int g_legacy_iter_cap = 0;  // hmpc_legacy_set_max_iterations: explicit opt-in (update_solver_settings is inert, as in the reference)
 // one tick = one pinned staging buffer [record | 12h forces | status word] and one contiguous device output block, so that
 // a blocking tick costs one asynchronous H2D copy, one launch, one asynchronous D2H copy and a single synchronisation
@@ -1553,6 +1660,7 @@ static void solve_global(void) {
   for (int i = 0; i < 12 * hz; ++i) g_q_soln[i] = (double)forces[i];
   g_has_solved = 1;
   g_pred_valid = 0;
+  g_slack_valid = 0;
 }
 
 void update_problem_data(double *p, double *v, double *q, double *w, double *r, double *joint_angles, double yaw,
@@ -1589,6 +1697,21 @@ double hmpc_legacy_predicted_state(int step, int component) {
     g_pred_valid = 1;
   }
   return (double)g_pred[13 * step + component];
+}
+
+double hmpc_legacy_constraint_slack(int step, int contact, int j) {
+  if (!g_has_solved || !g_handle) return 0.0;  // as get_solution: 0 before the first solve and for out-of-range arguments
+  if (step < 0 || step >= g_setup.horizon || contact < 0 || contact >= 2 || j < 0 || j >= 10) return 0.0;
+  if (!g_slack_valid) {  // once per solve, on first use: one launch and one small copy
+    int rc = hmpc_constraint_margins(g_handle, nullptr);
+    if (rc == HMPC_OK) rc = hmpc_download_margins(g_handle, g_slack, nullptr, nullptr);
+    if (rc != HMPC_OK) {
+      fprintf(stderr, "[hector_mpc_hip] constraint margins failed (%d): %s\n", rc, hmpc_last_hip_error());
+      return 0.0;
+    }
+    g_slack_valid = 1;
+  }
+  return g_slack[10 * (2 * step + contact) + j];
 }
 
 void update_solver_settings(int max_iter, double rho, double sigma, double solver_alpha, double terminate,

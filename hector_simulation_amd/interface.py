@@ -68,6 +68,12 @@ def legacy_predicted_state(step: int, component: int) -> float:
     return float(_lib.load().hmpc_legacy_predicted_state(int(step), int(component)))
 
 
+def legacy_constraint_slack(step: int, contact: int, j: int) -> float:
+    """Slack ``j`` (0..9) of ``contact`` (0, 1) at ``step`` (0..horizon-1) of the process-global solver's last solution
+    (include/hector_mpc.h hmpc_legacy_constraint_slack); 0 before the first solve and for out-of-range arguments."""
+    return float(_lib.load().hmpc_legacy_constraint_slack(int(step), int(contact), int(j)))
+
+
 def last_status() -> int:
     return int(_lib.load().hmpc_last_status())
 
@@ -290,6 +296,41 @@ class BatchedMPC:
                                              float(dt_mpc), C.c_void_p(int(penalty_ptr or 0)), C.c_void_p(int(wpd_ptr or 0)),
                                              C.c_void_p(int(f_ff_ptr or 0)), C.c_void_p(tau_ptr), C.c_void_p(stream)),
                "hmpc_tick_sweep_device")
+
+    def constraint_margins(self, stream: int = 0) -> None:
+        """One launch behind the solve on ``stream``: the slack of every constraint row under the forces in the force buffer and the six
+        per-instance minima (include/hector_mpc.h hmpc_constraint_margins).  Raises when no solve of the current batch has been enqueued."""
+        _check(self.L.hmpc_constraint_margins(self.h, C.c_void_p(stream)), "hmpc_constraint_margins")
+
+    def download_margins(self) -> dict:
+        """slack float64[batch, horizon, contacts, 10] (+inf for swing leg-steps), summary float64[batch, 6] and where int32[batch, 6]
+        (-1 = no candidate).  Waits; runs no safe pass."""
+        b = self.batch
+        out = dict(slack=np.zeros((b, self.horizon, self.contacts, 10), dtype=np.float64), summary=np.zeros((b, 6), dtype=np.float64),
+                   where=np.zeros((b, 6), dtype=np.int32))
+        _check(self.L.hmpc_download_margins(self.h, *[out[k].ctypes.data for k in ("slack", "summary", "where")]), "hmpc_download_margins")
+        return out
+
+    def set_device_margins(self, slack_ptr: int = 0, summary_ptr: int = 0, where_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later margins (float64[max_batch, horizon, contacts, 10], float64[max_batch, 6],
+        int32[max_batch, 6]; 0 / None = the handle's own)."""
+        self._keep_mar = keepalive
+        _check(self.L.hmpc_set_device_margins(self.h, *[C.c_void_p(int(p or 0)) for p in (slack_ptr, summary_ptr, where_ptr)]),
+               "hmpc_set_device_margins")
+
+    def margin_penalty(self, floor, out_ptr: int, penalty_in_ptr: int = 0, stream: int = 0) -> None:
+        """out[i] = +inf where some summary[i, k] >= floor[k] is false (NaN floor entries are not tested), else penalty_in[i] or 0: a
+        ``penalty_ptr`` of ``sweep_select``.  ``out_ptr``, ``penalty_in_ptr``: float64[batch] in HBM (may be the same)."""
+        fl = np.ascontiguousarray(floor, dtype=np.float64)
+        assert fl.shape == (6,)
+        _check(self.L.hmpc_margin_penalty(self.h, fl.ctypes.data, C.c_void_p(int(penalty_in_ptr or 0)), C.c_void_p(int(out_ptr or 0)),
+                                          C.c_void_p(stream)), "hmpc_margin_penalty")
+
+    def set_sweep_margin_floor(self, floor=None) -> None:
+        """floor[6] for ``tick_sweep_device`` (commands whose margins miss it are masked); None = off, the default."""
+        fl = None if floor is None else np.ascontiguousarray(floor, dtype=np.float64)
+        assert fl is None or fl.shape == (6,)
+        _check(self.L.hmpc_set_sweep_margin_floor(self.h, None if fl is None else fl.ctypes.data), "hmpc_set_sweep_margin_floor")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

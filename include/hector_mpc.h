@@ -410,6 +410,57 @@ int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost);
  * `step` (0..horizon-1: x_{step+1}) under the last solution.  Predicts lazily, once per solve, on first use (one launch, one
  * copy).  0 before the first solve and for out-of-range arguments, as get_solution. */
 double hmpc_legacy_predicted_state(int step, int component);
+/* ---- the constraint margins of every solved instance ----
+ * How far the forces in the force buffer are from each limit the QP was solved under.  Per instance, with NC contacts, U = 6 NC,
+ * Fc[8 NC][U] THE binary32 constraint block the solve kernel assembles for the record (hmpc_params and hmpc_set_instance_mu included;
+ * the margins kernel calls the solve kernel's own assembly stage) and u_i[U] step i of the handle's force buffer as it stands:
+ *   c_{i,r} = sum_{k<U} Fc[r][k] u_i[k],   r = 8 c + j: row j of contact c,
+ * evaluated in binary64 as one ascending chain of fused multiply-adds started at +0 (every term, the structural zeros too).
+ * Contact c is in stance at step i by the rule that sizes the QP: ub7 = fl32(cap_c * (float)gait[NC i + c]) is not within 1e-4 of
+ * zero (cap_c = f_max for the feet, the record's own cap for the hand).  Ten one-sided slacks per leg-step, >= 0 when the limit holds:
+ *   slack[batch][h][NC][10]  binary64
+ *     [0..3]  c_{8c+0..3}                                friction pyramid (Fz -+ mu Fx, Fz -+ mu Fy >= 0)
+ *     [4]     c_{8c+4}                                   Mx >= 0
+ *     [5]     (double)0.01f - c_{8c+4}                   Mx <= 0.01
+ *     [6],[7] 0.0 - c_{8c+5},  0.0 - c_{8c+6}            line contact: toe, heel (<= 0)
+ *     [8]     c_{8c+7}                                   Fz floor (the row is 2 Fz >= 0)
+ *     [9]     (double)ub7 - c_{8c+7}                     Fz cap
+ *   All ten are +inf for a swing leg-step: its variables were eliminated, these rows are no constraints of the QP.
+ *   summary[batch][6] binary64, where[batch][6] int32: per class the lexicographic (value, index) minimum over the stance leg-steps,
+ *   index = 10 NC i + 10 c + j'.  A candidate replaces the incumbent iff its value is < the incumbent's, or == with a lower index, so
+ *   a NaN never enters and the result does not depend on the order of the reduction.  No candidate: +inf and where = -1.
+ *     [0] friction        j' 0..3          [1] Mx            j' 4, 5          [2] line contact   j' 6, 7
+ *     [3] Fz floor        j' 8             [4] Fz cap        j' 9
+ *     [5] friction headroom fraction: per stance leg-step with slack[8] > 0, m / (0.5 * slack[8]) (one IEEE division), m = the least
+ *         of slack[0..3] by <, started at +inf; index = 10 NC i + 10 c.  1 = no tangential force, 0 = on the pyramid.
+ * The result is a pure function of (record, hmpc_params, per-instance mu, force buffer).  An instance whose status word is not
+ * HMPC_S_OK / HMPC_S_OK_RELAXED is computed all the same, from whatever its slot of the force buffer holds: check the status words.
+ * After hmpc_debug_solve_external_qp the margins are still against the handle's OWN assembly of the record, not the block handed in.
+ *
+ * hmpc_constraint_margins enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.
+ * It reads the forces where the solve wrote them (hmpc_set_device_outputs is honoured) and needs no prediction.  HMPC_E_ARG, nothing
+ * enqueued, when no solve has been enqueued since the current batch was set (the rule of hmpc_predict_states).
+ * hmpc_set_device_margins: caller-owned device buffers for later margins (any may be NULL = the handle's own, allocated for max_batch
+ * by the first call that needs them; never inside hmpc_solve).  hmpc_get_device_margins: where the next margins go; any pointer may be
+ * NULL.  hmpc_download_margins waits for the stream of the last call, then copies (any pointer may be NULL); HMPC_E_ARG when nothing
+ * has been computed since the last solve of the current batch.  It does NOT run the safe pass.
+ * hmpc_margin_penalty enqueues one launch: device_penalty_out[i] = +inf if for some k with a non-NaN floor[k] the test
+ * summary[i][k] >= floor[k] is false (a NaN summary therefore masks), else device_penalty_in[i] (+0.0 when device_penalty_in is NULL).
+ * In-place is allowed.  The output is a device_penalty of hmpc_sweep_select.  HMPC_E_ARG without margins of the last solve.
+ * hmpc_set_sweep_margin_floor: floor[6] for hmpc_tick_sweep_device, NULL = off (the default).  When set, the tick enqueues the
+ * margins and the penalty between its prediction and its selection; the penalty goes to scratch of the handle and the caller's
+ * device_penalty is its device_penalty_in.  When off the tick enqueues exactly the launches it did without.
+ * Device groups: per member, through hmpc_group_member. */
+int hmpc_constraint_margins(hmpc_handle *h, void *stream);
+int hmpc_set_device_margins(hmpc_handle *h, double *device_slack, double *device_summary, int32_t *device_where);
+int hmpc_get_device_margins(hmpc_handle *h, double **device_slack, double **device_summary, int32_t **device_where);
+int hmpc_download_margins(hmpc_handle *h, double *slack, double *summary, int32_t *where);
+int hmpc_margin_penalty(hmpc_handle *h, const double floor[6], const double *device_penalty_in, double *device_penalty_out, void *stream);
+int hmpc_set_sweep_margin_floor(hmpc_handle *h, const double floor[6]);
+/* ... of the process-global solver behind setup_problem / update_problem_data: slack j (0..9) of `contact` (0, 1) at `step`
+ * (0..horizon-1) under the last solution.  Computed lazily, once per solve, on first use (one launch, one copy).  0 before the first
+ * solve and for out-of-range arguments, as get_solution. */
+double hmpc_legacy_constraint_slack(int step, int contact, int j);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size
