@@ -42,6 +42,7 @@
 
 #include "hmpc_kernel_args.h"
 #include "hmpc_record.h"  // RecLayout (RL:: below), stance()
+#include "hmpc_schur_tiles.h"  // the deal of the tiles to the waves (mfs_owner, MfsTiles); index arithmetic of the Schur tiles
 
 namespace hmpc {
 // per-phase shader-clock profile of developer builds (-DHMPC_PROFILE, scripts/phase_profile.py); an empty object otherwise
@@ -437,79 +438,9 @@ __device__ __forceinline__ LazyInt<LAZY, F> lazy_int(F f) {
 // 203 k cycles against 265 k for the scalar sweeps there.
 typedef double hmpc_d4 __attribute__((ext_vector_type(4)));
 
-// tile t (block-row-major over I <= J of the NTG x NTG grid of 16 x 16 tiles) -> I, J
-constexpr int mfs_tile_i(int t, int ntg) {
-  int i = 0, base = 0;
-  while (t >= base + (ntg - i)) base += ntg - i, ++i;
-  return i;
-}
-constexpr int mfs_tile_j(int t, int ntg) {
-  int i = 0, base = 0;
-  while (t >= base + (ntg - i)) base += ntg - i, ++i;
-  return i + (t - base);
-}
-// Which wave holds tile (I, J).  By default the NTG (NTG + 1) / 2 tiles are dealt in contiguous runs of the block-row-major
-// order (a wave then needs few distinct A operands: one per tile row it touches).  The 12 x 12 grid on four waves (180
-// variables, two leg-step blocks per thread) is dealt by hand instead: there the 160 accumulator registers and the 144
-// registers of the two blocks have to pass each other in the register file when M is handed over chunk by chunk
-// (mfs_relayout), and what bounds the peak is how many of a wave's tiles are still unstored when its blocks are born -- a
-// thread's slot-0 block lies in row chunk 0 (wave 3: 0-1), its slot-1 block in chunk 1 / 1-2 / 2-3 / 3 for waves 0..3.  With
-// tiles per row chunk (9, 7, 4, 0), (8, 8, 4, 0), (8, 5, 3, 3), (8, 4, 4, 3) for waves 0..3 no wave holds more than 176 registers
-// of matrix at any time (contiguous runs: 232, and the allocator spills); every wave owns three diagonal tiles.
-constexpr int mfs_owner(int ntg, int nwv, int I, int J) {
-  if (ntg == 12 && nwv == 4) {
-    switch (I) {
-      case 0: return J <= 8 ? 0 : 1;
-      case 1: return J <= 5 ? 1 : 2;
-      case 2: return J <= 3 ? 2 : 3;
-      case 3: return J <= 9 ? 0 : 1;
-      case 4: return J <= 9 ? 1 : 2;
-      case 5: return J <= 7 ? 2 : 3;
-      case 6: return J <= 9 ? 0 : 1;
-      case 7: return J <= 8 ? 1 : 2;
-      case 8: return 3;
-      case 9: return 2;
-      default: return 3;
-    }
-  }
-  // 8 x 8 grid on four waves (120 variables): tile rows dealt in pairs I, 7 - I (8 + 1, 7 + 2, 6 + 3, 5 + 4 tiles): every wave
-  // touches exactly two tile rows (two A operands per step instead of up to four) and owns two diagonal tiles
-  if (ntg == 8 && nwv == 4) return I < 4 ? I : 7 - I;
-  const int ntiles = ntg * (ntg + 1) / 2, base = ntiles / nwv, rem = ntiles % nwv;
-  int t = 0;  // index of (I, J) in block-row-major order
-  for (int i = 0; i < I; ++i) t += ntg - i;
-  t += J - I;
-  int w = 0, first = 0;
-  while (w < nwv - 1 && t >= first + base + (w < rem ? 1 : 0)) first += base + (w < rem ? 1 : 0), ++w;
-  return w;
-}
-constexpr int mfs_count(int ntg, int nwv, int wv) {
-  int c = 0;
-  for (int i = 0; i < ntg; ++i)
-    for (int j = i; j < ntg; ++j) c += (mfs_owner(ntg, nwv, i, j) == wv) ? 1 : 0;
-  return c;
-}
-template <int NTG, int NWV>
-struct MfsGrid {
-  static constexpr int NTILES = NTG * (NTG + 1) / 2;
-  static constexpr int TPW = (NTILES + NWV - 1) / NWV;  // accumulator tiles per wave (some waves may hold one less)
-};
+// (which wave holds which tile: mfs_owner, mfs_count, MfsGrid, MfsTiles of hmpc_schur_tiles.h)
 template <int NTG, int NWV>
 using MfsAcc = hmpc_d4[MfsGrid<NTG, NWV>::TPW];  // a wave's accumulator tiles
-template <int NTG, int NWV, int WV>
-struct MfsTiles {  // the wave's tiles, sorted by (I, J)
-  static constexpr int TPW = MfsGrid<NTG, NWV>::TPW;
-  int cnt;
-  int i[TPW], j[TPW];
-  constexpr MfsTiles() : cnt(0), i{}, j{} {
-    for (int ii = 0; ii < NTG; ++ii)
-      for (int jj = ii; jj < NTG; ++jj)
-        if (mfs_owner(NTG, NWV, ii, jj) == WV) i[cnt] = ii, j[cnt] = jj, ++cnt;
-    for (int t = cnt; t < TPW; ++t) i[t] = i[cnt - 1], j[t] = j[cnt - 1];  // (a slot beyond the wave's count is never used)
-  }
-};
-static_assert(mfs_count(12, 4, 0) == 20 && mfs_count(12, 4, 1) == 20 && mfs_count(12, 4, 2) == 19 && mfs_count(12, 4, 3) == 19, "12 x 12 deal");
-static_assert(mfs_count(8, 4, 0) == 9 && mfs_count(8, 4, 3) == 9, "8 x 8 deal");
 template <int NTG>
 struct MfsPanel {
   // panel row stride in doubles.  Round 4 used 16 NTG + 16 (= 0 mod 32 banks): the four rows of a B-operand read hit different
@@ -698,6 +629,14 @@ __device__ __forceinline__ void mfs_load_parked(MfsAcc<NTG, NWV> &acc, const int
 
 // The NTG * 4 block-pivot steps on the tiles in acc (code specialised per wave).  Callers: a barrier between the last read
 // of whatever PN aliases and this call.
+// CHECK = true (the Schur matrix of the block start, n = k0 rows of a 16 NTG grid): a tile (I, J) with 16 J >= n is DEAD -- identity
+// padding from load to store -- and takes no part: not published, no operand fetched, no matrix instruction (schur_tile_live: one
+// scalar compare per tile, tile coordinates stay compile-time; a wave whose tiles are all dead only meets the barriers).  The live
+// tiles keep every bit: (a) the ceil(n / 4) steps end before the first dead tile row, so a dead column is never a pivot and the
+// pivot's own tile is live; (b) the panel entries of a dead column are exact zeros (identity padding off the diagonal, never
+// updated by anything but products with such zeros), so the update acc -= Q' 0 of a dead tile changes nothing; (c) nothing reads
+// a dead column of the panel -- the B operand of column J goes to tiles (., J) only, the A operand of row I to tiles (I, .), and
+// J live implies I live -- and schur_store never writes a column >= n.  CHECK = false (stage S): every tile is live, compile time.
 template <int NTG, int NWV, int WV, bool CHECK = false>
 __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &acc, const int n) {
   constexpr MfsTiles<NTG, NWV, WV> T;
@@ -707,6 +646,10 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
   auto pick = [&](const hmpc_d4 &v, int rr) __attribute__((always_inline)) -> double {  // rr uniform
     const double lo = (rr & 1) ? v[1] : v[0], hi = (rr & 1) ? v[3] : v[2];
     return (rr & 2) ? hi : lo;
+  };
+  auto live = [&](const int t) __attribute__((always_inline)) -> bool {  // (uniform; stage S: true at compile time)
+    if constexpr (CHECK) return schur_tile_live(T.j[t], n);
+    else return true;
   };
   auto rcp1 = [](double d) __attribute__((always_inline)) -> double {  // v_rcp_f64 (2^-24) + Newton steps (two: last bit; one: 2e-15)
     double r = __builtin_amdgcn_rcp(d);
@@ -756,6 +699,7 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
       double(*P)[PST] = PN.P[s & 1];
 #pragma unroll
       for (int t = 0; t < CNT; ++t) {
+        if (!live(t)) continue;
         if (T.i[t] == IK) {  // compile time
           double v = pick(acc[t], rr);
           if (T.j[t] == IK) {
@@ -802,6 +746,22 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
     const double(*P)[PST] = PN.P[s & 1];
     const double x0 = PN.Dinv[s & 1][g][0], x1 = PN.Dinv[s & 1][g][1], x2 = PN.Dinv[s & 1][g][2], x3 = PN.Dinv[s & 1][g][3];
     // tile(I,J) -= Q_I' P_J, Q = D^-1 P: A operand -Q[g][16 I + c], B operand P[g][16 J + c].
+    if constexpr (CHECK) {
+      // live tiles only, tile by tile behind one scalar branch each (the operand pipeline below, with a test per tile in it, keeps its
+      // double buffers alive across the branches: +10 VGPRs on the continuation variant).  The wave's tiles are sorted by (I, J): in a tile
+      // row the tiles before a live one are live, so the row's A operand is formed with the row's first tile.
+      double alast = 0.0;
+#pragma unroll
+      for (int t = 0; t < CNT; ++t) {
+        if (!live(t)) continue;
+        const double bo = P[g][16 * T.j[t] + c];
+        if (t == 0 || T.i[t] != T.i[t - 1]) {  // compile time
+          const int m = 16 * T.i[t] + c;
+          alast = -dfma(x3, P[3][m], dfma(x2, P[2][m], dfma(x1, P[1][m], x0 * P[0][m])));
+        }
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(alast, bo, acc[t], 0, 0, 0);
+      }
+    } else {
     // groups of GT tiles, the operands of group k+1 read while the matrix instructions of group k run
     constexpr int GT = (TPW % 3 == 0) ? 3 : (TPW < MFS_GT ? TPW : MFS_GT), NGRP = (CNT + GT - 1) / GT;
     double aop[2][GT], bop[2][GT];
@@ -829,6 +789,7 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
         const int t = grp * GT + u;
         if (t < CNT) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[grp & 1][u], bop[grp & 1][u], acc[t], 0, 0, 0);
       }
+    }
     }
 #pragma unroll
     for (int t = 0; t < CNT; ++t)
@@ -991,48 +952,75 @@ __device__ __forceinline__ void schur_scale_exponents(const int k0, const double
     kexp[tid] = (signed char)k;
   }
 }
+// Tiles of S0 from the packed triangle, code specialised per wave.  Everything that says WHERE an entry lies and WHETHER it is
+// data comes from lane constants formed once per call plus compile-time constants (hmpc_schur_tiles.h; checked on the host
+// against the per-entry expressions by tests/test_schur_tile_index.py): tri(j) once per tile column, tri(i) only in the diagonal
+// tiles (whose lower half reads the mirror), one validity bit per tile column and one per (tile row, r).  The scaling exponents
+// come straight from the diagonal of S0 (what schur_scale_exponents leaves in kexp for the store at the end: no barrier between
+// that pass and this one), one per tile column and one per (tile row, r), shared by the tiles of a row.  Identity padding is a
+// select on the loaded value, then ONE scaling by 2^(k_i + k_j): the same bits as the multiplication by that power of two.
+// A padding entry reads its nominal address, which lies inside the triangle (16 NTG <= QMAX rows) and is replaced before use.
+// Dead tiles (schur_tile_live) are not loaded: nothing reads their accumulators (mfs_steps<.., CHECK = true>, schur_store).
+// (Round 5 had a min / max, a compare, hi (hi + 1) / 2 + lo, an LDS read of the diagonal with its exponent, a scale factor and
+// two 64-bit selects PER ENTRY: ~27 VALU instructions each, 440 per wave and round.)
 template <int NTG, int NWV, int WV>
 __device__ __forceinline__ void schur_load(MfsAcc<NTG, NWV> &acc, const int k0, const double *Ep, const signed char *kexp) {
   constexpr MfsTiles<NTG, NWV, WV> T;
   constexpr int CNT = mfs_count(NTG, NWV, WV);
-  const int ln = threadIdx.x & 63, g = ln >> 4, c = ln & 15;
-  // the scaling exponents straight from the diagonal of S0 (what schur_scale_exponents leaves in kexp for the store at the end):
-  // no barrier between that pass and this one
-  auto kof = [&](const int i) __attribute__((always_inline)) -> int {
-    if (i >= k0) return 0;
-    const int ex = ((__double2hiint(Ep[(unsigned)(i * (i + 1) / 2 + i)]) >> 20) & 2047) - 1023;
-    return -(ex >> 1);
-  };
+  const SchurLane L = schur_lane(threadIdx.x & 63);
   (void)kexp;
+  int kr[4] = {0, 0, 0, 0}, rt[4] = {0, 0, 0, 0};
+  bool rv[4] = {false, false, false, false};
 #pragma unroll
   for (int t = 0; t < CNT; ++t) {
-    const int j = 16 * T.j[t] + c;
-    const int kj = kof(j);
+    if (!schur_tile_live(T.j[t], k0)) continue;  // uniform
+    const int I = T.i[t], J = T.j[t];             // compile time
+    const int ct = schur_col_tri(L, J);
+    const bool cv = schur_col_valid(L, J, k0);
+    const int kc = schur_exponent(__double2hiint(Ep[(unsigned)(ct + 16 * J + L.c)]), cv);
+    if (t == 0 || I != T.i[t - 1]) {  // compile time: a new tile row (the wave's tiles are sorted by (I, J): in a row, the tiles before a live one are live)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        rt[r] = schur_row_tri(L, I, r);
+        rv[r] = schur_row_valid(L, I, r, k0);
+        kr[r] = schur_exponent(__double2hiint(Ep[(unsigned)(rt[r] + 16 * I + 4 * r + L.g)]), rv[r]);
+      }
+    }
+    double v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = Ep[(unsigned)schur_offset(L, I, J, r, ct, rt[r])];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = 16 * T.i[t] + g + 4 * r;
-      const int lo = i < j ? i : j, hi = i < j ? j : i;
-      const bool valid = hi < k0;
-      const double v = Ep[(unsigned)(valid ? hi * (hi + 1) / 2 + lo : 0)];
-      acc[t][r] = valid ? v * __hiloint2double((1023 + kof(i) + kj) << 20, 0) : ((i == j) ? 1.0 : 0.0);  // identity padding
+      const double pad = schur_on_diagonal(L, I, J, r) ? 1.0 : 0.0;  // identity padding
+      acc[t][r] = ldexp(schur_load_valid(I, J, cv, rv[r]) ? v[r] : pad, kr[r] + kc);
     }
   }
 }
-// E = S0^-1 = -A (scaling undone) back into the packed triangle (callers: a barrier before E is read)
+// E = S0^-1 = -A (scaling undone) back into the packed triangle (callers: a barrier before E is read): the same lane constants,
+// the exponents from kexp (the diagonal of S0 is long overwritten), one mask per tile column (j < k0; the diagonal tiles add
+// i <= j) with the tile's stores as a run under it.  Dead tiles store nothing.
 template <int NTG, int NWV, int WV>
 __device__ __forceinline__ void schur_store(const MfsAcc<NTG, NWV> &acc, const int k0, double *Ep, const signed char *kexp) {
   constexpr MfsTiles<NTG, NWV, WV> T;
   constexpr int CNT = mfs_count(NTG, NWV, WV);
-  const int ln = threadIdx.x & 63, g = ln >> 4, c = ln & 15;
+  const SchurLane L = schur_lane(threadIdx.x & 63);
+  int kr[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int t = 0; t < CNT; ++t) {
-    const int j = 16 * T.j[t] + c;
-    const int kj = (int)kexp[j];
+    if (!schur_tile_live(T.j[t], k0)) continue;  // uniform
+    const int I = T.i[t], J = T.j[t];             // compile time
+    const int ct = schur_col_tri(L, J);
+    const int kc = (int)kexp[16 * J + L.c];
+    if (t == 0 || I != T.i[t - 1]) {  // compile time
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * T.i[t] + g + 4 * r;
-      if (i <= j && j < k0)  // (upper triangle of the tile grid: i <= j always holds off the diagonal tiles)
-        Ep[(unsigned)(j * (j + 1) / 2 + i)] = -acc[t][r] * __hiloint2double((1023 + (int)kexp[i] + kj) << 20, 0);
+      for (int r = 0; r < 4; ++r) kr[r] = (int)kexp[16 * I + 4 * r + L.g];
+    }
+    if (schur_col_valid(L, J, k0)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double e = ldexp(-acc[t][r], kr[r] + kc);
+        if (schur_store_valid(L, I, J, r, true)) Ep[(unsigned)schur_offset_upper(L, I, r, ct)] = e;  // (off the diagonal tiles: compile-time true)
+      }
     }
   }
 }
