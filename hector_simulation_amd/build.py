@@ -1,7 +1,7 @@
 """In-tree build of libhector_mpc_hip.so (hipcc, gfx950 only; cross-compiles without a GPU).
 
 The kernel family is compiled as HMPC_VARIANT_GROUPS translation units side by side (csrc/hmpc_variants.hip with
--DHMPC_VARIANT_GROUP=k) next to the two host-side ones, the prediction kernel (csrc/hmpc_predict.hip), the selection kernels (csrc/hmpc_select.hip) and the margins kernels (csrc/hmpc_margins.hip), then linked: ~25 s instead of the 60 s of one serial unit.
+-DHMPC_VARIANT_GROUP=k) next to the units of HOST_SOURCES, then linked: ~25 s instead of the 60 s of one serial unit.
 Staleness is decided by a content hash of the sources (kept next to the library), not by mtimes -- a snapshot copied to
 another box keeps the prebuilt library valid -- and builds are serialised by a file lock so that N ranks started by
 torchrun never compile into the same file at once."""
@@ -19,7 +19,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhector_mpc_hip.so")
 VARIANT_GROUPS = 4  # = HMPC_VARIANT_GROUPS of csrc/hmpc_variants.h
-HOST_SOURCES = ["hmpc_capi.hip", "hmpc_group.hip", "hmpc_predict.hip", "hmpc_select.hip", "hmpc_margins.hip"]  # (hmpc_predict.hip, hmpc_select.hip, hmpc_margins.hip: the prediction, selection and margins kernels, units of their own)
+# the units of the library besides the kernel family: the batched C ABI, what a solve launches, the reference's interface, device groups,
+# and the units that compile the kernels launched around a solve (builder, prediction, selection, margins).  THE list: compile_commands
+# and every script that builds the library by hand (scripts/sanitize_host.sh) take the units from here.
+HOST_SOURCES = ["hmpc_capi.hip", "hmpc_launch.hip", "hmpc_legacy.hip", "hmpc_group.hip", "hmpc_builder.hip", "hmpc_predict.hip",
+                "hmpc_select.hip", "hmpc_margins.hip"]
 # every header and unit of csrc/, so that a new header can never be left out of the staleness hash
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join("..", "..", "include", "hector_mpc.h")]
 # -ffp-contract=off is part of the numerical contract (HMPC-A1): every fused multiply-add in the source is explicit

@@ -1,4 +1,4 @@
-// hmpc_device_buffer.h -- the two owner types of the device memory a handle holds (hmpc_capi.hip).  Errors come back as hipError_t: what
+// hmpc_device_buffer.h -- the two owner types of the device memory a handle holds (hmpc_handle.h).  Errors come back as hipError_t: what
 // to make of one (HIP_TRY, the error text) is the caller's business.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,143 @@
+// hmpc_handle.h -- what the host units of libhector_mpc_hip.so share and nobody outside sees: the handle, the error string, the options
+// of one launch, and what hmpc_launch.hip (what a solve enqueues) offers hmpc_capi.hip (the batched C ABI).  Everything here is hidden.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "../../include/hector_mpc.h"
+#include "hmpc_device_buffer.h"
+#include "hmpc_kernel_args.h"
+#include "hmpc_margins.h"
+#include "hmpc_plan.h"
+
+#pragma GCC visibility push(hidden)
+
+std::string &hip_error_text();  // what hmpc_last_hip_error reports: per thread (hmpc_launch.hip)
+
+#define HIP_TRY(expr)                                                                                    \
+  do {                                                                                                   \
+    hipError_t _e = (expr);                                                                              \
+    if (_e != hipSuccess) {                                                                              \
+      hip_error_text() = std::string(#expr) + ": " + hipGetErrorString(_e);                              \
+      return HMPC_E_HIP;                                                                                 \
+    }                                                                                                    \
+  } while (0)
+
+struct hmpc_handle {  // (opaque to callers: its constructor and destructor are not exported)
+  problem_setup setup{};
+  int nc = 2;  // contacts per horizon step: 2 (reference) or 3 (hand-contact extension)
+  int max_batch = 0, device = 0, batch = 0;
+  size_t stride = 0;
+  DeviceBuffer<unsigned char> d_record_store;    // the handle's own records (uploads, the record builder)
+  const unsigned char *d_records = nullptr;      // the current batch's: d_record_store, or the caller's (hmpc_set_device_records)
+  OutputBuffer<float> d_forces;                  // the caller's, hmpc_set_device_outputs, else the handle's own (allocated at create)
+  OutputBuffer<uint32_t> d_status;
+  DeviceBuffer<double> d_x64, d_obj64;
+  DeviceBuffer<float> d_dbg_f;
+  DeviceBuffer<int> d_dbg_i;
+  DeviceBuffer<long long> d_prof;
+  int warm = 1;    // block warm start of the working set (default on)
+  DeviceBuffer<signed char> d_wset;  // working sets carried from tick to tick (hmpc_set_tick_warm_start), [max_batch][8 nc h]
+  int tick_warm = 0, tick_shift = 0;
+  int auto_resolve = 1;  // hmpc_download re-solves flagged instances with the safe variant (default on)
+  int max_stance = -1;  // max reduced variables of the current batch (known only for host-uploaded records; else -1)
+  hipStream_t last_stream = nullptr;
+  bool attrs_set[N_VARIANTS] = {};
+  // persistent device scratch for the host-pointer convenience entry points (grown on demand): no allocation per call and nothing to
+  // leak on an early error return
+  DeviceBuffer<unsigned char> d_scratch;
+  // number of instances the solve kernels have flagged (working set full / max-iter / infeasible / KKT) since the handle
+  // was created; monotonically increasing device counter, hmpc_download compares it with the value it saw last and
+  // skips the status scan of the safe pass when nothing new was flagged
+  DeviceBuffer<unsigned int> d_flagged;
+  unsigned int flagged_seen = 0;
+  // device-side safe pass (hmpc_set_device_repair): list of the instances the last fast launch flagged + its counter
+  int device_repair = 0;
+  DeviceBuffer<int> d_flag_list;
+  DeviceBuffer<unsigned int> d_flag_count;
+  // parity hook (hmpc_debug_solve_external_qp): device copies of caller-supplied QP data, only set during that call
+  const float *d_ext_H = nullptr, *d_ext_g = nullptr, *d_ext_Fc = nullptr;
+  int ext_ld = 0;
+  int iter_cap = 0;  // hmpc_set_max_iterations: cap on the active-set iterations of every solve (0 = the variant's own bound)
+  // hmpc_set_dispatch_order: 1 = workgroups take the instances longest-previous-solve first (d_order, rebuilt at the head of
+  // every solve from the status words the previous solve of a batch of the same size left; order_batch = that size, 0 = none)
+  int dispatch_order = 1, order_batch = 0;
+  bool order_valid = false;
+  DeviceBuffer<int> d_order;
+  DeviceBuffer<unsigned char> d_keys;  // predicted cost bucket per instance (cold-handle order), allocated on first use
+  // size classes of a device-resident batch whose widest reduced QP the host was not told (hmpc_set_max_reduced_vars < 0):
+  // stance leg-steps per instance, written on the device by the record builder (cls_valid) or, for records handed in by
+  // pointer, by classify_records_kernel at the head of every solve
+  DeviceBuffer<unsigned char> d_cls;
+  int cls_valid = 0;
+  // packed Schur inverses of the EGLOBAL safe variants: [e_slices][nmax (nmax + 1) / 2] doubles, grown on demand
+  DeviceBuffer<double> d_escratch;
+  // hand-over of full working sets (KernelArgs::spill): one slot per instance (slot = instance index), allocated on the first
+  // launch of a variant that saves its state; spill_stride = bytes per slot of the allocation, spill_cap = slots
+  DeviceBuffer<unsigned char> d_spill;
+  DeviceBuffer<int> d_spill_slot;
+  size_t spill_stride = 0;
+  int spill_cap = 0;
+  int handover = 1;  // hmpc_set_handover (default on)
+  hmpc_params params{};  // robot / contact constants (hmpc_set_params; defaults = the reference's literals)
+  const float *d_mu_inst = nullptr;  // hmpc_set_instance_mu: per-instance friction parameter in HBM (caller-owned), nullptr = params.mu for all
+  DeviceBuffer<double> d_reg_rho;  // Hessians that are not positive definite: the pivot the safe variant found, then rho of hmpc_resolve_failed's regularisation steps, per instance (allocated with the first list launch)
+  ResultState results;  // which of the results below belong to the current batch and its last solve (hmpc_plan.h)
+  // prediction (hmpc_predict_states): states [max_batch][horizon][13] binary32 and cost [max_batch][2] binary64, to the caller's buffers
+  // (hmpc_set_device_prediction) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<float> d_pred_states;
+  OutputBuffer<double> d_pred_cost;
+  // selection (hmpc_sweep_select): one row per sweep group, to the caller's buffers (hmpc_set_device_selection) or the handle's own,
+  // allocated for max_batch groups by the first call that needs them
+  OutputBuffer<int32_t> d_sel_index;
+  OutputBuffer<double> d_sel_score;
+  OutputBuffer<float> d_sel_forces;
+  OutputBuffer<uint32_t> d_sel_status;
+  OutputBuffer<float> d_sel_states;
+  // constraint margins (hmpc_constraint_margins): slack [max_batch][horizon][nc][10] and summary [max_batch][6] binary64, where
+  // [max_batch][6], to the caller's buffers (hmpc_set_device_margins) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<double> d_mar_slack, d_mar_summary;
+  OutputBuffer<int32_t> d_mar_where;
+  // hmpc_set_sweep_margin_floor: hmpc_tick_sweep_device masks the commands whose margins miss the floor (penalty: scratch of the handle)
+  bool sweep_floor_on = false;
+  double sweep_floor[hmpc::MARGIN_CLASSES] = {};
+  DeviceBuffer<double> d_sweep_penalty;
+  DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
+};
+
+// the fast variant of the handle's batch (the only place a handle is mapped to a fast variant)
+inline int pick_variant(const hmpc_handle *h) { return pick_variant(h->nc, h->setup.horizon, h->max_stance); }
+
+struct LaunchOpt {
+  bool assemble_only = false;
+  int dbg_index = 0;
+  const int *d_index_list = nullptr;  // workgroup b solves instance d_index_list[b] (the repair passes over flagged instances)
+  int n_list = 0;
+  double relax = 0.0;
+  int warm = -1;           // -1 = the handle's setting, 0/1 = override for this launch (the safe pass chooses per pass without touching the handle)
+  bool carry_wset = true;  // false keeps a repeated launch of the same batch from consuming/advancing the tick-to-tick working sets
+  const unsigned int *d_list_count = nullptr;
+  bool record_flagged = false;
+  bool longest_first = false;  // workgroup b takes instance h->d_order.get()[b] (enqueue_solve, hmpc_set_dispatch_order)
+  int cls_lo = 0, cls_hi = -1;  // cls_hi >= 0: only instances whose size class lies in [cls_lo, cls_hi] (h->d_cls.get())
+  int skip_ok = 0;         // list launch: instances an earlier pass over the same list solved are left alone (1: ok / ok-relaxed, 2: ok only)
+  int sweep_k = 0, sweep_phase = 0;  // command sweep: group size; phase 0 = one workgroup per group forms M, 1 = one per instance solves with it (a SWEEP variant)
+  bool list_indefinite = false;  // device-side chain, safe launch: instances ended as HMPC_S_INDEFINITE are appended to the handle's short list
+  int reg_step = 0;        // safe pass over an index list: regularisation step 1 / 2 for instances whose Hessian is not positive definite (KernelArgs::reg_step)
+};
+
+// ---- hmpc_launch.hip
+const Variant *variants();  // [N_VARIANTS], in the order of HMPC_VARIANT_TABLE
+// returns a device buffer of at least `bytes` owned by the handle (contents undefined); its earlier users may be on any stream
+int scratch(hmpc_handle *h, size_t bytes, void **out);
+// What stage A of a kernel reads of the handle: the batch, the problem shape and the robot / contact constants.  One place, so that the
+// prediction and margins kernels assemble from the very values the solve kernels do.
+void set_problem_args(const hmpc_handle *h, hmpc::KernelArgs &a);
+int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o);                       // one launch of variants()[vi]
+int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes, LaunchOpt o);          // the fast pass of one solve
+int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset);                           // what hmpc_solve enqueues
+int enqueue_command_sweep(hmpc_handle *h, hipStream_t stream, int group_size);                    // what hmpc_solve_command_sweep enqueues (group_size > 1)
+int resolve_failed(hmpc_handle *h, int *n_resolved);                                              // the host-driven repair of hmpc_resolve_failed (device set, batch > 0)
+
+#pragma GCC visibility pop

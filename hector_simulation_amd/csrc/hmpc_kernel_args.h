@@ -1,6 +1,6 @@
 // hmpc_kernel_args.h -- what the host side needs to know of the fused kernel (hmpc_kernel.h): its argument block, the status
 // codes, the layout of the assembly debug dump, the roles a variant can have.  Kept apart from the 3 500-line kernel header so that the host translation
-// units (hmpc_capi.hip, hmpc_group.hip) compile in seconds and the kernel family builds in parallel (hmpc_variants.hip).
+// units (hmpc_capi.hip, hmpc_launch.hip, hmpc_group.hip, ...) compile in seconds and the kernel family builds in parallel (hmpc_variants.hip).
 // The record KernelArgs::records points at -- field offsets, sizes, the stance rule -- is defined in hmpc_record.h, for both sides.
 #pragma once
 #include <stdint.h>
@@ -121,11 +121,19 @@ struct KernelArgs {
 constexpr int NPROF = 32;
 enum : int { P_ASM = 0, P_HG, P_SWEEP, P_XU, P_SEL, P_D, P_ED, P_W, P_MV, P_T1, P_UPD, P_POLISH, P_FINAL, P_TOTAL, P_BLOCK, P_B_S0, P_B_INV, P_B_DROP, P_SEL_A, P_A0, P_A1, P_A2, P_G };
 
-// offsets (in floats) of the debug dump, shared with the host
+// offsets (in floats) of the debug dump, shared with the host: dbg_layout for a variant known at run time (hmpc_debug_assemble),
+// DbgLayout -- the same values -- where the shape is a template parameter (the kernel)
+struct DbgOffsets {
+  int H, G, FC, LB, UB, X0, ACD, BCD, TOTAL;
+};
+constexpr DbgOffsets dbg_layout(int nmax, int nc) {
+  const int G = nmax * nmax, FC = G + nmax, LB = FC + 48 * nc * nc, UB = LB + 8 * nc * 20, X0 = UB + 8 * nc * 20, ACD = X0 + 16, BCD = ACD + 176;
+  return {0, G, FC, LB, UB, X0, ACD, BCD, BCD + 80 * nc};
+}
 template <int NMAX, int NC = 2>
 struct DbgLayout {
-  static constexpr int H = 0, G = NMAX * NMAX, FC = G + NMAX, LB = FC + 48 * NC * NC, UB = LB + 8 * NC * 20,
-                       X0 = UB + 8 * NC * 20, ACD = X0 + 16, BCD = ACD + 176, TOTAL = BCD + 80 * NC;
+  static constexpr DbgOffsets L = dbg_layout(NMAX, NC);
+  static constexpr int H = L.H, G = L.G, FC = L.FC, LB = L.LB, UB = L.UB, X0 = L.X0, ACD = L.ACD, BCD = L.BCD, TOTAL = L.TOTAL;
 };
 
 enum : int { S_OK = 0, S_MAXITER = 1, S_INFEASIBLE = 2, S_TOO_LARGE = 3, S_KKT = 4, S_WORKSET = 5, S_OK_RELAXED = 6, S_SWEEP_MISMATCH = 7, S_INDEFINITE = 8, S_REG_STEP = 9 };

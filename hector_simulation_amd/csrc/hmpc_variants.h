@@ -1,4 +1,4 @@
-// hmpc_variants.h -- the table of kernel variants, shared between the host side (hmpc_capi.hip: picks and launches) and
+// hmpc_variants.h -- the table of kernel variants, shared between the host side (hmpc_plan.h picks, hmpc_launch.hip launches) and
 // hmpc_variants.hip (instantiates; compiled once per group -DHMPC_VARIANT_GROUP=0..3 so that the groups build in parallel).
 #pragma once
 #include <stddef.h>
@@ -27,7 +27,7 @@ struct Variant {
   size_t spill_stride;  // bytes of one hand-over slot (KernelArgs::spill) when this variant SAVES its state (FAST on the hand-over shape), 0 otherwise
 };
 
-// index = position in hmpc_capi.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE), group = translation unit that builds it.
+// index = position in hmpc_launch.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE), group = translation unit that builds it.
 // The groups are balanced by compile time (the two-blocks-per-thread and 512-thread variants are the slow ones).
 #define HMPC_VARIANT_TABLE(X)                             \
   X(0, 0, 60, 10, 128, 60, 2, 1, FAST)                    \

@@ -13,14 +13,18 @@ SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fram
 # (every translation unit to an object first: handed to one hipcc command together with .hip sources, the objects would be parsed as HIP)
 CF="--offload-arch=gfx950 -O1 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-value -Wno-pass-failed"
 pids=""
-for src in hmpc_capi hmpc_group; do
+# (the units of the library: hector_simulation_amd/build.py HOST_SOURCES, the one list)
+UNITS=$(python -c "from hector_simulation_amd import build; print(' '.join(s[:-4] for s in build.HOST_SOURCES))") || exit 2
+HOST_OBJS=""
+for src in $UNITS; do
   hipcc $CF $SAN -fno-gpu-sanitize -c hector_simulation_amd/csrc/$src.hip -o $OUT/$src.o & pids="$pids $!"
+  HOST_OBJS="$HOST_OBJS $OUT/$src.o"
 done
 for g in 0 1 2 3; do
   hipcc $CF -DHMPC_VARIANT_GROUP=$g -c hector_simulation_amd/csrc/hmpc_variants.hip -o $OUT/hmpc_variants_$g.o & pids="$pids $!"
 done
 for p in $pids; do wait $p || exit 2; done
-hipcc --offload-arch=gfx950 -shared -fPIC $SAN -fno-gpu-sanitize -shared-libsan $OUT/hmpc_capi.o $OUT/hmpc_group.o $OUT/hmpc_variants_0.o $OUT/hmpc_variants_1.o \
+hipcc --offload-arch=gfx950 -shared -fPIC $SAN -fno-gpu-sanitize -shared-libsan $HOST_OBJS $OUT/hmpc_variants_0.o $OUT/hmpc_variants_1.o \
   $OUT/hmpc_variants_2.o $OUT/hmpc_variants_3.o -ldl -o $OUT/libhector_mpc_hip.so || exit 2
 rm -f $OUT/*.o
 CLANG=$(dirname $(dirname "$RT"))/../../../bin/clang

@@ -161,8 +161,8 @@ def test_each_of_the_fifteen_variants_is_built_by_exactly_one_translation_unit()
     hdr = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_variants.h")).read()
     rows = re.findall(r"X\((\d+), (\d+),[^)]*, (FAST|CONT|SAFE|SWEEP)\)", hdr)
     assert [int(i) for i, _, _ in rows] == list(range(15))
-    capi = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_capi.hip")).read()
-    assert "constexpr int N_VARIANTS = 15;" in capi
+    plan = open(os.path.join(ROOT, "hector_simulation_amd", "csrc", "hmpc_plan.h")).read()
+    assert "constexpr int N_VARIANTS = 15;" in plan
     groups = sorted({int(g) for _, g, _ in rows})
     assert groups == list(range(build.VARIANT_GROUPS))
     assert f"HMPC_VARIANT_GROUPS = {build.VARIANT_GROUPS}" in hdr

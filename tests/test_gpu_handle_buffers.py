@@ -1,4 +1,4 @@
-"""Where a handle's outputs go (csrc/hmpc_device_buffer.h OutputBuffer, as hmpc_capi.hip uses it): its own buffers, the caller's, and its
+"""Where a handle's outputs go (csrc/hmpc_device_buffer.h OutputBuffer, as the handle of csrc/hmpc_handle.h uses it): its own buffers, the caller's, and its
 own again after the caller's were reset to NULL -- the same bits every time, in the buffers hmpc_get_device_* names.
 
 One batch: 8 instances of the standing case at h = 10 (the 120-variable shape) as 2 groups of 4 commands, device repair on; every run is

@@ -41,7 +41,7 @@ def rel_inf(a, b):
 
 def variant_of(h, nc, n_max):
     """(name, binary64 bar) of the fast variant that holds a batch whose widest reduced QP has n_max variables (pick_variant of
-    csrc/hmpc_capi.hip, restated): 60 / 120 variables at h <= 10 or h <= 20, the wide 240-variable one, the three-contact one."""
+    csrc/hmpc_plan.h, restated): 60 / 120 variables at h <= 10 or h <= 20, the wide 240-variable one, the three-contact one."""
     if nc == 3:
         return "180/10 three contacts", BAR64_WIDE
     if n_max > 120:
@@ -192,7 +192,7 @@ def test_every_horizon(oracle, h):
 
 # ------------------------------------------------------------------------------------------------ d. routing at the class borders
 def classes_of(b_n, h):
-    """[(hint, rows)]: the size classes the device sorts a two-contact batch into (csrc/hmpc_capi.hip enqueue_fast)."""
+    """[(hint, rows)]: the size classes the device sorts a two-contact batch into (csrc/hmpc_plan.h class_launches)."""
     out = [(60, np.flatnonzero(b_n <= 60)), (120, np.flatnonzero((b_n > 60) & (b_n <= 120)))]
     if h > 10:
         out.append((240, np.flatnonzero(b_n > 120)))
