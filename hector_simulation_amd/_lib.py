@@ -31,6 +31,9 @@ EXPORTS = [
     "hmpc_sweep_select", "hmpc_set_device_selection", "hmpc_get_device_selection", "hmpc_download_selection", "hmpc_tick_sweep_device",
     "hmpc_constraint_margins", "hmpc_set_device_margins", "hmpc_get_device_margins", "hmpc_download_margins", "hmpc_margin_penalty",
     "hmpc_set_sweep_margin_floor", "hmpc_legacy_constraint_slack",
+    "hmpc_kkt_certificate", "hmpc_set_device_certificate", "hmpc_get_device_certificate", "hmpc_download_certificate",
+    "hmpc_set_certificate_tolerance", "hmpc_certificate_penalty", "hmpc_set_sweep_certificate_ceiling", "hmpc_legacy_multiplier",
+    "hmpc_legacy_stationarity",
 ]
 
 
@@ -202,6 +205,17 @@ def load():
     L.hmpc_set_sweep_margin_floor.argtypes = [vp, vp]
     L.hmpc_legacy_constraint_slack.argtypes = [ci, ci, ci]
     L.hmpc_legacy_constraint_slack.restype = cd
+    L.hmpc_kkt_certificate.argtypes = [vp, vp]
+    L.hmpc_set_device_certificate.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hmpc_get_device_certificate.argtypes = [vp] + [C.POINTER(vp)] * 5
+    L.hmpc_download_certificate.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hmpc_set_certificate_tolerance.argtypes = [vp, cd]
+    L.hmpc_certificate_penalty.argtypes = [vp, vp, vp, vp, vp]
+    L.hmpc_set_sweep_certificate_ceiling.argtypes = [vp, vp]
+    L.hmpc_legacy_multiplier.argtypes = [ci, ci, ci]
+    L.hmpc_legacy_multiplier.restype = cd
+    L.hmpc_legacy_stationarity.argtypes = []
+    L.hmpc_legacy_stationarity.restype = cd
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

@@ -1,5 +1,5 @@
 // hmpc_capi.hip -- the batched C ABI of include/hector_mpc.h over the gfx950 kernels: handles, batches, settings, downloads, the debug
-// hooks, the caller-side rows f1-f3 and the device-resident ticks, and the results derived from a solve (prediction, margins,
+// hooks, the caller-side rows f1-f3 and the device-resident ticks, and the results derived from a solve (prediction, margins, certificate,
 // selection).  What a solve launches is hmpc_launch.hip's; the reference's own process-global interface is hmpc_legacy.hip's.
 // There is NO CPU fallback: without a gfx950 device every entry point fails (HMPC_E_NO_DEVICE).
 #include <hip/hip_runtime.h>
@@ -790,6 +790,105 @@ int hmpc_set_sweep_margin_floor(hmpc_handle *h, const double floor[6]) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// KKT certificate: whether the forces of the last solve minimise the QP, and its multipliers (hmpc_certificate.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next certificate goes: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int certificate_buffers(hmpc_handle *h, hmpc::CertificateOut *b) {
+  const size_t mb = (size_t)h->max_batch, ls = mb * h->setup.horizon * h->nc;
+  HIP_TRY(h->d_cert_grad.ensure(ls * 6));
+  HIP_TRY(h->d_cert_lambda.ensure(ls * 10));
+  HIP_TRY(h->d_cert_resid.ensure(ls * 6));
+  HIP_TRY(h->d_cert_summary.ensure(mb * hmpc::CERT_CLASSES));
+  HIP_TRY(h->d_cert_where.ensure(mb * hmpc::CERT_WHERE));
+  *b = {h->d_cert_grad.get(), h->d_cert_lambda.get(), h->d_cert_resid.get(), h->d_cert_summary.get(), h->d_cert_where.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_certificate(hmpc_handle *h, double *device_grad, double *device_lambda, double *device_resid, double *device_summary,
+                                int32_t *device_where) {
+  if (!h) return HMPC_E_ARG;
+  h->d_cert_grad.set_caller(device_grad), h->d_cert_lambda.set_caller(device_lambda), h->d_cert_resid.set_caller(device_resid);
+  h->d_cert_summary.set_caller(device_summary), h->d_cert_where.set_caller(device_where);
+  h->results.retarget_certificate();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_certificate(hmpc_handle *h, double **device_grad, double **device_lambda, double **device_resid, double **device_summary,
+                                int32_t **device_where) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::CertificateOut b;
+  const int rc = certificate_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_grad) *device_grad = b.grad;
+  if (device_lambda) *device_lambda = b.lambda;
+  if (device_resid) *device_resid = b.resid;
+  if (device_summary) *device_summary = b.summary;
+  if (device_where) *device_where = b.where;
+  return HMPC_OK;
+}
+
+int hmpc_set_certificate_tolerance(hmpc_handle *h, double act_tol) {
+  if (!h || !(act_tol > 0.0 && act_tol < 0.005)) return HMPC_E_ARG;  // (0.005: half the Mx window, above which both sides of row 4 would be active at once)
+  h->cert_act_tol = act_tol;
+  return HMPC_OK;
+}
+
+int hmpc_kkt_certificate(hmpc_handle *h, void *stream) {
+  if (!h || !h->results.has_solve()) return HMPC_E_ARG;  // no solve of the current batch: the force buffer holds another batch's forces, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::CertificateOut b;
+  const int rc = certificate_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_certificate(h->nc, a, h->cert_act_tol, b, (hipStream_t)stream));
+  h->results.on_certificate();
+  return HMPC_OK;
+}
+
+int hmpc_download_certificate(hmpc_handle *h, double *grad, double *lambda, double *resid, double *summary, int32_t *where) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_certificate()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::CertificateOut b;
+  const int rc = certificate_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, ls = n * h->setup.horizon * h->nc;
+  if (grad) HIP_TRY(hipMemcpy(grad, b.grad, ls * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (lambda) HIP_TRY(hipMemcpy(lambda, b.lambda, ls * 10 * sizeof(double), hipMemcpyDeviceToHost));
+  if (resid) HIP_TRY(hipMemcpy(resid, b.resid, ls * 6 * sizeof(double), hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, n * hmpc::CERT_CLASSES * sizeof(double), hipMemcpyDeviceToHost));
+  if (where) HIP_TRY(hipMemcpy(where, b.where, n * hmpc::CERT_WHERE * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+int hmpc_certificate_penalty(hmpc_handle *h, const double ceil[3], const double *device_penalty_in, double *device_penalty_out, void *stream) {
+  if (!h || !ceil || !device_penalty_out) return HMPC_E_ARG;
+  if (!h->results.has_certificate()) return HMPC_E_ARG;  // no certificate of the last solve of this batch: the summary holds another solve's, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::CertificateOut b;
+  const int rc = certificate_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_certificate_penalty(b.summary, ceil, device_penalty_in, device_penalty_out, h->batch, (hipStream_t)stream));
+  return HMPC_OK;
+}
+
+int hmpc_set_sweep_certificate_ceiling(hmpc_handle *h, const double ceil[3]) {
+  if (!h) return HMPC_E_ARG;
+  h->sweep_ceil_on = ceil != nullptr;
+  for (int k = 0; k < hmpc::CERT_CEILS; ++k) h->sweep_ceil[k] = ceil ? ceil[k] : 0.0;
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {
@@ -899,6 +998,12 @@ int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks
     HIP_TRY(h->d_sweep_penalty.reserve((size_t)h->max_batch * sizeof(double), (hipStream_t)stream, /*whole_device=*/true));
     rc = hmpc_constraint_margins(h, stream);
     if (rc == HMPC_OK) rc = hmpc_margin_penalty(h, h->sweep_floor, device_penalty, h->d_sweep_penalty.get(), stream);
+    device_penalty = h->d_sweep_penalty.get();
+  }
+  if (rc == HMPC_OK && h->sweep_ceil_on) {  // ... and those whose certificate exceeds the ceiling: behind the margin penalty, through the same scratch (in place)
+    HIP_TRY(h->d_sweep_penalty.reserve((size_t)h->max_batch * sizeof(double), (hipStream_t)stream, /*whole_device=*/true));
+    rc = hmpc_kkt_certificate(h, stream);
+    if (rc == HMPC_OK) rc = hmpc_certificate_penalty(h, h->sweep_ceil, device_penalty, h->d_sweep_penalty.get(), stream);
     device_penalty = h->d_sweep_penalty.get();
   }
   if (rc == HMPC_OK) rc = hmpc_sweep_select(h, group_size, device_penalty, stream);

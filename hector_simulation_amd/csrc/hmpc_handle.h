@@ -8,6 +8,7 @@
 #include "../../include/hector_mpc.h"
 #include "hmpc_device_buffer.h"
 #include "hmpc_kernel_args.h"
+#include "hmpc_certificate.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -103,6 +104,15 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   bool sweep_floor_on = false;
   double sweep_floor[hmpc::MARGIN_CLASSES] = {};
   DeviceBuffer<double> d_sweep_penalty;
+  // KKT certificate (hmpc_kkt_certificate): grad [max_batch][horizon][6 nc], lambda [max_batch][horizon][nc][10], resid
+  // [max_batch][horizon][nc][6] and summary [max_batch][4] binary64, where [max_batch][2], to the caller's buffers
+  // (hmpc_set_device_certificate) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<double> d_cert_grad, d_cert_lambda, d_cert_resid, d_cert_summary;
+  OutputBuffer<int32_t> d_cert_where;
+  double cert_act_tol = 1e-3;  // hmpc_set_certificate_tolerance
+  // hmpc_set_sweep_certificate_ceiling: hmpc_tick_sweep_device masks the commands whose certificate exceeds the ceiling (same scratch)
+  bool sweep_ceil_on = false;
+  double sweep_ceil[hmpc::CERT_CEILS] = {};
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

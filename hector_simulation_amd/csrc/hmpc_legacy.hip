@@ -25,6 +25,8 @@ static float g_pred[13 * HMPC_MAX_HORIZON];  // hmpc_legacy_predicted_state: the
 static int g_pred_valid = 0;
 static double g_slack[10 * 2 * HMPC_MAX_HORIZON];  // hmpc_legacy_constraint_slack: the last solve's slacks, fetched on first use
 static int g_slack_valid = 0;
+static double g_lambda[10 * 2 * HMPC_MAX_HORIZON], g_cert_summary[4];  // hmpc_legacy_multiplier, hmpc_legacy_stationarity: the last solve's certificate, fetched on first use
+static int g_cert_valid = 0;
 static int g_legacy_iter_cap = 0;  // hmpc_legacy_set_max_iterations: explicit opt-in (update_solver_settings is inert, as in the reference)
 // one tick = one pinned staging buffer [record | 12h forces | status word] and one contiguous device output block, so that
 // a blocking tick costs one asynchronous H2D copy, one launch, one asynchronous D2H copy and a single synchronisation
@@ -133,6 +135,7 @@ static void solve_global(void) {
   g_has_solved = 1;
   g_pred_valid = 0;
   g_slack_valid = 0;
+  g_cert_valid = 0;
 }
 
 void update_problem_data(double *p, double *v, double *q, double *w, double *r, double *joint_angles, double yaw,
@@ -184,6 +187,30 @@ double hmpc_legacy_constraint_slack(int step, int contact, int j) {
     g_slack_valid = 1;
   }
   return g_slack[10 * (2 * step + contact) + j];
+}
+
+// once per solve, on first use: one launch and two small copies
+static bool legacy_certificate(void) {
+  if (g_cert_valid) return true;
+  int rc = hmpc_kkt_certificate(g_handle, nullptr);
+  if (rc == HMPC_OK) rc = hmpc_download_certificate(g_handle, nullptr, g_lambda, nullptr, g_cert_summary, nullptr);
+  if (rc != HMPC_OK) {
+    fprintf(stderr, "[hector_mpc_hip] KKT certificate failed (%d): %s\n", rc, hmpc_last_hip_error());
+    return false;
+  }
+  g_cert_valid = 1;
+  return true;
+}
+
+double hmpc_legacy_multiplier(int step, int contact, int j) {
+  if (!g_has_solved || !g_handle) return 0.0;  // as get_solution: 0 before the first solve and for out-of-range arguments
+  if (step < 0 || step >= g_setup.horizon || contact < 0 || contact >= 2 || j < 0 || j >= 10) return 0.0;
+  return legacy_certificate() ? g_lambda[10 * (2 * step + contact) + j] : 0.0;
+}
+
+double hmpc_legacy_stationarity(void) {
+  if (!g_has_solved || !g_handle) return 0.0;
+  return legacy_certificate() ? g_cert_summary[0] : 0.0;
 }
 
 void update_solver_settings(int max_iter, double rho, double sigma, double solver_alpha, double terminate,

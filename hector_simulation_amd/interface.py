@@ -74,6 +74,17 @@ def legacy_constraint_slack(step: int, contact: int, j: int) -> float:
     return float(_lib.load().hmpc_legacy_constraint_slack(int(step), int(contact), int(j)))
 
 
+def legacy_multiplier(step: int, contact: int, j: int) -> float:
+    """Multiplier ``j`` (0..9) of ``contact`` (0, 1) at ``step`` (0..horizon-1) of the process-global solver's last solution
+    (include/hector_mpc.h hmpc_legacy_multiplier); 0 before the first solve and for out-of-range arguments."""
+    return float(_lib.load().hmpc_legacy_multiplier(int(step), int(contact), int(j)))
+
+
+def legacy_stationarity() -> float:
+    """The stationarity residual (summary[0] of the KKT certificate) of the process-global solver's last solution; 0 before the first."""
+    return float(_lib.load().hmpc_legacy_stationarity())
+
+
 def last_status() -> int:
     return int(_lib.load().hmpc_last_status())
 
@@ -331,6 +342,49 @@ class BatchedMPC:
         fl = None if floor is None else np.ascontiguousarray(floor, dtype=np.float64)
         assert fl is None or fl.shape == (6,)
         _check(self.L.hmpc_set_sweep_margin_floor(self.h, None if fl is None else fl.ctypes.data), "hmpc_set_sweep_margin_floor")
+
+    def kkt_certificate(self, stream: int = 0) -> None:
+        """One launch behind the solve on ``stream``: the gradient of the QP objective at the forces in the force buffer, multipliers >= 0
+        on the active limits, the stationarity residual they leave and the per-instance summary (include/hector_mpc.h
+        hmpc_kkt_certificate).  Raises when no solve of the current batch has been enqueued."""
+        _check(self.L.hmpc_kkt_certificate(self.h, C.c_void_p(stream)), "hmpc_kkt_certificate")
+
+    def download_certificate(self) -> dict:
+        """grad float64[batch, horizon, 6 contacts], lambda float64[batch, horizon, contacts, 10], resid float64[batch, horizon, contacts, 6],
+        summary float64[batch, 4] and where int32[batch, 2] (-1 = no candidate).  Waits; runs no safe pass."""
+        b, hz, nc = self.batch, self.horizon, self.contacts
+        out = {"grad": np.zeros((b, hz, 6 * nc), dtype=np.float64), "lambda": np.zeros((b, hz, nc, 10), dtype=np.float64),
+               "resid": np.zeros((b, hz, nc, 6), dtype=np.float64), "summary": np.zeros((b, 4), dtype=np.float64),
+               "where": np.zeros((b, 2), dtype=np.int32)}
+        _check(self.L.hmpc_download_certificate(self.h, *[out[k].ctypes.data for k in ("grad", "lambda", "resid", "summary", "where")]),
+               "hmpc_download_certificate")
+        return out
+
+    def set_device_certificate(self, grad_ptr: int = 0, lambda_ptr: int = 0, resid_ptr: int = 0, summary_ptr: int = 0, where_ptr: int = 0,
+                               keepalive=None) -> None:
+        """Caller-owned device buffers for later certificates (shapes of ``download_certificate`` with max_batch rows; 0 / None = the
+        handle's own)."""
+        self._keep_cert = keepalive
+        _check(self.L.hmpc_set_device_certificate(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_ptr, lambda_ptr, resid_ptr, summary_ptr,
+                                                                                               where_ptr)]), "hmpc_set_device_certificate")
+
+    def set_certificate_tolerance(self, act_tol: float) -> None:
+        """A slack <= ``act_tol`` makes its limit active for the multipliers (default 1e-3; 0 < act_tol < 0.005)."""
+        _check(self.L.hmpc_set_certificate_tolerance(self.h, float(act_tol)), "hmpc_set_certificate_tolerance")
+
+    def certificate_penalty(self, ceil, out_ptr: int, penalty_in_ptr: int = 0, stream: int = 0) -> None:
+        """out[i] = +inf where some summary[i, k] <= ceil[k] (k < 3) is false (NaN ceil entries are not tested), else penalty_in[i] or 0: a
+        ``penalty_ptr`` of ``sweep_select``.  ``out_ptr``, ``penalty_in_ptr``: float64[batch] in HBM (may be the same)."""
+        cl = np.ascontiguousarray(ceil, dtype=np.float64)
+        assert cl.shape == (3,)
+        _check(self.L.hmpc_certificate_penalty(self.h, cl.ctypes.data, C.c_void_p(int(penalty_in_ptr or 0)), C.c_void_p(int(out_ptr or 0)),
+                                               C.c_void_p(stream)), "hmpc_certificate_penalty")
+
+    def set_sweep_certificate_ceiling(self, ceil=None) -> None:
+        """ceil[3] for ``tick_sweep_device`` (commands whose certificate exceeds it are masked); None = off, the default."""
+        cl = None if ceil is None else np.ascontiguousarray(ceil, dtype=np.float64)
+        assert cl is None or cl.shape == (3,)
+        _check(self.L.hmpc_set_sweep_certificate_ceiling(self.h, None if cl is None else cl.ctypes.data), "hmpc_set_sweep_certificate_ceiling")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

@@ -461,6 +461,75 @@ int hmpc_set_sweep_margin_floor(hmpc_handle *h, const double floor[6]);
  * (0..horizon-1) under the last solution.  Computed lazily, once per solve, on first use (one launch, one copy).  0 before the first
  * solve and for out-of-range arguments, as get_solution. */
 double hmpc_legacy_constraint_slack(int step, int contact, int j);
+/* ---- the KKT certificate and the Lagrange multipliers of every solved instance ----
+ * Whether the forces in the force buffer minimise the QP, and the QP's dual solution.  Per instance, let NC be the number of contacts
+ * and U = 6 NC.  Let x0, Acd, Bcd, Fc, the weights w[12], the trajectory, Alpha_K[U], the gait and the caps be the binary32 values the
+ * solve kernel's assembly stage builds for the record (hmpc_params and hmpc_set_instance_mu included), and u_i[U] step i of the force
+ * buffer as it stands.  Everything below is binary64.  Every sum is one ascending chain of explicit fused multiply-adds started at +0,
+ * dense, with the structural zeros taking part.
+ *   1. States.  x_1 .. x_h exactly as hmpc_predict_states defines them, un-rounded.
+ *   2. Costate.  q_i[s] = (w_s + w_s) (x_i[s] - traj[12 (i-1) + s]) for s < 12, q_i[12] = 0, for i = 1 .. h.  p_h = q_h.  For
+ *      i = h-1 .. 1: p_i[s] = q_i[s] + sum_{k<13} Acd[k][s] p_{i+1}[k] (the chain runs first; one addition follows).
+ *   3. Gradient.  For i = 0 .. h-1 and c < U: grad_i[c] = fma(alpha_c + alpha_c, u_i[c], sum_{k<13} Bcd[k][c] p_{i+1}[k]).  This is the
+ *      gradient of cost[0] + cost[1] of the prediction; in exact arithmetic it equals H u + g of the reference's QP.
+ *   4. Slacks.  s[i][c][0..9] and the stance rule are exactly those of hmpc_constraint_margins.
+ *   5. Multipliers of stance leg-step (i, c).  cols(c) = {3c, 3c+1, 3c+2, 3NC+3c, 3NC+3c+1, 3NC+3c+2}; r = grad_i[cols(c)] in R^6;
+ *      n_j' = sigma_j' Fc[8c + src(j')][cols(c)] with src = (0,1,2,3,4,4,5,6,7,7) and sigma = (+,+,+,+,+,-,-,-,+,-) (rows 8c .. 8c+7 of
+ *      Fc are zero outside cols(c)).  The active set is A = { j' : s[j'] <= act_tol }; a NaN slack is not active.
+ *      lambda_A = argmin over lambda >= 0 of |r - N_A lambda|_2, e = r - N_A lambda_A; elsewhere lambda_j' = 0.  With A empty, e = r.
+ *      A swing leg-step has lambda = 0 and e = 0: its variables were eliminated.  e is unique (the residual of a projection on a closed
+ *      convex cone); lambda is unique iff the active normals are linearly independent.  Stationarity of the QP at u means e = 0 on
+ *      every stance leg-step.
+ *   6. Algorithm.  Lawson-Hanson active-set NNLS over the columns of A in ascending j', ties to the lowest j'.  The passive-set least
+ *      squares goes through the Cholesky factor of the <= 6 x 6 Gram matrix.  A column whose pivot falls below 1e-12 of its own
+ *      diagonal is not admitted: a dependent normal never enters the passive set, so |P| <= 6.  A column admitted and given no
+ *      positive weight by its first solution leaves again at once; a column refused either way is not proposed again until lambda
+ *      has moved.  At most 32 outer and 32 inner steps in total; a solution that is not finite ends the loop.  Whatever lambda >= 0 the
+ *      loop holds when it stops is the answer, and e is recomputed from that lambda (dense over the ten j', ascending): any lambda >= 0
+ *      is a valid certificate and the residual reported is the residual of the lambda reported, so a NaN or an iteration cap can make
+ *      a certificate pessimistic but never wrong.  The loop terminates on NaN input.
+ *   7. act_tol: hmpc_set_certificate_tolerance, default 1e-3 -- derived, not tuned: >= 8 x the slack that binary32 rounding of a force at
+ *      the cap leaves on an active row (500 N * 2^-24 * |row|_1 <~ 1.2e-4), and 5 x below half the Mx window (0.005), above which both
+ *      sides of row 4 would be active at once.  HMPC_E_ARG unless 0 < act_tol < 0.005.
+ *   8. summary[batch][4] binary64 and where[batch][2] int32: maxima over the stance leg-steps.  A candidate v counts as +inf when it is
+ *      NaN; it replaces the incumbent iff it is greater, or equal with a lower index.  No candidate: 0 and -1.  The reduction does
+ *      not depend on its order.
+ *        [0] stationarity: max |e_k|; where[0] = 6 (NC i + c) + k.
+ *        [1] complementarity: max over active j' of lambda_j' * max(s_j', 0); where[1] = 10 NC i + 10 c + j'.
+ *        [2] primal violation: max of max(0, -s_j') over all ten slacks (a NaN slack is a NaN candidate).
+ *        [3] gradient scale: max |grad_i[c]| over the stance variables, for callers who want a relative test.
+ * Outputs: grad[batch][h][U], lambda[batch][h][NC][10], resid[batch][h][NC][6] (= e), summary, where; all binary64 except where.  The
+ * result is a pure function of (record, hmpc_params, per-instance mu, force buffer, act_tol).  Instances that are not HMPC_S_OK are
+ * computed all the same.
+ *
+ * hmpc_kkt_certificate enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance, sharing nothing with the solver
+ * but the assembly stage) and synchronises nothing.  It reads the forces where the solve wrote them and needs neither a prediction nor
+ * margins.  HMPC_E_ARG, nothing enqueued, when no solve of the current batch has been enqueued.
+ * hmpc_set_device_certificate: caller-owned device buffers for later certificates (any may be NULL = the handle's own, allocated for
+ * max_batch by the first call that needs them; never inside hmpc_solve).  hmpc_get_device_certificate: where the next certificate
+ * goes; any pointer may be NULL.  hmpc_download_certificate waits for the stream of the last call, then copies (any pointer may be
+ * NULL); HMPC_E_ARG when nothing has been computed since the last solve of the current batch.  It does NOT run the safe pass.
+ * hmpc_certificate_penalty enqueues one launch: device_penalty_out[i] = +inf if for some k < 3 with a non-NaN ceil[k] the test
+ * summary[i][k] <= ceil[k] is false (a NaN summary therefore masks), else device_penalty_in[i] (+0.0 when device_penalty_in is NULL).
+ * In-place is allowed.  The output is a device_penalty of hmpc_sweep_select.  HMPC_E_ARG without a certificate of the last solve.
+ * hmpc_set_sweep_certificate_ceiling: ceil[3] for hmpc_tick_sweep_device, NULL = off (the default).  When set, the tick enqueues the
+ * certificate and its penalty between its prediction and its selection, behind the margin penalty when a margin floor is set as well
+ * (chained through the same scratch of the handle).  When off the tick enqueues exactly the launches it did without.
+ * Device groups: per member, through hmpc_group_member. */
+int hmpc_kkt_certificate(hmpc_handle *h, void *stream);
+int hmpc_set_device_certificate(hmpc_handle *h, double *device_grad, double *device_lambda, double *device_resid, double *device_summary,
+                                int32_t *device_where);
+int hmpc_get_device_certificate(hmpc_handle *h, double **device_grad, double **device_lambda, double **device_resid, double **device_summary,
+                                int32_t **device_where);
+int hmpc_download_certificate(hmpc_handle *h, double *grad, double *lambda, double *resid, double *summary, int32_t *where);
+int hmpc_set_certificate_tolerance(hmpc_handle *h, double act_tol);
+int hmpc_certificate_penalty(hmpc_handle *h, const double ceil[3], const double *device_penalty_in, double *device_penalty_out, void *stream);
+int hmpc_set_sweep_certificate_ceiling(hmpc_handle *h, const double ceil[3]);
+/* ... of the process-global solver behind setup_problem / update_problem_data: multiplier j (0..9) of `contact` (0, 1) at `step`
+ * (0..horizon-1), and summary[0] (the stationarity residual), of the last solution.  Computed lazily, once per solve, on first use (one
+ * launch, two copies).  0 before the first solve and for out-of-range arguments, as get_solution. */
+double hmpc_legacy_multiplier(int step, int contact, int j);
+double hmpc_legacy_stationarity(void);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size

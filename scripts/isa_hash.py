@@ -9,7 +9,7 @@ with: the kernel's instructions as llvm-objdump prints them (addresses and symbo
 per kernel symbol.  Two builds with the same hash run the same instructions.  --diff pairs kernels across a rename: an old
 row whose name is gone is matched to a new kernel with the same hash and instruction count; only what stays unmatched is
 CHANGED / NEW / MISSING.  --unit adds the kernels of another translation unit of csrc/ (hmpc_predict.hip, hmpc_select.hip,
-hmpc_margins.hip, the builder kernels of hmpc_builder.hip) to the listing."""
+hmpc_margins.hip, hmpc_certificate.hip, the builder kernels of hmpc_builder.hip) to the listing."""
 import concurrent.futures
 import hashlib
 import os

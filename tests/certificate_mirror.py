@@ -1,0 +1,321 @@
+"""numpy restatement (float64) of the KKT certificate's definition (include/hector_mpc.h hmpc_kkt_certificate; csrc/hmpc_certificate.h),
+fed with the oracle's binary32 assembly of a record and a force vector, and what the certificate tests share: the bounds, the map from
+qpOASES' dual solution to one-sided multipliers, the 1 N perturbation and the penalty rule.  The NNLS is the algorithm of the
+definition's point 6 in plain Python (no scipy); numpy has no fma, so the GPU's chains differ from these by binary64 round-off only."""
+import numpy as np
+
+import margins_mirror as mm
+import prediction_mirror as pm
+from hector_simulation_amd import records, synthetic
+
+ACT_TOL = 1e-3
+SRC = (0, 1, 2, 3, 4, 4, 5, 6, 7, 7)
+SIGMA = np.array([1.0, 1.0, 1.0, 1.0, 1.0, -1.0, -1.0, -1.0, 1.0, -1.0])
+PIVOT = 1e-12
+STEPS = 32
+# G_bound_r = G_FACTOR 2^-24 (sum_j |H_rj||u_j| + |g_r|): the costate gradient against H32 u + g32 of the oracle's binary32 assembly; the
+# factor is 2 x the kappa of 3.8 measured at random forces on the six shapes of prediction_mirror.SHAPES.
+G_FACTOR = 8.0
+# D_bound_r = 2^-40 (the same magnitude sum): the round-off between the GPU's fma chains and numpy's.  Each chain has <= 620 roundings of
+# <= 2^-53 each (620 < 2^10, with 2^3 to spare); the magnitude sum dominates because x - traj cancels where |g| does not.
+D_FACTOR = 2.0 ** -40
+
+
+def cols(c, nc):
+    return [3 * c, 3 * c + 1, 3 * c + 2, 3 * nc + 3 * c, 3 * nc + 3 * c + 1, 3 * nc + 3 * c + 2]
+
+
+def normals(Fc, c, nc):
+    """N[6, 10]: column j' = sigma_j' Fc[8 c + src(j')][cols(c)], float64."""
+    F = np.asarray(Fc, dtype=np.float64)
+    return np.stack([SIGMA[j] * F[8 * c + SRC[j], cols(c, nc)] for j in range(10)], axis=1)
+
+
+def gradient(Acd, Bcd, x0, u, weights, traj, alpha):
+    """grad[h, U] of one instance by the costate recursion; every chain in ascending index order from +0, dense."""
+    A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+    u = np.asarray(u, dtype=np.float64)
+    h, U = u.shape
+    x, _ = pm.rollout(Acd, Bcd, x0, u, weights, traj, alpha)  # x[i - 1] = x_i
+    w = np.asarray(weights, dtype=np.float64)
+    tr = np.asarray(traj, dtype=np.float64).reshape(h, 12)
+    al = np.asarray(alpha, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = np.zeros((h + 2, 13))
+        for i in range(h, 0, -1):
+            q = np.zeros(13)
+            q[:12] = (w + w) * (x[i - 1, :12] - tr[i - 1])
+            if i < h:
+                acc = np.zeros(13)
+                for k in range(13):
+                    acc = acc + A[k, :] * p[i + 1, k]
+                q = q + acc
+            p[i] = q
+        grad = np.zeros((h, U))
+        for i in range(h):
+            acc = np.zeros(U)
+            for k in range(13):
+                acc = acc + B[k, :] * p[i + 1, k]
+            grad[i] = (al + al) * u[i] + acc
+    return grad
+
+
+def nnls(N, r, active):
+    """Lawson-Hanson over the columns `active` (ascending j') of N[6, 10]: (lambda[10] >= 0, e[6] = r - N lambda).  The steps, their order
+    and their stopping rules are those of nnls_leg_step (csrc/hmpc_certificate.h)."""
+    N = np.asarray(N, dtype=np.float64)
+    r = np.asarray(r, dtype=np.float64)
+    lam = np.zeros(10)
+    P, L = [], np.zeros((6, 6))
+    barred = set()
+
+    def residual():
+        acc = np.zeros(6)
+        for j in range(10):
+            acc = acc + N[:, j] * lam[j]
+        return r - acc
+
+    def dot(a, b):
+        acc = 0.0
+        for k in range(6):
+            acc = acc + a[k] * b[k]
+        return acc
+
+    def append(j):
+        m = len(P)
+        if m >= 6:
+            return False
+        djj = dot(N[:, j], N[:, j])
+        ss, row = 0.0, np.zeros(6)
+        for a in range(m):
+            v = dot(N[:, P[a]], N[:, j])
+            for b in range(a):
+                v = v - L[a, b] * row[b]
+            v = v / L[a, a]
+            row[a] = v
+            ss = ss + v * v
+        d = djj - ss
+        if not (d >= PIVOT * djj and d > 0.0):
+            return False
+        row[m] = np.sqrt(d)
+        L[m, :] = row
+        P.append(j)
+        return True
+
+    def solve():
+        m = len(P)
+        y, z = np.zeros(6), np.zeros(6)
+        for a in range(m):
+            v = dot(N[:, P[a]], r)
+            for b in range(a):
+                v = v - L[a, b] * y[b]
+            y[a] = v / L[a, a]
+        finite = True
+        for a in range(m - 1, -1, -1):
+            v = y[a]
+            for b in range(a + 1, m):
+                v = v - L[b, a] * z[b]
+            v = v / L[a, a]
+            z[a] = v
+            finite = finite and (v - v == 0.0)
+        return z, finite
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        e = residual()
+        outer = inner = 0
+        stop = False
+        while not stop and outer < STEPS:
+            js, wbest = -1, 0.0
+            for j in active:
+                if j in P or j in barred:
+                    continue
+                w = dot(N[:, j], e)
+                if w > wbest:
+                    wbest, js = w, j
+            if js < 0:
+                break
+            outer += 1
+            if not append(js):
+                barred.add(js)
+                continue
+            z, finite = solve()
+            if not finite:
+                break
+            if not (z[len(P) - 1] > 0.0):
+                P.pop()
+                barred.add(js)
+                continue
+            while True:
+                amin, jmin, al = -1, 16, 0.0
+                for a in range(len(P)):
+                    if not (z[a] > 0.0):
+                        la = lam[P[a]]
+                        t = la / (la - z[a])
+                        if not (t >= 0.0):
+                            t = 0.0
+                        if amin < 0 or t < al or (t == al and P[a] < jmin):
+                            amin, jmin, al = a, P[a], t
+                if amin < 0:
+                    for a in range(len(P)):
+                        lam[P[a]] = z[a]
+                    break
+                if inner >= STEPS:
+                    stop = True
+                    break
+                inner += 1
+                keep = []
+                for a in range(len(P)):
+                    ja = P[a]
+                    v = lam[ja] + al * (z[a] - lam[ja])
+                    if not (v > 0.0) or a == amin:
+                        v = 0.0
+                    lam[ja] = v
+                    if v > 0.0:
+                        keep.append(ja)
+                del P[:]
+                for ja in keep:
+                    if not append(ja):
+                        stop = True
+                        break
+                if stop:
+                    break
+                z, finite = solve()
+                if not finite:
+                    stop = True
+                    break
+            if stop:
+                break
+            e = residual()
+            barred.clear()
+        e = residual()
+    return lam, e
+
+
+def active_set(slack10, act_tol=ACT_TOL):
+    with np.errstate(invalid="ignore"):
+        return [j for j in range(10) if slack10[j] <= act_tol]
+
+
+def cert_max(cands):
+    """(value, index) maximum of [(v, idx)]: NaN counts as +inf; greater wins, equal with a lower index wins; none: (0, -1)."""
+    best_v, best_i = -1.0, np.iinfo(np.int32).max
+    for v, i in cands:
+        v = np.inf if np.isnan(v) else v
+        if v > best_v or (v == best_v and i < best_i):
+            best_v, best_i = v, i
+    return (0.0, -1) if best_i == np.iinfo(np.int32).max else (float(best_v), int(best_i))
+
+
+def summarise(grad, lam, resid, slack, stance, act_tol=ACT_TOL):
+    """(summary[4], where[2]) of one instance from its per-leg-step arrays: grad[h, U], lam[h, nc, 10], resid[h, nc, 6], slack[h, nc, 10],
+    stance[h, nc] bool."""
+    h, nc = stance.shape
+    c0, c1, c2, c3 = [], [], [], []
+    with np.errstate(invalid="ignore"):
+        for i in range(h):
+            for c in range(nc):
+                if not stance[i, c]:
+                    continue
+                ls = nc * i + c
+                r = grad[i, cols(c, nc)]
+                for k in range(6):
+                    c0.append((abs(resid[i, c, k]), 6 * ls + k))
+                    c3.append((abs(r[k]), 6 * ls + k))
+                for j in range(10):
+                    s = slack[i, c, j]
+                    if s <= act_tol:
+                        c1.append((lam[i, c, j] * (s if s > 0.0 else 0.0), 10 * ls + j))
+                    c2.append(((0.0 - s) if s < 0.0 else (0.0 if s == s else s), 10 * ls + j))
+    out = [cert_max(c) for c in (c0, c1, c2, c3)]
+    return np.array([o[0] for o in out]), np.array([out[0][1], out[1][1]], dtype=np.int32)
+
+
+def certificate_instance(o, un_k, u, h, nc, caps, act_tol=ACT_TOL):
+    """The definition for one instance from the oracle's assembly `o`, the unpacked record fields and forces u[h, 6 nc]."""
+    u = np.asarray(u).reshape(h, 6 * nc)
+    grad = gradient(o["Acd"], o["Bcd"], o["x0"], u, un_k["weights"], un_k["traj"], un_k["Alpha_K"])
+    slack, _ = mm.slacks(o["Fc"], u, un_k["gait"], caps)
+    stance, _ = mm.stance_mask(un_k["gait"], caps, h, nc)
+    lam, resid = np.zeros((h, nc, 10)), np.zeros((h, nc, 6))
+    for i in range(h):
+        for c in range(nc):
+            if stance[i, c]:
+                lam[i, c], resid[i, c] = nnls(normals(o["Fc"], c, nc), grad[i, cols(c, nc)], active_set(slack[i, c], act_tol))
+    summary, where = summarise(grad, lam, resid, slack, stance, act_tol)
+    return dict(grad=grad, slack=slack, stance=stance, resid=resid, summary=summary, where=where, **{"lambda": lam})
+
+
+def unpacked_row(un, k):
+    return {key: np.asarray(un[key][k]) for key in ("weights", "traj", "Alpha_K", "gait")}
+
+
+def batch_caps_row(un, k, nc):
+    return [np.float32(synthetic.F_MAX)] * 2 + ([np.float32(np.asarray(un["f_max_hand"][k]).reshape(-1)[0])] if nc == 3 else [])
+
+
+def certificate_records(oracle, rec, h, nc, forces, mu=None, act_tol=ACT_TOL, with_bounds=False):
+    """The definition over a batch of packed records: dict of grad[b, h, U], lambda[b, h, nc, 10], resid[b, h, nc, 6], slack, stance,
+    summary[b, 4], where[b, 2] (and, with_bounds, Hu_g / G_bound / D_bound [b, h, U] from the oracle's binary32 H and g)."""
+    un = records.unpack_records(rec, h, nc)
+    b = rec.shape[0]
+    rows = []
+    for k in range(b):
+        o = mm.assemble(oracle, rec[k], h, nc, None if mu is None else mu[k])
+        d = certificate_instance(o, unpacked_row(un, k), forces[k], h, nc, batch_caps_row(un, k, nc), act_tol)
+        d["N"] = [normals(o["Fc"], c, nc) for c in range(nc)]
+        if with_bounds:
+            d["Hu_g"], d["G_bound"], d["D_bound"] = row_bounds(o["H"], o["g"], forces[k], h, nc)
+        rows.append(d)
+    out = {key: np.stack([r[key] for r in rows]) for key in rows[0] if key != "N"}
+    out["N"] = [r["N"] for r in rows]
+    return out
+
+
+def row_bounds(H32, g32, u, h, nc):
+    """(H32 u + g32, G_bound, D_bound), each [h, U], from the oracle's binary32 H and g widened to float64."""
+    H, g = np.asarray(H32, dtype=np.float64), np.asarray(g32, dtype=np.float64)
+    uf = np.asarray(u, dtype=np.float64).reshape(-1)
+    mag = np.abs(H) @ np.abs(uf) + np.abs(g)
+    return (H @ uf + g).reshape(h, 6 * nc), (G_FACTOR * 2.0 ** -24 * mag).reshape(h, 6 * nc), (D_FACTOR * mag).reshape(h, 6 * nc)
+
+
+def qpoases_primal_dual(oracle, rec_row, h, nc):
+    """qpOASES on the reference's reduced QP of one record: (u[h, 6 nc] float64 scattered, y_one_sided[h, nc, 10] >= 0).  qpOASES' y of a
+    constraint row is > 0 at its lower side and < 0 at its upper side; the ten one-sided constraints take them by their sigma."""
+    o = oracle.assemble_record(rec_row, h, synthetic.DT_MPC, synthetic.F_MAX, reduce=True, nc=nc)
+    x, y, _, _, st = oracle.qpoases_solve(o["H_red"], o["g_red"], o["A_red"], o["lb_red"], o["ub_red"])
+    assert st == 0, st
+    u = np.zeros(6 * nc * h)
+    u[o["var_ind"]] = x
+    yc = np.zeros(8 * nc * h)
+    yc[o["con_ind"]] = y[o["n"]:]
+    yc = yc.reshape(h, nc, 8)
+    lam = np.zeros((h, nc, 10))
+    for j in range(10):
+        lam[..., j] = np.maximum(SIGMA[j] * yc[..., SRC[j]], 0.0)
+    return u.reshape(h, 6 * nc), lam
+
+
+def move_one_newton(u, gait, h, nc):
+    """The forces with 1 N moved between the step-0 Fz of the stance feet (+1 N on the one foot in single support); float32 in, float32
+    out.  u: [h, 6 nc]."""
+    out = np.array(u, dtype=np.float32).reshape(h, 6 * nc).copy()
+    g0 = np.asarray(gait).reshape(h, nc)[0, :2]
+    feet = [c for c in range(2) if g0[c]]
+    assert feet, "no stance foot at step 0"
+    out[0, 3 * feet[0] + 2] += np.float32(1.0)
+    if len(feet) == 2:
+        out[0, 3 * feet[1] + 2] -= np.float32(1.0)
+    return out
+
+
+def penalty(summary, ceil, penalty_in=None):
+    """out[i] = +inf if for some k < 3 with a non-NaN ceil[k] the test summary[i][k] <= ceil[k] is false, else penalty_in[i] or +0.0."""
+    summary, ceil = np.asarray(summary, dtype=np.float64), np.asarray(ceil, dtype=np.float64)
+    ok = np.ones(summary.shape[0], dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for k in range(3):
+            if not np.isnan(ceil[k]):
+                ok &= summary[:, k] <= ceil[k]
+    base = np.zeros(summary.shape[0]) if penalty_in is None else np.asarray(penalty_in, dtype=np.float64)
+    return np.where(ok, base, np.inf)
