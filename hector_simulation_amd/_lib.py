@@ -34,6 +34,8 @@ EXPORTS = [
     "hmpc_kkt_certificate", "hmpc_set_device_certificate", "hmpc_get_device_certificate", "hmpc_download_certificate",
     "hmpc_set_certificate_tolerance", "hmpc_certificate_penalty", "hmpc_set_sweep_certificate_ceiling", "hmpc_legacy_multiplier",
     "hmpc_legacy_stationarity",
+    "hmpc_feedback_gains", "hmpc_set_device_gains", "hmpc_get_device_gains", "hmpc_download_gains", "hmpc_first_order_wrench",
+    "hmpc_set_device_first_order", "hmpc_download_first_order", "hmpc_legacy_feedback_gain",
 ]
 
 
@@ -216,6 +218,15 @@ def load():
     L.hmpc_legacy_multiplier.restype = cd
     L.hmpc_legacy_stationarity.argtypes = []
     L.hmpc_legacy_stationarity.restype = cd
+    L.hmpc_feedback_gains.argtypes = [vp, vp]
+    L.hmpc_set_device_gains.argtypes = [vp, vp, vp, vp, vp]
+    L.hmpc_get_device_gains.argtypes = [vp] + [C.POINTER(vp)] * 4
+    L.hmpc_download_gains.argtypes = [vp, vp, vp, vp, vp]
+    L.hmpc_first_order_wrench.argtypes = [vp, vp, vp]
+    L.hmpc_set_device_first_order.argtypes = [vp, vp, vp]
+    L.hmpc_download_first_order.argtypes = [vp, vp, vp]
+    L.hmpc_legacy_feedback_gain.argtypes = [ci, ci]
+    L.hmpc_legacy_feedback_gain.restype = cd
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

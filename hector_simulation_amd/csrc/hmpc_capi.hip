@@ -889,6 +889,128 @@ int hmpc_set_sweep_certificate_ceiling(hmpc_handle *h, const double ceil[3]) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Feedback gains: du_0/dx_0 and du_0/dX_d of the QP the last solve solved, and the first-order wrench from them (hmpc_feedback.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next gains go: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int gain_buffers(hmpc_handle *h, hmpc::FeedbackOut *b) {
+  const size_t mb = (size_t)h->max_batch, u = 6 * (size_t)h->nc;
+  HIP_TRY(h->d_fb_gain.ensure(mb * u * 13));
+  HIP_TRY(h->d_fb_ref.ensure(mb * h->setup.horizon * u * 12));
+  HIP_TRY(h->d_fb_summary.ensure(mb * hmpc::FB_SUMMARY));
+  HIP_TRY(h->d_fb_free.ensure(mb * h->setup.horizon));
+  *b = {h->d_fb_gain.get(), h->d_fb_ref.get(), h->d_fb_summary.get(), h->d_fb_free.get()};
+  return HMPC_OK;
+}
+
+struct FirstOrderBuffers {
+  float *wrench;
+  double *worst;
+};
+
+static int first_order_buffers(hmpc_handle *h, FirstOrderBuffers *b) {
+  const size_t mb = (size_t)h->max_batch;
+  HIP_TRY(h->d_fo_wrench.ensure(mb * 6 * h->nc));
+  HIP_TRY(h->d_fo_worst.ensure(mb));
+  *b = {h->d_fo_wrench.get(), h->d_fo_worst.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_gains(hmpc_handle *h, double *device_gain, double *device_ref_gain, double *device_summary, int32_t *device_free_dims) {
+  if (!h) return HMPC_E_ARG;
+  h->d_fb_gain.set_caller(device_gain), h->d_fb_ref.set_caller(device_ref_gain), h->d_fb_summary.set_caller(device_summary);
+  h->d_fb_free.set_caller(device_free_dims);
+  h->results.retarget_gains();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_gains(hmpc_handle *h, double **device_gain, double **device_ref_gain, double **device_summary, int32_t **device_free_dims) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::FeedbackOut b;
+  const int rc = gain_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_gain) *device_gain = b.gain;
+  if (device_ref_gain) *device_ref_gain = b.ref_gain;
+  if (device_summary) *device_summary = b.summary;
+  if (device_free_dims) *device_free_dims = b.free_dims;
+  return HMPC_OK;
+}
+
+int hmpc_feedback_gains(hmpc_handle *h, void *stream) {
+  if (!h || !h->results.has_solve()) return HMPC_E_ARG;  // no solve of the current batch: the force buffer holds another batch's forces, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::FeedbackOut b;
+  const int rc = gain_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_feedback(h->nc, a, h->cert_act_tol, b, (hipStream_t)stream));
+  h->results.on_gains();
+  return HMPC_OK;
+}
+
+int hmpc_download_gains(hmpc_handle *h, double *gain, double *ref_gain, double *summary, int32_t *free_dims) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_gains()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::FeedbackOut b;
+  const int rc = gain_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, u = 6 * (size_t)h->nc;
+  if (gain) HIP_TRY(hipMemcpy(gain, b.gain, n * u * 13 * sizeof(double), hipMemcpyDeviceToHost));
+  if (ref_gain) HIP_TRY(hipMemcpy(ref_gain, b.ref_gain, n * h->setup.horizon * u * 12 * sizeof(double), hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, n * hmpc::FB_SUMMARY * sizeof(double), hipMemcpyDeviceToHost));
+  if (free_dims) HIP_TRY(hipMemcpy(free_dims, b.free_dims, n * h->setup.horizon * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+int hmpc_set_device_first_order(hmpc_handle *h, float *device_wrench, double *device_worst_slack) {
+  if (!h) return HMPC_E_ARG;
+  h->d_fo_wrench.set_caller(device_wrench), h->d_fo_worst.set_caller(device_worst_slack);
+  h->results.retarget_first_order();
+  return HMPC_OK;
+}
+
+int hmpc_first_order_wrench(hmpc_handle *h, const void *device_records_new, void *stream) {
+  if (!h || !device_records_new || !h->results.has_gains()) return HMPC_E_ARG;  // no gains of the last solve of this batch: the buffers hold another solve's, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::FeedbackOut g;
+  int rc = gain_buffers(h, &g);
+  if (rc != HMPC_OK) return rc;
+  FirstOrderBuffers b;
+  rc = first_order_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));
+  set_problem_args(h, a);
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_first_order(h->nc, a, (const unsigned char *)device_records_new, g, b.wrench, b.worst, (hipStream_t)stream));
+  h->results.on_first_order();
+  return HMPC_OK;
+}
+
+int hmpc_download_first_order(hmpc_handle *h, float *wrench, double *worst_slack) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_first_order()) return HMPC_E_ARG;  // nothing computed from the gains of the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  FirstOrderBuffers b;
+  const int rc = first_order_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch;
+  if (wrench) HIP_TRY(hipMemcpy(wrench, b.wrench, n * 6 * h->nc * sizeof(float), hipMemcpyDeviceToHost));
+  if (worst_slack) HIP_TRY(hipMemcpy(worst_slack, b.worst, n * sizeof(double), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

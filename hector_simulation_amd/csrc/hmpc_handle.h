@@ -9,6 +9,7 @@
 #include "hmpc_device_buffer.h"
 #include "hmpc_kernel_args.h"
 #include "hmpc_certificate.h"
+#include "hmpc_feedback.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -113,6 +114,14 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // hmpc_set_sweep_certificate_ceiling: hmpc_tick_sweep_device masks the commands whose certificate exceeds the ceiling (same scratch)
   bool sweep_ceil_on = false;
   double sweep_ceil[hmpc::CERT_CEILS] = {};
+  // feedback gains (hmpc_feedback_gains): gain [max_batch][6 nc][13], ref_gain [max_batch][horizon][6 nc][12] and summary [max_batch][2]
+  // binary64, free_dims [max_batch][horizon]; the first-order wrench (hmpc_first_order_wrench): wrench [max_batch][6 nc] binary32,
+  // worst_slack [max_batch] binary64; to the caller's buffers (hmpc_set_device_gains, hmpc_set_device_first_order) or the handle's
+  // own, allocated by the first call that needs them
+  OutputBuffer<double> d_fb_gain, d_fb_ref, d_fb_summary;
+  OutputBuffer<int32_t> d_fb_free;
+  OutputBuffer<float> d_fo_wrench;
+  OutputBuffer<double> d_fo_worst;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

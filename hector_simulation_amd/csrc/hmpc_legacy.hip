@@ -27,6 +27,8 @@ static double g_slack[10 * 2 * HMPC_MAX_HORIZON];  // hmpc_legacy_constraint_sla
 static int g_slack_valid = 0;
 static double g_lambda[10 * 2 * HMPC_MAX_HORIZON], g_cert_summary[4];  // hmpc_legacy_multiplier, hmpc_legacy_stationarity: the last solve's certificate, fetched on first use
 static int g_cert_valid = 0;
+static double g_gain[12 * 13];  // hmpc_legacy_feedback_gain: K_0 of the last solve, fetched on first use
+static int g_gain_valid = 0;
 static int g_legacy_iter_cap = 0;  // hmpc_legacy_set_max_iterations: explicit opt-in (update_solver_settings is inert, as in the reference)
 // one tick = one pinned staging buffer [record | 12h forces | status word] and one contiguous device output block, so that
 // a blocking tick costs one asynchronous H2D copy, one launch, one asynchronous D2H copy and a single synchronisation
@@ -136,6 +138,7 @@ static void solve_global(void) {
   g_pred_valid = 0;
   g_slack_valid = 0;
   g_cert_valid = 0;
+  g_gain_valid = 0;
 }
 
 void update_problem_data(double *p, double *v, double *q, double *w, double *r, double *joint_angles, double yaw,
@@ -211,6 +214,21 @@ double hmpc_legacy_multiplier(int step, int contact, int j) {
 double hmpc_legacy_stationarity(void) {
   if (!g_has_solved || !g_handle) return 0.0;
   return legacy_certificate() ? g_cert_summary[0] : 0.0;
+}
+
+double hmpc_legacy_feedback_gain(int component, int state) {
+  if (!g_has_solved || !g_handle) return 0.0;  // as get_solution: 0 before the first solve and for out-of-range arguments
+  if (component < 0 || component >= 12 || state < 0 || state >= 13) return 0.0;
+  if (!g_gain_valid) {  // once per solve, on first use: one launch and one small copy
+    int rc = hmpc_feedback_gains(g_handle, nullptr);
+    if (rc == HMPC_OK) rc = hmpc_download_gains(g_handle, g_gain, nullptr, nullptr, nullptr);
+    if (rc != HMPC_OK) {
+      fprintf(stderr, "[hector_mpc_hip] feedback gains failed (%d): %s\n", rc, hmpc_last_hip_error());
+      return 0.0;
+    }
+    g_gain_valid = 1;
+  }
+  return g_gain[13 * component + state];
 }
 
 void update_solver_settings(int max_iter, double rho, double sigma, double solver_alpha, double terminate,

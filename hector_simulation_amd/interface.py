@@ -85,6 +85,12 @@ def legacy_stationarity() -> float:
     return float(_lib.load().hmpc_legacy_stationarity())
 
 
+def legacy_feedback_gain(component: int, state: int) -> float:
+    """Entry [component][state] (0..11, 0..12) of K_0 = du_0/dx_0 of the process-global solver's last solution (include/hector_mpc.h
+    hmpc_legacy_feedback_gain); 0 before the first solve and for out-of-range arguments."""
+    return float(_lib.load().hmpc_legacy_feedback_gain(int(component), int(state)))
+
+
 def last_status() -> int:
     return int(_lib.load().hmpc_last_status())
 
@@ -385,6 +391,48 @@ class BatchedMPC:
         cl = None if ceil is None else np.ascontiguousarray(ceil, dtype=np.float64)
         assert cl is None or cl.shape == (3,)
         _check(self.L.hmpc_set_sweep_certificate_ceiling(self.h, None if cl is None else cl.ctypes.data), "hmpc_set_sweep_certificate_ceiling")
+
+    def feedback_gains(self, stream: int = 0) -> None:
+        """One launch behind the solve on ``stream``: K_0 = du_0/dx_0 and du_0/dX_d of the QP that was solved, its linearisation and the
+        active set at the forces in the force buffer frozen (include/hector_mpc.h hmpc_feedback_gains).  Raises when no solve of the
+        current batch has been enqueued."""
+        _check(self.L.hmpc_feedback_gains(self.h, C.c_void_p(stream)), "hmpc_feedback_gains")
+
+    def download_gains(self) -> dict:
+        """gain float64[batch, 6 contacts, 13], ref_gain float64[batch, horizon, 6 contacts, 12], summary float64[batch, 2] (smallest
+        Cholesky pivot ratio, max |gain|) and free_dims int32[batch, horizon].  Waits; runs no safe pass."""
+        b, hz, u = self.batch, self.horizon, 6 * self.contacts
+        out = dict(gain=np.zeros((b, u, 13), dtype=np.float64), ref_gain=np.zeros((b, hz, u, 12), dtype=np.float64),
+                   summary=np.zeros((b, 2), dtype=np.float64), free_dims=np.zeros((b, hz), dtype=np.int32))
+        _check(self.L.hmpc_download_gains(self.h, *[out[k].ctypes.data for k in ("gain", "ref_gain", "summary", "free_dims")]),
+               "hmpc_download_gains")
+        return out
+
+    def set_device_gains(self, gain_ptr: int = 0, ref_gain_ptr: int = 0, summary_ptr: int = 0, free_dims_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later gains (shapes of ``download_gains`` with max_batch rows; 0 / None = the handle's own)."""
+        self._keep_gains = keepalive
+        _check(self.L.hmpc_set_device_gains(self.h, *[C.c_void_p(int(p or 0)) for p in (gain_ptr, ref_gain_ptr, summary_ptr, free_dims_ptr)]),
+               "hmpc_set_device_gains")
+
+    def first_order_wrench(self, records_ptr: int, stream: int = 0) -> None:
+        """One launch: the step-0 wrench of every instance moved to first order to the records at ``records_ptr`` (``batch`` records of
+        this handle's stride in HBM: the same robots a moment later), by the gains of the last solve (include/hector_mpc.h
+        hmpc_first_order_wrench).  Raises without gains of the last solve."""
+        _check(self.L.hmpc_first_order_wrench(self.h, C.c_void_p(int(records_ptr or 0)), C.c_void_p(stream)), "hmpc_first_order_wrench")
+
+    def download_first_order(self) -> dict:
+        """wrench float32[batch, 6 contacts] and worst_slack float64[batch] (the least step-0 slack at that wrench; +inf with no stance
+        contact).  Waits."""
+        out = dict(wrench=np.zeros((self.batch, 6 * self.contacts), dtype=np.float32), worst_slack=np.zeros(self.batch, dtype=np.float64))
+        _check(self.L.hmpc_download_first_order(self.h, out["wrench"].ctypes.data, out["worst_slack"].ctypes.data), "hmpc_download_first_order")
+        return out
+
+    def set_device_first_order(self, wrench_ptr: int = 0, worst_slack_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later first-order wrenches (float32[max_batch, 6 contacts], float64[max_batch]; 0 / None = the
+        handle's own)."""
+        self._keep_fo = keepalive
+        _check(self.L.hmpc_set_device_first_order(self.h, C.c_void_p(int(wrench_ptr or 0)), C.c_void_p(int(worst_slack_ptr or 0))),
+               "hmpc_set_device_first_order")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

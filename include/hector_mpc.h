@@ -530,6 +530,71 @@ int hmpc_set_sweep_certificate_ceiling(hmpc_handle *h, const double ceil[3]);
  * launch, two copies).  0 before the first solve and for out-of-range arguments, as get_solution. */
 double hmpc_legacy_multiplier(int step, int contact, int j);
 double hmpc_legacy_stationarity(void);
+/* ---- the feedback gains of every solved instance; first-order force updates ----
+ * At the optimum the MPC also defines a local linear policy: how the step-0 wrench changes when the state estimate or the reference
+ * trajectory moves a little while the active limits stay the same.  Per instance, let NC be the number of contacts and U = 6 NC.  Let
+ * Acd[13][13], Bcd[13][U], Fc, the weights w[12], Alpha_K[U], the gait and the caps be the binary32 values the solve kernel's assembly
+ * stage builds for the record (hmpc_params and hmpc_set_instance_mu included), and u_i[U] step i of the force buffer as it stands.
+ * Everything below is binary64.  Every sum is one ascending chain of explicit fused multiply-adds started at +0; sums over a column
+ * (row) of Z_i run over the six rows (the columns) of its contact, all others are dense.
+ *   1. Slacks, stance rule, active set: exactly hmpc_kkt_certificate's.  j' is active iff s[i][c][j'] <= act_tol, the value of
+ *      hmpc_set_certificate_tolerance; a NaN slack is not active.
+ *   2. Free directions of stance leg-step (i, c).  The active normals n_j' (as in the certificate) are orthonormalised in R^6 in
+ *      ascending j' by modified Gram-Schmidt applied twice.  A normal is admitted, divided by its remaining length, iff fewer than six
+ *      vectors are held, its squared remainder is > 0 and it is >= 1e-12 of the normal's own squared length (the certificate's dependence
+ *      rule).  The basis is completed with unit vectors e_k: each time the one not yet taken whose squared remainder (reduced the same
+ *      way) is largest, ties to the lowest k, divided by its remaining length, until six vectors are held.  These completions are the
+ *      columns of Z_{i,c} (6 x (6 - m)); a swing leg-step has none.  Z_i (U x r_i) places every Z_{i,c} on cols(c), contacts
+ *      ascending.  free_dims[i] = r_i.
+ *   3. Backward pass.  Q = diag(w + w, 0) (13 x 13), R = diag(Alpha_K + Alpha_K), P_h = Q.  For i = h-1 .. 0, with P = P_{i+1}:
+ *      PA = P Acd, PB = P Bcd, W = R + Bcd' PB, G_i = Z_i' (W Z_i), factored by Cholesky from its lower triangle (pivot d_j = G_jj -
+ *      sum_{b<j} L_jb^2, L_jj = sqrt(d_j)); X = G_i^-1 (Z_i' Bcd') by two triangular solves; S_i = Z_i X (U x 13); K_i = 0 - S_i PA
+ *      (S_i and K_i are exactly 0 when r_i = 0).  For i > 0: M_i = Acd + Bcd K_i, P_i = Q + PA' M_i, evaluated on the upper triangle
+ *      and copied to the lower.
+ *   4. Outputs.  gain[batch][U][13] = K_0 = du_0/dx_0.  ref_gain[batch][h][U][12]: row j-1 is Psi_j[c][s] (w_s + w_s) for s < 12, with
+ *      Psi_1 = S_0 and Psi_{j+1} = Psi_j M_j'; it is du_0/dtraj of step j (traj[12 (j-1) + s]).  free_dims[batch][h], int32.
+ *      summary[batch][2]: [0] the smallest ratio d_j / G_jj over the pivots of every G_i (1 when no G_i exists; a NaN ratio counts as
+ *      0), [1] max |K_0| (a NaN entry counts as +inf).
+ *   5. Meaning.  These are the derivatives of the QP's solution in (x_0, X_d) with the linearisation (Acd, Bcd, Fc) and the active set
+ *      frozen: exact wherever the active set is locally constant.  At a weakly active limit the solution has one-sided derivatives only,
+ *      and the gain reported is the frozen set's.  Rows of a swing contact are exactly 0, and N_A' K_0 = 0 for the active normals of
+ *      every stance leg-step of step 0: a first-order update stays on the active limits.  The result is a pure function of (record,
+ *      hmpc_params, per-instance mu, force buffer, act_tol).  Instances that are not HMPC_S_OK are computed all the same.
+ *   6. Termination.  Every loop's trip count is fixed by (h, NC) and the number of vectors held; nothing iterates on data, so NaN input
+ *      ends like any other.
+ *
+ * hmpc_feedback_gains enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance, sharing nothing with the solver
+ * but the assembly stage: no H, no H^-1) and synchronises nothing.  It reads the forces where the solve wrote them.  HMPC_E_ARG, nothing
+ * enqueued, when no solve of the current batch has been enqueued.
+ * hmpc_set_device_gains: caller-owned device buffers for later gains (any may be NULL = the handle's own, allocated for max_batch by
+ * the first call that needs them; never inside hmpc_solve); moving the buffers makes gains already computed stale.
+ * hmpc_get_device_gains: where the next gains go; any pointer may be NULL.  hmpc_download_gains waits for the stream of the last call,
+ * then copies (any pointer may be NULL); HMPC_E_ARG when nothing has been computed since the last solve of the current batch.  It does
+ * NOT run the safe pass.
+ *
+ * hmpc_first_order_wrench enqueues ONE launch: device_records_new is `batch` records of the handle's stride in HBM, the same robots a
+ * moment later.  The kernel assembles x0' of the new record through the same stage function; dx = (double)x0' - (double)x0 as it is
+ * (a yaw that wraps is the caller's business, as in the reference); dt_j = (double)traj'_j - (double)traj_j.
+ *   wrench[batch][U] = (float)((double)u_0[c] + chain_c), chain_c the ascending chain of fused multiply-adds from +0 over
+ *   gain[c][s] dx[s] (s < 13), then ref_gain[j][c][s] dt_j[s] (j < h ascending, s < 12): identical records give step 0 of the force
+ *   buffer bit for bit.  worst_slack[batch]: the least of the ten step-0 slacks of every stance contact at that wrench (binary32, as
+ *   stored), against the ORIGINAL record's Fc and caps; +inf with no stance contact; a NaN slack never enters.  What to do when it goes
+ *   negative is the caller's decision.
+ * It needs gains of the last solve of the current batch (HMPC_E_ARG otherwise, and for a NULL pointer; nothing enqueued), and changes
+ * neither the force buffer nor any result state but its own.  hmpc_set_device_first_order / hmpc_download_first_order: as above.
+ * Device groups: per member, through hmpc_group_member. */
+int hmpc_feedback_gains(hmpc_handle *h, void *stream);
+int hmpc_set_device_gains(hmpc_handle *h, double *device_gain, double *device_ref_gain, double *device_summary, int32_t *device_free_dims);
+int hmpc_get_device_gains(hmpc_handle *h, double **device_gain, double **device_ref_gain, double **device_summary,
+                          int32_t **device_free_dims);
+int hmpc_download_gains(hmpc_handle *h, double *gain, double *ref_gain, double *summary, int32_t *free_dims);
+int hmpc_first_order_wrench(hmpc_handle *h, const void *device_records_new, void *stream);
+int hmpc_set_device_first_order(hmpc_handle *h, float *device_wrench, double *device_worst_slack);
+int hmpc_download_first_order(hmpc_handle *h, float *wrench, double *worst_slack);
+/* ... of the process-global solver behind setup_problem / update_problem_data: entry [component][state] (0..11, 0..12) of K_0 of the
+ * last solution.  Computed lazily, once per solve, on first use (one launch, one copy).  0 before the first solve and for
+ * out-of-range arguments, as get_solution. */
+double hmpc_legacy_feedback_gain(int component, int state);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size

@@ -1,0 +1,265 @@
+"""numpy restatement (float64) of the feedback gains' definition (include/hector_mpc.h hmpc_feedback_gains; csrc/hmpc_feedback.h), fed with
+the oracle's binary32 assembly of a record and a force vector; the dense condensed form the Riccati recursion is checked against; the
+first-order wrench; and what the feedback tests share: the perturbed records of the finite-difference test and its measured bound.
+numpy has no fma, so the GPU's chains differ from these by binary64 round-off only."""
+import numpy as np
+
+import certificate_mirror as cm
+import margins_mirror as mm
+from hector_simulation_amd import records, synthetic
+
+ACT_TOL = cm.ACT_TOL
+DEPENDENT = 1e-12
+# The Riccati gains against the dense condensed form, two different binary64 algorithms: <= MIRROR_TOL max(1, max|K|).
+MIRROR_TOL = 1e-9
+# Finite differences of the reference's qpOASES solves at +-FD_STEP against K_0 dx + sum ref_gain dt, relative to max(1, max|u|), over the
+# instances whose active set is the same in both solves: E measured 1.69e-4 over CASES (standing_3c, its trajectory step halved once) (tests/test_feedback_mirror.py prints it);
+# FD_FORCE = 2 E, the factor covering the seed-to-seed spread of the binary32 assembly noise of two independently assembled records.
+FD_STEP = 1e-3
+FD_E_MEASURED = 1.69e-4
+FD_FORCE = 2 * FD_E_MEASURED
+FD_LEFT_OUT_CAP = 0.25
+
+
+def free_directions(N, active):
+    """(number of normals admitted, V[6, 6]): the columns of V are the six orthonormal vectors held, the admitted normals first; the rest
+    are the columns of Z.  The steps and their order are those of free_directions (csrc/hmpc_feedback.h)."""
+    held = []
+
+    def reduce(v):
+        v = v.copy()
+        for _ in range(2):
+            for q in held:
+                d = 0.0
+                for k in range(6):
+                    d = d + q[k] * v[k]
+                v = v - d * q
+        return v
+
+    def norm2(v):
+        acc = 0.0
+        for k in range(6):
+            acc = acc + v[k] * v[k]
+        return acc
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for j in active:
+            v = np.asarray(N[:, j], dtype=np.float64)
+            len2 = norm2(v)
+            v = reduce(v)
+            rem2 = norm2(v)
+            if len(held) < 6 and rem2 > 0.0 and rem2 >= DEPENDENT * len2:
+                held.append(v / np.sqrt(rem2))
+        normals = len(held)
+        taken = set()
+        while len(held) < 6:
+            best, vb, rb = -1, None, 0.0
+            for k in range(6):
+                if k in taken:
+                    continue
+                v = reduce(np.eye(6)[k])
+                rem2 = norm2(v)
+                if best < 0 or rem2 > rb:
+                    best, vb, rb = k, v, rem2
+            taken.add(best)
+            held.append(vb / np.sqrt(rb))
+    return normals, np.stack(held, axis=1)
+
+
+def z_of_step(Zc, nc):
+    """Z_i[U, r_i] from the per-contact Z_{i,c} (6 x r_c, or None for a swing leg-step)."""
+    U = 6 * nc
+    blocks = []
+    for c in range(nc):
+        if Zc[c] is None or Zc[c].shape[1] == 0:
+            continue
+        z = np.zeros((U, Zc[c].shape[1]))
+        z[cm.cols(c, nc), :] = Zc[c]
+        blocks.append(z)
+    return np.concatenate(blocks, axis=1) if blocks else np.zeros((U, 0))
+
+
+def cholesky_lower(G):
+    """(L, the pivot ratios d_j / G_jj) by the kernel's column order; a failed pivot propagates NaN."""
+    r = G.shape[0]
+    L, ratio = np.zeros((r, r)), np.zeros(r)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for j in range(r):
+            d = G[j, j] - float(np.sum(L[j, :j] * L[j, :j]))
+            ratio[j] = d / G[j, j]
+            L[j, j] = np.sqrt(d)
+            for a in range(j + 1, r):
+                L[a, j] = (G[a, j] - float(np.sum(L[a, :j] * L[j, :j]))) / L[j, j]
+    return L, ratio
+
+
+def riccati(Acd, Bcd, weights, alpha, Z):
+    """gain[U, 13], ref_gain[h, U, 12], summary[2] from the binary32 model widened to float64 and Z = [Z_0 .. Z_{h-1}] (each U x r_i)."""
+    A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+    w, al = np.asarray(weights, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+    h, U = len(Z), B.shape[1]
+    q2 = np.concatenate([w + w, [0.0]])
+    Q, R = np.diag(q2), np.diag(al + al)
+    P = Q.copy()
+    M = [None] * h
+    pivmin = 1.0
+    K = S = np.zeros((U, 13))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for i in range(h - 1, -1, -1):
+            PA, PB = P @ A, P @ B
+            Zi = Z[i]
+            if Zi.shape[1] > 0:
+                W = R + B.T @ PB
+                G = Zi.T @ (W @ Zi)
+                L, ratio = cholesky_lower(np.tril(G) + np.tril(G, -1).T)
+                for p in ratio:
+                    v = 0.0 if np.isnan(p) else p
+                    pivmin = v if v < pivmin else pivmin
+                X = Zi.T @ B.T
+                X = np.linalg.solve(L.T, np.linalg.solve(L, X)) if np.isfinite(L).all() else np.full_like(X, np.nan)
+                S = Zi @ X
+                K = 0.0 - S @ PA
+            else:
+                S, K = np.zeros((U, 13)), np.zeros((U, 13))
+            if i > 0:
+                M[i] = A + B @ K
+                Pn = Q + PA.T @ M[i]
+                P = np.triu(Pn) + np.triu(Pn, 1).T
+        ref = np.zeros((h, U, 12))
+        Psi = S
+        for j in range(1, h + 1):
+            ref[j - 1] = Psi[:, :12] * q2[None, :12]
+            if j < h:
+                Psi = Psi @ M[j].T
+        a = np.abs(K)
+        kmax = float(np.where(np.isnan(a), np.inf, a).max())
+    return K, ref, np.array([pivmin, kmax])
+
+
+def dense_gains(Acd, Bcd, weights, alpha, Z):
+    """The same derivatives from the condensed QP: -[Zf (Zf' H Zf)^-1 Zf' 2 Bq' S Aq] rows 0..U-1 and +[... 2 Bq' S], with H = 2 (Bq' S Bq +
+    alpha) built in float64 from powers of Acd and Bcd, Zf = blockdiag(Z_i).  Returns (gain[U, 13], ref_gain[h, U, 12])."""
+    A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+    w, al = np.asarray(weights, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+    h, U = len(Z), B.shape[1]
+    Ap = [np.eye(13)]
+    for _ in range(h):
+        Ap.append(A @ Ap[-1])
+    Aq = np.concatenate(Ap[1:], axis=0)  # [13 h, 13]
+    Bq = np.zeros((13 * h, U * h))
+    for i in range(1, h + 1):
+        for k in range(i):
+            Bq[13 * (i - 1):13 * i, U * k:U * (k + 1)] = Ap[i - 1 - k] @ B
+    S = np.diag(np.tile(np.concatenate([w, [0.0]]), h))
+    H = 2.0 * (Bq.T @ S @ Bq + np.diag(np.tile(al, h)))
+    r = [z.shape[1] for z in Z]
+    Zf = np.zeros((U * h, sum(r)))
+    o = 0
+    for i in range(h):
+        Zf[U * i:U * (i + 1), o:o + r[i]] = Z[i]
+        o += r[i]
+    if Zf.shape[1] == 0:
+        return np.zeros((U, 13)), np.zeros((h, U, 12))
+    T = Zf @ np.linalg.solve(Zf.T @ H @ Zf, Zf.T @ (2.0 * Bq.T @ S))  # [U h, 13 h]
+    gain = -(T @ Aq)[:U]
+    ref = T[:U].reshape(U, h, 13)[:, :, :12].transpose(1, 0, 2)
+    return gain, ref
+
+
+def gains_instance(o, un_k, u, h, nc, caps, act_tol=ACT_TOL):
+    """The definition for one instance from the oracle's assembly `o`, the unpacked record fields and forces u[h, 6 nc]."""
+    u = np.asarray(u).reshape(h, 6 * nc)
+    slack, _ = mm.slacks(o["Fc"], u, un_k["gait"], caps)
+    stance, _ = mm.stance_mask(un_k["gait"], caps, h, nc)
+    N = [cm.normals(o["Fc"], c, nc) for c in range(nc)]
+    Z, free_dims, active = [], np.zeros(h, dtype=np.int32), {}
+    for i in range(h):
+        Zc = []
+        for c in range(nc):
+            if not stance[i, c]:
+                Zc.append(None)
+                continue
+            active[(i, c)] = cm.active_set(slack[i, c], act_tol)
+            m, V = free_directions(N[c], active[(i, c)])
+            Zc.append(V[:, m:])
+        Z.append(z_of_step(Zc, nc))
+        free_dims[i] = Z[-1].shape[1]
+    gain, ref, summary = riccati(o["Acd"], o["Bcd"], un_k["weights"], un_k["Alpha_K"], Z)
+    return dict(gain=gain, ref_gain=ref, summary=summary, free_dims=free_dims, Z=Z, N=N, active=active, stance=stance, slack=slack)
+
+
+def gains_records(oracle, rec, h, nc, forces, mu=None, act_tol=ACT_TOL, with_dense=False):
+    """The definition over a batch of packed records: dict of gain[b, U, 13], ref_gain[b, h, U, 12], summary[b, 2], free_dims[b, h], stance,
+    slack, the lists Z / N / active per instance (and, with_dense, dense_gain / dense_ref_gain from the condensed form on the same Z)."""
+    un = records.unpack_records(rec, h, nc)
+    rows = []
+    for k in range(rec.shape[0]):
+        o = mm.assemble(oracle, rec[k], h, nc, None if mu is None else mu[k])
+        unk = cm.unpacked_row(un, k)
+        d = gains_instance(o, unk, forces[k], h, nc, cm.batch_caps_row(un, k, nc), act_tol)
+        d["x0"] = o["x0"].astype(np.float64)
+        d["Acd"], d["Bcd"], d["Fc"] = o["Acd"], o["Bcd"], o["Fc"]
+        if with_dense:
+            d["dense_gain"], d["dense_ref_gain"] = dense_gains(o["Acd"], o["Bcd"], unk["weights"], unk["Alpha_K"], d["Z"])
+        rows.append(d)
+    lists = ("Z", "N", "active")
+    out = {key: np.stack([r[key] for r in rows]) for key in rows[0] if key not in lists}
+    for key in lists:
+        out[key] = [r[key] for r in rows]
+    return out
+
+
+def unconstrained_gain(oracle, rec_row, h, nc):
+    """K_0 of the Riccati recursion with every stance leg-step free (r = 6 per stance contact)."""
+    un = records.unpack_records(rec_row[None, :], h, nc)
+    o = mm.assemble(oracle, rec_row, h, nc)
+    stance, _ = mm.stance_mask(un["gait"][0], cm.batch_caps_row(un, 0, nc), h, nc)
+    Z = [z_of_step([np.eye(6) if stance[i, c] else None for c in range(nc)], nc) for i in range(h)]
+    return riccati(o["Acd"], o["Bcd"], un["weights"][0], un["Alpha_K"][0], Z)[0]
+
+
+def perturbed_records(rec, h, nc, seed, step=FD_STEP, traj_step=None):
+    """The records with p, v, w and the trajectory of every instance moved by uniform +-step (the trajectory by +-traj_step): the same
+    robots a moment later, orientation and feet as they were, so that Acd and Bcd stay bit for bit."""
+    rng = np.random.default_rng(seed)
+    f = {k: np.array(v, copy=True) for k, v in records.unpack_records(rec, h, nc).items()}
+    for key in ("p", "v", "w"):
+        f[key] = (f[key].astype(np.float64) + rng.uniform(-step, step, f[key].shape)).astype(np.float32)
+    ts = step if traj_step is None else traj_step
+    f["traj"] = (f["traj"].astype(np.float64) + rng.uniform(-ts, ts, f["traj"].shape)).astype(np.float32)
+    return records.pack_records(f, h, nc)
+
+
+def deltas(oracle, rec, rec_new, h, nc):
+    """(dx[b, 13], dt[b, h, 12]) in float64 from the oracle's binary32 x0 of both records and their trajectories."""
+    un, un2 = records.unpack_records(rec, h, nc), records.unpack_records(rec_new, h, nc)
+    b = rec.shape[0]
+    dx = np.zeros((b, 13))
+    for k in range(b):
+        dx[k] = mm.assemble(oracle, rec_new[k], h, nc)["x0"].astype(np.float64) - mm.assemble(oracle, rec[k], h, nc)["x0"].astype(np.float64)
+    dt = np.asarray(un2["traj"], dtype=np.float64).reshape(b, h, 12) - np.asarray(un["traj"], dtype=np.float64).reshape(b, h, 12)
+    return dx, dt
+
+
+def first_order(gain, ref_gain, dx, dt, u0):
+    """wrench[U] float32 = (float)(u0 + chain): the 13 state terms, then the 12 h reference terms, ascending from +0."""
+    U = gain.shape[0]
+    acc = np.zeros(U)
+    for s in range(13):
+        acc = acc + gain[:, s] * dx[s]
+    for j in range(ref_gain.shape[0]):
+        for s in range(12):
+            acc = acc + ref_gain[j, :, s] * dt[j, s]
+    return (np.asarray(u0, dtype=np.float64) + acc).astype(np.float32), acc
+
+
+def same_active_sets(a, b):
+    """Per instance: the two dicts (leg-step -> list of active j') agree."""
+    return np.array([x == y for x, y in zip(a, b)])
+
+
+def qpoases_forces(oracle, rec, h, nc):
+    """The reference's qpOASES forces of every record, float64[b, h, 6 nc]; all must solve."""
+    r = oracle.solve_records(rec, h, synthetic.DT_MPC, synthetic.F_MAX, nc=nc)
+    assert r["n_bad"] == 0, r["n_bad"]
+    return r["q_soln"].reshape(rec.shape[0], h, 6 * nc)
