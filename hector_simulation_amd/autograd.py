@@ -1,0 +1,71 @@
+"""``loss.backward()`` through a batched solve: a ``torch.autograd.Function`` over ``BatchedMPC.solve`` whose backward is ONE launch of
+the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.hip).
+
+    forces = differentiable_solve(mpc, fields, traj, weights, alpha_k)     # CUDA float32 [b, h * 6 contacts]
+    loss(forces).backward()                                                # traj.grad, weights.grad, alpha_k.grad
+
+The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
+constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
+stay available through ``mpc.download_adjoint()``.  A backward is refused when the ``BatchedMPC`` object has uploaded, solved or been given
+other records or outputs since its forward (``BatchedMPC.generation``); calls made on the C handle behind the object's back are not seen."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import records
+
+
+def _buffers(mpc, device):
+    """Caller-owned adjoint buffers of ``mpc`` as torch tensors (made once per handle, for max_batch rows), and the handle pointed at
+    them: a ``set_device_adjoint`` of the user's since the last backward is undone here, so that what backward reads is what the launch
+    writes."""
+    buf = getattr(mpc, "_autograd_buffers", None)
+    if buf is None:
+        b, hz, u = mpc.max_batch, mpc.horizon, 6 * mpc.contacts
+        shapes = dict(grad_x0=(b, 13), grad_traj=(b, hz, 12), grad_weights=(b, 12), grad_alpha=(b, u), dir=(b, hz, u), summary=(b, 2))
+        buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_buffers = buf
+    if mpc.get_device_adjoint() != {k: buf[k].data_ptr() for k in mpc.ADJOINT_KEYS}:
+        mpc.set_device_adjoint(*[buf[k].data_ptr() for k in mpc.ADJOINT_KEYS], keepalive=buf)
+    return buf
+
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mpc, fields, traj, weights, alpha_k):
+        f = dict(fields)
+        f["traj"] = traj.detach().cpu().numpy()
+        f["weights"] = weights.detach().cpu().numpy()
+        f["Alpha_K"] = alpha_k.detach().cpu().numpy()
+        device = torch.device("cuda", mpc.device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        mpc.upload(records.pack_records(f, mpc.horizon, mpc.contacts))
+        mpc.solve(stream)
+        forces, _ = mpc.download()  # (the safe pass: repaired forces, in the handle's force buffer as well)
+        ctx.mpc, ctx.generation, ctx.device = mpc, mpc.generation, device  # (after the download: the safe pass replaces no batch)
+        ctx.meta = [(t.shape, t.dtype, t.device) for t in (traj, weights, alpha_k)]
+        return torch.from_numpy(np.ascontiguousarray(forces)).to(device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        mpc = ctx.mpc
+        if mpc.generation != ctx.generation:  # an upload, a solve, new records or outputs through this object since the forward
+            raise RuntimeError("differentiable_solve: the handle has solved another batch since this forward; its forces are gone")
+        b = mpc.batch
+        buf = _buffers(mpc, ctx.device)
+        seed = grad_output.detach().to(device=ctx.device, dtype=torch.float64).contiguous()
+        mpc.solve_adjoint(seed.data_ptr(), torch.cuda.current_stream(ctx.device).cuda_stream)
+        grads = []
+        for key, (shape, dtype, dev), need in zip(("grad_traj", "grad_weights", "grad_alpha"), ctx.meta, ctx.needs_input_grad[2:]):
+            # (a copy in every case: a float64 leaf on the handle's device would otherwise get a view of the handle's own buffer as
+            #  its .grad, which the next launch overwrites)
+            grads.append(buf[key][:b].to(device=dev, dtype=dtype, copy=True).reshape(shape) if need else None)
+        return (None, None) + tuple(grads)
+
+
+def differentiable_solve(mpc, fields, traj, weights, alpha_k):
+    """Solves the batch ``fields`` (the dict ``records.pack_records`` takes) with its reference trajectory, tracking weights and Alpha_K
+    replaced by the tensors ``traj`` [b, 12 h], ``weights`` [b, 12] and ``alpha_k`` [b, 6 contacts] (any device, any float dtype), and returns
+    the forces as a CUDA float32 tensor [b, h * 6 contacts] that autograd differentiates in those three."""
+    return _Solve.apply(mpc, fields, traj, weights, alpha_k)

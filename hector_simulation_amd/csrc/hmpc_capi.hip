@@ -1011,6 +1011,83 @@ int hmpc_download_first_order(hmpc_handle *h, float *wrench, double *worst_slack
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Adjoint: the gradients of a loss over the force trajectory in the state, the reference, the weights and Alpha_K (hmpc_adjoint.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next adjoint goes: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int adjoint_buffers(hmpc_handle *h, hmpc::AdjointOut *b) {
+  const size_t mb = (size_t)h->max_batch, u = 6 * (size_t)h->nc, hz = (size_t)h->setup.horizon;
+  HIP_TRY(h->d_adj_x0.ensure(mb * 13));
+  HIP_TRY(h->d_adj_traj.ensure(mb * hz * 12));
+  HIP_TRY(h->d_adj_weights.ensure(mb * 12));
+  HIP_TRY(h->d_adj_alpha.ensure(mb * u));
+  HIP_TRY(h->d_adj_dir.ensure(mb * hz * u));
+  HIP_TRY(h->d_adj_summary.ensure(mb * hmpc::ADJ_SUMMARY));
+  *b = {h->d_adj_x0.get(), h->d_adj_traj.get(), h->d_adj_weights.get(), h->d_adj_alpha.get(), h->d_adj_dir.get(), h->d_adj_summary.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_adjoint(hmpc_handle *h, double *device_grad_x0, double *device_grad_traj, double *device_grad_weights,
+                            double *device_grad_alpha, double *device_dir, double *device_summary) {
+  if (!h) return HMPC_E_ARG;
+  h->d_adj_x0.set_caller(device_grad_x0), h->d_adj_traj.set_caller(device_grad_traj), h->d_adj_weights.set_caller(device_grad_weights);
+  h->d_adj_alpha.set_caller(device_grad_alpha), h->d_adj_dir.set_caller(device_dir), h->d_adj_summary.set_caller(device_summary);
+  h->results.retarget_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint(hmpc_handle *h, double **device_grad_x0, double **device_grad_traj, double **device_grad_weights,
+                            double **device_grad_alpha, double **device_dir, double **device_summary) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::AdjointOut b;
+  const int rc = adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_grad_x0) *device_grad_x0 = b.grad_x0;
+  if (device_grad_traj) *device_grad_traj = b.grad_traj;
+  if (device_grad_weights) *device_grad_weights = b.grad_weights;
+  if (device_grad_alpha) *device_grad_alpha = b.grad_alpha;
+  if (device_dir) *device_dir = b.dir;
+  if (device_summary) *device_summary = b.summary;
+  return HMPC_OK;
+}
+
+int hmpc_solve_adjoint(hmpc_handle *h, const double *device_seed, void *stream) {
+  if (!h || !device_seed || !h->results.has_solve()) return HMPC_E_ARG;  // no solve of the current batch: the force buffer holds another batch's forces, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::AdjointOut b;
+  const int rc = adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_adjoint(h->nc, a, h->cert_act_tol, device_seed, b, (hipStream_t)stream));
+  h->results.on_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
+                          double *summary) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_adjoint()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::AdjointOut b;
+  const int rc = adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, u = 6 * (size_t)h->nc, hz = (size_t)h->setup.horizon, d = sizeof(double);
+  if (grad_x0) HIP_TRY(hipMemcpy(grad_x0, b.grad_x0, n * 13 * d, hipMemcpyDeviceToHost));
+  if (grad_traj) HIP_TRY(hipMemcpy(grad_traj, b.grad_traj, n * hz * 12 * d, hipMemcpyDeviceToHost));
+  if (grad_weights) HIP_TRY(hipMemcpy(grad_weights, b.grad_weights, n * 12 * d, hipMemcpyDeviceToHost));
+  if (grad_alpha) HIP_TRY(hipMemcpy(grad_alpha, b.grad_alpha, n * u * d, hipMemcpyDeviceToHost));
+  if (dir) HIP_TRY(hipMemcpy(dir, b.dir, n * hz * u * d, hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, n * hmpc::ADJ_SUMMARY * d, hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

@@ -23,6 +23,8 @@
 //   gain = K_0;  Psi_1 = S_0, Psi_{j+1} = Psi_j M_j';  ref_gain[j-1][c][s] = Psi_j[c][s] (w_s + w_s), s < 12.
 //   summary[0] = min over all pivots of d_j / G_jj (NaN counting as 0; 1 with no pivot), summary[1] = max |K_0| (NaN counting as +inf).
 // Every loop's trip count is fixed by (h, NC) and the number of held vectors (<= 6): nothing iterates on data.
+// A step of the backward pass is riccati_gain_step + riccati_cost_step, which the adjoint (hmpc_adjoint.h) compiles too, with its vector
+// recursion switched on.
 // Mapping: the NC h Gram-Schmidt problems run one per lane before the backward pass (they do not depend on P), each on the 36 doubles
 // of its own slot of Z; the products of a step are spread over all NT lanes, one output entry per lane and pass, a barrier between
 // dependent products; the Cholesky factor is built column by column (lane a owns row a; one barrier per column), the 13 right-hand
@@ -144,6 +146,239 @@ __device__ __forceinline__ int free_directions(const float *Fc, const int c, con
   return normals;
 }
 
+// What the adjoint's vector recursion (hmpc_adjoint.h) adds to a step of the backward pass: l_i, p_{i+1}, where p_i and k_i go.  The gains
+// leave it empty.
+struct RiccatiVec {
+  const double *ell = nullptr, *p = nullptr;
+  double *p_next = nullptr, *k = nullptr;
+};
+
+// Step i of the backward pass up to K_i, by the NT lanes of the workgroup (every lane calls it; P = P_{i+1} in Wk.P on entry, behind a
+// barrier; the caller puts a barrier behind it): PA, PB, W, G, the Cholesky factor, X, S_i (Wk.S), K_i (K[U][13]).  With
+// riccati_cost_step the matrix step that feedback_of_instance and adjoint_of_instance share.  VEC: the vector recursion of hmpc_adjoint.h
+// rides in the passes' spare lanes (Work then has v[U], y[U] too): v beside PA / PB, y = Z'v beside W / X, its triangular solves on
+// lane 13 in the loop of the columns of X (a branch of its own would run behind them), k_i beside S, p_i beside P_i.  Without VEC none
+// of that is compiled.
+template <int NC, int HMAX, int NT, bool VEC, class Work>
+__device__ __forceinline__ void riccati_gain_step(FeedbackKeep<NC, HMAX> &Kp, Work &Wk, const int i, double *K, double &pivmin,
+                                                  const RiccatiVec vec) {
+  constexpr int U = 6 * NC;
+  const int tid = threadIdx.x;
+  const double *A = Kp.A, *B = Kp.B;
+  // normals held by each contact's leg-step, the first column of each contact in Z_i (the first contact's is 0), and r_i
+  const int hl0 = (int)Kp.held[NC * i], hl1 = (int)Kp.held[NC * i + 1], hl2 = (NC == 3) ? (int)Kp.held[NC * i + NC - 1] : 6;
+  const int o1 = 6 - hl0, o2 = o1 + 6 - hl1, r = o2 + 6 - hl2;
+  const double *Zi = Kp.Z + 36 * NC * i;
+  for (int t = tid; t < 169 + 13 * U + (VEC ? U : 0); t += NT) {  // PA = P A, PB = P B;  (VEC) v = l_i + B' p
+    double acc = 0.0;
+    if (t < 169) {
+      const int k = t / 13, s = t % 13;
+#pragma unroll
+      for (int l = 0; l < 13; ++l) acc = __builtin_fma(Wk.P[k * 13 + l], A[l * 13 + s], acc);
+      Wk.PA[t] = acc;
+    } else if (!VEC || t < 169 + 13 * U) {
+      const int k = (t - 169) / U, c = (t - 169) % U;
+#pragma unroll
+      for (int l = 0; l < 13; ++l) acc = __builtin_fma(Wk.P[k * 13 + l], B[l * U + c], acc);
+      Wk.PB[t - 169] = acc;
+    } else if constexpr (VEC) {
+      const int c = t - 169 - 13 * U;
+#pragma unroll
+      for (int k = 0; k < 13; ++k) acc = __builtin_fma(B[k * U + c], vec.p[k], acc);
+      Wk.v[c] = vec.ell[c] + acc;
+    }
+  }
+  __syncthreads();
+  if (r > 0) {  // (uniform)
+    for (int t = tid; t < U * U + 13 * r + (VEC ? r : 0); t += NT) {  // W = R + B' PB;  X = Z' B';  (VEC) y = Z' v
+      double acc = 0.0;
+      if (t < U * U) {
+        const int c = t / U, d = t % U;
+#pragma unroll
+        for (int k = 0; k < 13; ++k) acc = __builtin_fma(B[k * U + c], Wk.PB[k * U + d], acc);
+        Wk.W[t] = (c == d) ? Kp.r2[c] + acc : acc;
+      } else if (!VEC || t < U * U + 13 * r) {
+        const int a = (t - U * U) / 13, s = (t - U * U) % 13;
+        int ca;
+        const double *za = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, a, ca);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc = __builtin_fma(za[k], B[s * U + fb_col<NC>(ca, k)], acc);
+        Wk.X[a * 13 + s] = acc;
+      } else if constexpr (VEC) {
+        const int a = t - U * U - 13 * r;
+        int ca;
+        const double *za = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, a, ca);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc = __builtin_fma(za[k], Wk.v[fb_col<NC>(ca, k)], acc);
+        Wk.y[a] = acc;
+      }
+    }
+    __syncthreads();
+    for (int t = tid; t < U * r; t += NT) {  // WZ = W Z
+      const int c = t / r, b = t % r;
+      int cb;
+      const double *zb = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, b, cb);
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = __builtin_fma(Wk.W[c * U + fb_col<NC>(cb, k)], zb[k], acc);
+      Wk.WZ[c * U + b] = acc;
+    }
+    __syncthreads();
+    for (int t = tid; t < r * r; t += NT) {  // G = Z' WZ
+      const int a = t / r, b = t % r;
+      int ca;
+      const double *za = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, a, ca);
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc = __builtin_fma(za[k], Wk.WZ[fb_col<NC>(ca, k) * U + b], acc);
+      Wk.G[a * U + b] = acc;
+    }
+    __syncthreads();
+    // (the chains below run over all U slots with the terms outside their range switched off: the loads do not wait for each other)
+    for (int j = 0; j < r; ++j) {  // Cholesky, column j: lane a >= j owns row a; L below the diagonal in G, its diagonal in Ld
+      if (tid >= j && tid < r) {
+        const double gjj = Wk.G[j * U + j];
+        double ss = 0.0, acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < U; ++b) {
+          const double ljb = Wk.G[j * U + b], lab = Wk.G[tid * U + b];
+          ss = (b < j) ? __builtin_fma(ljb, ljb, ss) : ss;
+          acc = (b < j) ? __builtin_fma(lab, ljb, acc) : acc;
+        }
+        const double d = gjj - ss, ljj = __builtin_sqrt(d);
+        if (tid == j) Wk.Ld[j] = ljj, Wk.piv[j] = d / gjj;
+        else Wk.G[tid * U + j] = (Wk.G[tid * U + j] - acc) / ljj;
+      }
+      __syncthreads();
+    }
+    // Two copies of the two triangular solves, on purpose.  The second is the gains' own, kept verbatim: written over (col, ld) like the
+    // first it compiles to other machine code for the kernels of hmpc_feedback.hip, whose hashes must stay (scripts/isa_hash.py --diff).
+    // The first adds the vector y as a fourteenth lane of the same loop; as a branch of its own it would run behind the columns of X
+    // (same wave), 25 % slower over the launch (profiles/r20/README.md).  Change both or neither, and check the hashes.
+    if constexpr (VEC) {
+      if (tid < 14) {  // the same two solves, with the same chains: lanes 0 .. 12 a column of X each, lane 13 the vector y beside them
+        double *col = (tid < 13) ? Wk.X + tid : Wk.y;
+        const int ld = (tid < 13) ? 13 : 1;
+        for (int a = 0; a < r; ++a) {
+          double acc = 0.0;
+#pragma unroll
+          for (int b = 0; b < U; ++b) {
+            const double l = Wk.G[a * U + b], x = col[b * ld];
+            acc = (b < a) ? __builtin_fma(l, x, acc) : acc;
+          }
+          col[a * ld] = (col[a * ld] - acc) / Wk.Ld[a];
+        }
+        for (int a = r - 1; a >= 0; --a) {
+          double acc = 0.0;
+#pragma unroll
+          for (int b = 0; b < U; ++b) {
+            const double l = Wk.G[b * U + a], x = col[b * ld];
+            acc = (b > a && b < r) ? __builtin_fma(l, x, acc) : acc;
+          }
+          col[a * ld] = (col[a * ld] - acc) / Wk.Ld[a];
+        }
+      }
+    } else {
+      if (tid < 13) {  // L y = X[:, tid], L' x = y, in place
+        for (int a = 0; a < r; ++a) {
+          double acc = 0.0;
+#pragma unroll
+          for (int b = 0; b < U; ++b) {
+            const double l = Wk.G[a * U + b], x = Wk.X[b * 13 + tid];
+            acc = (b < a) ? __builtin_fma(l, x, acc) : acc;
+          }
+          Wk.X[a * 13 + tid] = (Wk.X[a * 13 + tid] - acc) / Wk.Ld[a];
+        }
+        for (int a = r - 1; a >= 0; --a) {
+          double acc = 0.0;
+#pragma unroll
+          for (int b = 0; b < U; ++b) {
+            const double l = Wk.G[b * U + a], x = Wk.X[b * 13 + tid];
+            acc = (b > a && b < r) ? __builtin_fma(l, x, acc) : acc;
+          }
+          Wk.X[a * 13 + tid] = (Wk.X[a * 13 + tid] - acc) / Wk.Ld[a];
+        }
+      }
+    }
+    if (tid == 64)  // (a lane of the other wave: off the solves' path)
+      for (int j = 0; j < r; ++j) {
+        const double p = Wk.piv[j], v = (p == p) ? p : 0.0;
+        pivmin = (v < pivmin) ? v : pivmin;
+      }
+    __syncthreads();
+    for (int t = tid; t < 13 * U + (VEC ? U : 0); t += NT) {  // S = Z X;  (VEC) k_i = 0 - Z y
+      const bool kvec = VEC && t >= 13 * U;
+      const int c = kvec ? t - 13 * U : t / 13, s = t % 13;
+      const int cc = (c < 3 * NC) ? c / 3 : (c - 3 * NC) / 3, k = (c < 3 * NC) ? c % 3 : 3 + (c - 3 * NC) % 3;
+      const int hc = (cc == 2) ? hl2 : ((cc == 1) ? hl1 : hl0), oc = (cc == 2) ? o2 : ((cc == 1) ? o1 : 0);
+      const double *zrow = Kp.Z + 36 * (NC * i + cc) + 6 * hc + k;
+      double acc = 0.0;
+      if (kvec) {
+        if constexpr (VEC) {
+          for (int b = 0; b < 6 - hc; ++b) acc = __builtin_fma(zrow[6 * b], Wk.y[oc + b], acc);
+          vec.k[c] = 0.0 - acc;
+        }
+        continue;
+      }
+      for (int b = 0; b < 6 - hc; ++b) acc = __builtin_fma(zrow[6 * b], Wk.X[(oc + b) * 13 + s], acc);
+      Wk.S[t] = acc;
+    }
+    __syncthreads();
+    for (int t = tid; t < 13 * U; t += NT) {  // K = 0 - S PA
+      const int c = t / 13, s = t % 13;
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < 13; ++k) acc = __builtin_fma(Wk.S[c * 13 + k], Wk.PA[k * 13 + s], acc);
+      K[t] = 0.0 - acc;
+    }
+  } else {
+    for (int t = tid; t < 13 * U; t += NT) Wk.S[t] = 0.0, K[t] = 0.0;
+    if constexpr (VEC)
+      if (tid < U) vec.k[tid] = 0.0;
+  }
+}
+
+// The rest of step i behind riccati_gain_step and a barrier: M_i = A + B K_i into M[13][13], then (with_P) P_i = Q + PA' M_i into Wk.P,
+// evaluated on the upper triangle and copied to the lower; (VEC) p_i beside it.  Ends with a barrier.
+template <int NC, int HMAX, int NT, bool VEC, class Work>
+__device__ __forceinline__ void riccati_cost_step(FeedbackKeep<NC, HMAX> &Kp, Work &Wk, const double *K, double *M, const bool with_P,
+                                                  const RiccatiVec vec) {
+  constexpr int U = 6 * NC;
+  const int tid = threadIdx.x;
+  const double *A = Kp.A, *B = Kp.B;
+  for (int t = tid; t < 169; t += NT) {  // M_i = A + B K_i
+    const int k = t / 13, s = t % 13;
+    double acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < U; ++c) acc = __builtin_fma(B[k * U + c], K[c * 13 + s], acc);
+    M[t] = A[t] + acc;
+  }
+  __syncthreads();
+  for (int t = tid; t < 169 + (VEC ? 13 : 0); t += NT) {  // P_i = Q + PA' M_i, upper triangle, copied;  (VEC) p_i = M_i' p + K_i' l_i
+    if constexpr (VEC) {
+      if (t >= 169) {
+        const int s = t - 169;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 13; ++k) acc = __builtin_fma(M[k * 13 + s], vec.p[k], acc);
+#pragma unroll
+        for (int c = 0; c < U; ++c) acc = __builtin_fma(K[c * 13 + s], vec.ell[c], acc);
+        vec.p_next[s] = acc;
+        continue;
+      }
+      if (!with_P) continue;  // (P_0 is not needed)
+    }
+    const int s = t / 13, tt = t % 13;
+    if (s > tt) continue;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 13; ++k) acc = __builtin_fma(Wk.PA[k * 13 + s], M[k * 13 + tt], acc);
+    const double v = (s == tt) ? Kp.q2[s] + acc : acc;
+    Wk.P[s * 13 + tt] = v, Wk.P[tt * 13 + s] = v;
+  }
+  __syncthreads();
+}
+
 // The gains of one instance, by the NT lanes of its workgroup.  In (LDS or any memory all lanes see): Acd[13][13], Bcd[13][6 NC], W[12],
 // alpha[6 NC], Fc[8 NC][6 NC], u[h][6 NC], gait[NC h] bytes, cap[NC].  Out: gain_out[6 NC][13], ref_out[h][6 NC][12], free_out[h],
 // summary_out[2].  Every lane of the workgroup calls it.  Wk may overlay the binary32 inputs (see FeedbackWork).
@@ -176,147 +411,11 @@ __device__ __forceinline__ void feedback_of_instance(const float *Acd, const flo
   for (int t = tid; t < 169; t += NT) Wk.P[t] = (t % 14 == 0) ? Kp.q2[t / 13] : 0.0;
   __syncthreads();
   for (int i = h - 1; i >= 0; --i) {
-    // normals held by each contact's leg-step, the first column of each contact in Z_i (the first contact's is 0), and r_i
-    const int hl0 = (int)Kp.held[NC * i], hl1 = (int)Kp.held[NC * i + 1], hl2 = (NC == 3) ? (int)Kp.held[NC * i + NC - 1] : 6;
-    const int o1 = 6 - hl0, o2 = o1 + 6 - hl1, r = o2 + 6 - hl2;
-    const double *Zi = Kp.Z + 36 * NC * i;
-    for (int t = tid; t < 169 + 13 * U; t += NT) {  // PA = P A, PB = P B
-      double acc = 0.0;
-      if (t < 169) {
-        const int k = t / 13, s = t % 13;
-#pragma unroll
-        for (int l = 0; l < 13; ++l) acc = __builtin_fma(Wk.P[k * 13 + l], A[l * 13 + s], acc);
-        Wk.PA[t] = acc;
-      } else {
-        const int k = (t - 169) / U, c = (t - 169) % U;
-#pragma unroll
-        for (int l = 0; l < 13; ++l) acc = __builtin_fma(Wk.P[k * 13 + l], B[l * U + c], acc);
-        Wk.PB[t - 169] = acc;
-      }
-    }
-    __syncthreads();
-    if (r > 0) {  // (uniform)
-      for (int t = tid; t < U * U + 13 * r; t += NT) {  // W = R + B' PB;  X = Z' B'
-        double acc = 0.0;
-        if (t < U * U) {
-          const int c = t / U, d = t % U;
-#pragma unroll
-          for (int k = 0; k < 13; ++k) acc = __builtin_fma(B[k * U + c], Wk.PB[k * U + d], acc);
-          Wk.W[t] = (c == d) ? Kp.r2[c] + acc : acc;
-        } else {
-          const int a = (t - U * U) / 13, s = (t - U * U) % 13;
-          int ca;
-          const double *za = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, a, ca);
-#pragma unroll
-          for (int k = 0; k < 6; ++k) acc = __builtin_fma(za[k], B[s * U + fb_col<NC>(ca, k)], acc);
-          Wk.X[a * 13 + s] = acc;
-        }
-      }
-      __syncthreads();
-      for (int t = tid; t < U * r; t += NT) {  // WZ = W Z
-        const int c = t / r, b = t % r;
-        int cb;
-        const double *zb = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, b, cb);
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc = __builtin_fma(Wk.W[c * U + fb_col<NC>(cb, k)], zb[k], acc);
-        Wk.WZ[c * U + b] = acc;
-      }
-      __syncthreads();
-      for (int t = tid; t < r * r; t += NT) {  // G = Z' WZ
-        const int a = t / r, b = t % r;
-        int ca;
-        const double *za = fb_zcol(Zi, hl0, hl1, hl2, o1, o2, a, ca);
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc = __builtin_fma(za[k], Wk.WZ[fb_col<NC>(ca, k) * U + b], acc);
-        Wk.G[a * U + b] = acc;
-      }
-      __syncthreads();
-      // (the chains below run over all U slots with the terms outside their range switched off: the loads do not wait for each other)
-      for (int j = 0; j < r; ++j) {  // Cholesky, column j: lane a >= j owns row a; L below the diagonal in G, its diagonal in Ld
-        if (tid >= j && tid < r) {
-          const double gjj = Wk.G[j * U + j];
-          double ss = 0.0, acc = 0.0;
-#pragma unroll
-          for (int b = 0; b < U; ++b) {
-            const double ljb = Wk.G[j * U + b], lab = Wk.G[tid * U + b];
-            ss = (b < j) ? __builtin_fma(ljb, ljb, ss) : ss;
-            acc = (b < j) ? __builtin_fma(lab, ljb, acc) : acc;
-          }
-          const double d = gjj - ss, ljj = __builtin_sqrt(d);
-          if (tid == j) Wk.Ld[j] = ljj, Wk.piv[j] = d / gjj;
-          else Wk.G[tid * U + j] = (Wk.G[tid * U + j] - acc) / ljj;
-        }
-        __syncthreads();
-      }
-      if (tid < 13) {  // L y = X[:, tid], L' x = y, in place
-        for (int a = 0; a < r; ++a) {
-          double acc = 0.0;
-#pragma unroll
-          for (int b = 0; b < U; ++b) {
-            const double l = Wk.G[a * U + b], x = Wk.X[b * 13 + tid];
-            acc = (b < a) ? __builtin_fma(l, x, acc) : acc;
-          }
-          Wk.X[a * 13 + tid] = (Wk.X[a * 13 + tid] - acc) / Wk.Ld[a];
-        }
-        for (int a = r - 1; a >= 0; --a) {
-          double acc = 0.0;
-#pragma unroll
-          for (int b = 0; b < U; ++b) {
-            const double l = Wk.G[b * U + a], x = Wk.X[b * 13 + tid];
-            acc = (b > a && b < r) ? __builtin_fma(l, x, acc) : acc;
-          }
-          Wk.X[a * 13 + tid] = (Wk.X[a * 13 + tid] - acc) / Wk.Ld[a];
-        }
-      }
-      if (tid == 64)  // (a lane of the other wave: off the solves' path)
-        for (int j = 0; j < r; ++j) {
-          const double p = Wk.piv[j], v = (p == p) ? p : 0.0;
-          pivmin = (v < pivmin) ? v : pivmin;
-        }
-      __syncthreads();
-      for (int t = tid; t < 13 * U; t += NT) {  // S = Z X
-        const int c = t / 13, s = t % 13;
-        const int cc = (c < 3 * NC) ? c / 3 : (c - 3 * NC) / 3, k = (c < 3 * NC) ? c % 3 : 3 + (c - 3 * NC) % 3;
-        const int hc = (cc == 2) ? hl2 : ((cc == 1) ? hl1 : hl0), oc = (cc == 2) ? o2 : ((cc == 1) ? o1 : 0);
-        const double *zrow = Kp.Z + 36 * (NC * i + cc) + 6 * hc + k;
-        double acc = 0.0;
-        for (int b = 0; b < 6 - hc; ++b) acc = __builtin_fma(zrow[6 * b], Wk.X[(oc + b) * 13 + s], acc);
-        Wk.S[t] = acc;
-      }
-      __syncthreads();
-      for (int t = tid; t < 13 * U; t += NT) {  // K = 0 - S PA
-        const int c = t / 13, s = t % 13;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 13; ++k) acc = __builtin_fma(Wk.S[c * 13 + k], Wk.PA[k * 13 + s], acc);
-        Wk.K[t] = 0.0 - acc;
-      }
-    } else {
-      for (int t = tid; t < 13 * U; t += NT) Wk.S[t] = 0.0, Wk.K[t] = 0.0;
-    }
+    riccati_gain_step<NC, HMAX, NT, false>(Kp, Wk, i, Wk.K, pivmin, RiccatiVec{});
     __syncthreads();
     if (i > 0) {
       double *M = Wk.M + 169 * (i - 1);
-      for (int t = tid; t < 169; t += NT) {  // M_i = A + B K_i
-        const int k = t / 13, s = t % 13;
-        double acc = 0.0;
-#pragma unroll
-        for (int c = 0; c < U; ++c) acc = __builtin_fma(B[k * U + c], Wk.K[c * 13 + s], acc);
-        M[t] = A[t] + acc;
-      }
-      __syncthreads();
-      for (int t = tid; t < 169; t += NT) {  // P_i = Q + PA' M_i, upper triangle, copied
-        const int s = t / 13, tt = t % 13;
-        if (s > tt) continue;
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 13; ++k) acc = __builtin_fma(Wk.PA[k * 13 + s], M[k * 13 + tt], acc);
-        const double v = (s == tt) ? Kp.q2[s] + acc : acc;
-        Wk.P[s * 13 + tt] = v, Wk.P[tt * 13 + s] = v;
-      }
-      __syncthreads();
+      riccati_cost_step<NC, HMAX, NT, false>(Kp, Wk, Wk.K, M, true, RiccatiVec{});
     }
   }
   // ---- K_0, S_0: the gain, its maximum, and the forward chain of Psi

@@ -10,6 +10,7 @@
 #include "hmpc_kernel_args.h"
 #include "hmpc_certificate.h"
 #include "hmpc_feedback.h"
+#include "hmpc_adjoint.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -122,6 +123,10 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   OutputBuffer<int32_t> d_fb_free;
   OutputBuffer<float> d_fo_wrench;
   OutputBuffer<double> d_fo_worst;
+  // adjoint (hmpc_solve_adjoint): grad_x0 [max_batch][13], grad_traj [max_batch][horizon][12], grad_weights [max_batch][12], grad_alpha
+  // [max_batch][6 nc], dir [max_batch][horizon][6 nc] and summary [max_batch][2] binary64; to the caller's buffers
+  // (hmpc_set_device_adjoint) or the handle's own, allocated by the first call that needs them
+  OutputBuffer<double> d_adj_x0, d_adj_traj, d_adj_weights, d_adj_alpha, d_adj_dir, d_adj_summary;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

@@ -114,6 +114,7 @@ class BatchedMPC:
         self.stride = int(self.L.hmpc_record_stride_ex(self.horizon, self.contacts))
         self._keep = None
         self._keep_out = None
+        self.generation = 0  # counts the calls of this object that replace the batch or its forces (autograd.py compares it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -131,12 +132,14 @@ class BatchedMPC:
         return int(self.L.hmpc_batch(self.h))
 
     def upload(self, recs: np.ndarray) -> None:
+        self.generation += 1
         recs = np.ascontiguousarray(recs, dtype=np.uint8)
         assert recs.ndim == 2 and recs.shape[1] == self.stride, (recs.shape, self.stride)
         _check(self.L.hmpc_upload_records(self.h, recs.ctypes.data, recs.shape[0]), "hmpc_upload_records")
 
     def upload_async(self, host_ptr: int, batch: int, stream: int = 0) -> None:
         """Stream-ordered upload from a (pinned) host buffer of ``batch`` packed records."""
+        self.generation += 1
         _check(self.L.hmpc_upload_records_async(self.h, C.c_void_p(host_ptr), int(batch), C.c_void_p(stream)),
                "hmpc_upload_records_async")
 
@@ -149,11 +152,13 @@ class BatchedMPC:
         self.upload(records.pack_records(fields, self.horizon, self.contacts))
 
     def set_device_records(self, device_ptr: int, batch: int, max_reduced_vars: int = -1, keepalive=None) -> None:
+        self.generation += 1
         self._keep = keepalive
         _check(self.L.hmpc_set_device_records(self.h, C.c_void_p(device_ptr), int(batch)), "hmpc_set_device_records")
         _check(self.L.hmpc_set_max_reduced_vars(self.h, int(max_reduced_vars)), "hmpc_set_max_reduced_vars")
 
     def set_device_outputs(self, forces_ptr: int, status_ptr: int, keepalive=None) -> None:
+        self.generation += 1
         self._keep_out = keepalive
         _check(self.L.hmpc_set_device_outputs(self.h, C.c_void_p(forces_ptr), C.c_void_p(status_ptr)),
                "hmpc_set_device_outputs")
@@ -224,6 +229,7 @@ class BatchedMPC:
     def tick_solve_device(self, ticks_ptr: int, batch: int, dt_mpc: float, tau_ptr: int, f_ff_ptr: int = 0, wpd_ptr: int = 0,
                           stream: int = 0) -> None:
         """f1+f2 -> solve -> f3 on one stream, everything device-resident (include/hector_mpc.h hmpc_tick_solve_device)."""
+        self.generation += 1
         _check(self.L.hmpc_tick_solve_device(self.h, C.c_void_p(ticks_ptr), int(batch), float(dt_mpc), C.c_void_p(wpd_ptr),
                                              C.c_void_p(f_ff_ptr), C.c_void_p(tau_ptr), C.c_void_p(stream)),
                "hmpc_tick_solve_device")
@@ -234,12 +240,14 @@ class BatchedMPC:
         return int(n.value)
 
     def solve(self, stream: int = 0) -> None:
+        self.generation += 1
         _check(self.L.hmpc_solve(self.h, C.c_void_p(stream)), "hmpc_solve")
 
     def solve_command_sweep(self, group_size: int, stream: int = 0) -> None:
         """The current batch as groups of ``group_size`` consecutive records that differ in the reference trajectory only: H is
         assembled and inverted once per group, every instance solves with its group's inverse -- bit-identical results
         (include/hector_mpc.h hmpc_solve_command_sweep)."""
+        self.generation += 1
         _check(self.L.hmpc_solve_command_sweep(self.h, int(group_size), C.c_void_p(stream)), "hmpc_solve_command_sweep")
 
     def download(self):
@@ -309,6 +317,7 @@ class BatchedMPC:
         """Ticks (``TICK_DTYPE[n_ticks]``) and candidate commands (``COMMAND_DTYPE[n_ticks, group_size]``) in HBM in, the best command's
         torques in HBM out: records, sweep solve, prediction, selection and torques on one stream (include/hector_mpc.h
         hmpc_tick_sweep_device).  Which command won: ``download_selection()``."""
+        self.generation += 1
         _check(self.L.hmpc_tick_sweep_device(self.h, C.c_void_p(ticks_ptr), int(n_ticks), C.c_void_p(commands_ptr), int(group_size),
                                              float(dt_mpc), C.c_void_p(int(penalty_ptr or 0)), C.c_void_p(int(wpd_ptr or 0)),
                                              C.c_void_p(int(f_ff_ptr or 0)), C.c_void_p(tau_ptr), C.c_void_p(stream)),
@@ -433,6 +442,39 @@ class BatchedMPC:
         self._keep_fo = keepalive
         _check(self.L.hmpc_set_device_first_order(self.h, C.c_void_p(int(wrench_ptr or 0)), C.c_void_p(int(worst_slack_ptr or 0))),
                "hmpc_set_device_first_order")
+
+    ADJOINT_KEYS = ("grad_x0", "grad_traj", "grad_weights", "grad_alpha", "dir", "summary")
+
+    def solve_adjoint(self, seed_ptr: int, stream: int = 0) -> None:
+        """One launch behind the solve on ``stream``: from the seed dL/du (float64[batch, horizon, 6 contacts] in HBM) the gradients of L
+        in the state, the reference trajectory, the weights and Alpha_K, the active set at the forces in the force buffer frozen
+        (include/hector_mpc.h hmpc_solve_adjoint).  Raises for a null seed and when no solve of the current batch has been enqueued."""
+        _check(self.L.hmpc_solve_adjoint(self.h, C.c_void_p(int(seed_ptr or 0)), C.c_void_p(stream)), "hmpc_solve_adjoint")
+
+    def download_adjoint(self) -> dict:
+        """grad_x0 float64[batch, 13], grad_traj float64[batch, horizon, 12], grad_weights float64[batch, 12], grad_alpha
+        float64[batch, 6 contacts], dir float64[batch, horizon, 6 contacts] and summary float64[batch, 2] (smallest Cholesky pivot ratio,
+        max |dir|).  Waits; runs no safe pass."""
+        b, hz, u = self.batch, self.horizon, 6 * self.contacts
+        out = dict(grad_x0=np.zeros((b, 13)), grad_traj=np.zeros((b, hz, 12)), grad_weights=np.zeros((b, 12)), grad_alpha=np.zeros((b, u)),
+                   dir=np.zeros((b, hz, u)), summary=np.zeros((b, 2)))
+        _check(self.L.hmpc_download_adjoint(self.h, *[out[k].ctypes.data for k in self.ADJOINT_KEYS]), "hmpc_download_adjoint")
+        return out
+
+    def get_device_adjoint(self) -> dict:
+        """Device pointers of where the next adjoint goes, by the names of ``download_adjoint`` (the handle's own buffers are allocated
+        here if they were not yet)."""
+        ptrs = [C.c_void_p() for _ in self.ADJOINT_KEYS]
+        _check(self.L.hmpc_get_device_adjoint(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint")
+        return {k: int(p.value or 0) for k, p in zip(self.ADJOINT_KEYS, ptrs)}
+
+    def set_device_adjoint(self, grad_x0_ptr: int = 0, grad_traj_ptr: int = 0, grad_weights_ptr: int = 0, grad_alpha_ptr: int = 0,
+                           dir_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later adjoints (shapes of ``download_adjoint`` with max_batch rows; 0 / None = the handle's own)."""
+        self._keep_adj = keepalive
+        _check(self.L.hmpc_set_device_adjoint(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_x0_ptr, grad_traj_ptr, grad_weights_ptr,
+                                                                                           grad_alpha_ptr, dir_ptr, summary_ptr)]),
+               "hmpc_set_device_adjoint")
 
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where

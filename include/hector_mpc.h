@@ -595,6 +595,62 @@ int hmpc_download_first_order(hmpc_handle *h, float *wrench, double *worst_slack
  * last solution.  Computed lazily, once per solve, on first use (one launch, one copy).  0 before the first solve and for
  * out-of-range arguments, as get_solution. */
 double hmpc_legacy_feedback_gain(int component, int state);
+/* ---- the adjoint of the solve: loss gradients in the state, the reference, the weights and Alpha_K ----
+ * A sweep or a learning loop has a scalar loss L(u) over the whole force trajectory and wants its gradient in what it tunes.  With the
+ * active limits frozen the solution map is that of an equality-constrained LQ problem, and ONE backward / forward sweep turns the seed
+ * dL/du into all of those gradients.  Per instance, let NC be the number of contacts and U = 6 NC.  The assembly (x0, Acd, Bcd, Fc, w[12],
+ * traj, Alpha_K[U], gait, caps; hmpc_params and hmpc_set_instance_mu included) enters exactly as for hmpc_feedback_gains, and u_i[U] is step
+ * i of the force buffer as it stands.  The seed l[batch][h][U], binary64, is a caller-owned device pointer and stands for dL/du.
+ * Everything below is binary64.  Every sum is one ascending chain of explicit fused multiply-adds started at +0; "a ; b" continues
+ * chain a with the terms of b.  A = Acd, B = Bcd, q2 = (w + w, 0), l_i = l[i][.].
+ *   1. Slacks, stance rule, active set and free directions Z_i: exactly hmpc_feedback_gains' (items 1, 2), with the same act_tol.
+ *   2. Matrix backward pass: exactly hmpc_feedback_gains' (item 3), chain for chain: P_h = Q, then PA, PB, W, G_i, the Cholesky factor,
+ *      S_i, K_i, M_i, P_i; M_0 = A + B K_0 is formed as well (P_0 is not).
+ *   3. Vector backward pass, p_h = 0.  For i = h-1 .. 0, with p = p_{i+1}:
+ *        v[c]   = l_i[c] + sum_{k<13} B[k][c] p[k]
+ *        y[a]   = sum_k Z_i[k][a] v[k] over the six rows of column a's contact; y <- G_i^-1 y through the Cholesky factor: the two
+ *                 triangular solves of the gains' X, with their chains (forward: b < a ascending; backward: a < b < r_i ascending)
+ *        k_i[c] = 0 - sum_b Z_i[c][b] y[b] over the columns of c's contact (exactly 0 when r_i = 0)
+ *        p_i[s] = sum_{k<13} M_i[k][s] p[k] ; sum_{c<U} K_i[c][s] l_i[c]
+ *   4. Forward pass, dx_0 = 0.  For i = 0 .. h-1:
+ *        du_i[c]     = (sum_{s<13} K_i[c][s] dx_i[s]) + k_i[c]
+ *        dx_{i+1}[s] = sum_{k<13} A[s][k] dx_i[k] ; sum_{c<U} B[s][c] du_i[c]
+ *      x_1 .. x_h exactly as hmpc_predict_states defines them, un-rounded.
+ *   5. Outputs.
+ *        grad_x0[batch][13]      = p_0
+ *        grad_traj[batch][h][12]   row j-1: 0 - q2[s] dx_j[s]                                   (d/d traj[12 (j-1) + s])
+ *        grad_weights[batch][12] = sum_{j=1..h} (e + e) dx_j[s],  e = x_j[s] - traj[12 (j-1) + s]
+ *        grad_alpha[batch][U]    = sum_{i<h} (u_i[c] + u_i[c]) du_i[c]
+ *        dir[batch][h][U]        = du_i.  It is -Z (Z'HZ)^-1 Z' l of the condensed QP; the gradient in any other parameter theta is
+ *                                  sum dir . d(Hu + g)/d theta, left to the caller (r, the orientation, hmpc_params, mu, the caps).
+ *        summary[batch][2]       [0] the smallest pivot ratio: hmpc_feedback_gains' summary[0], bit for bit; [1] max |dir| (a NaN
+ *                                  entry counts as +inf).
+ *   6. Meaning.  The outputs are the derivatives of L(u*(x0, X_d, w, Alpha_K)) with the linearisation (Acd, Bcd, Fc) and the active
+ *      set frozen: exact wherever the active set is locally constant; at a weakly active limit there are one-sided derivatives only and
+ *      the frozen set's is reported, as for the gains.  The seed e_c at step 0 returns row c of the gains (grad_x0 = gain[c][.],
+ *      grad_traj[j] = ref_gain[j][c][.]).  Rows of dir on swing contacts are exactly 0, finite seed entries on swing contacts change no
+ *      output bit, and a zero seed gives zeros.  No loop iterates on data, so NaN input ends like any other.  The result is a pure
+ *      function of (record, hmpc_params, per-instance mu, force buffer, act_tol, seed).
+ *
+ * hmpc_solve_adjoint enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It
+ * reads the forces where the solve wrote them and needs no gains.  HMPC_E_ARG, nothing enqueued: a NULL seed, or no solve of the
+ * current batch has been enqueued.  One seed per call.
+ * hmpc_set_device_adjoint: caller-owned device buffers for later adjoints (any may be NULL = the handle's own, allocated for max_batch
+ * by the first call that needs them; never inside hmpc_solve); moving the buffers makes an adjoint already computed stale, as do every
+ * solve and every new batch.  The gains and the first-order wrench are not touched by any of these calls, nor they by theirs.
+ * hmpc_get_device_adjoint: where the next adjoint goes; any pointer may be NULL.  hmpc_download_adjoint waits for the stream of the last
+ * call, then copies (any pointer may be NULL); HMPC_E_ARG when nothing has been computed since the last solve of the current batch.  It
+ * does NOT run the safe pass.  With no batch set (batch = 0) it copies nothing and returns HMPC_OK, as hmpc_download_gains does; the
+ * launch itself is refused there, there being no solve.
+ * Device groups: per member, through hmpc_group_member.  There is no accessor on the process-global solver behind setup_problem /
+ * update_problem_data: a seed has no place in that interface. */
+int hmpc_solve_adjoint(hmpc_handle *h, const double *device_seed, void *stream);
+int hmpc_set_device_adjoint(hmpc_handle *h, double *device_grad_x0, double *device_grad_traj, double *device_grad_weights,
+                            double *device_grad_alpha, double *device_dir, double *device_summary);
+int hmpc_get_device_adjoint(hmpc_handle *h, double **device_grad_x0, double **device_grad_traj, double **device_grad_weights,
+                            double **device_grad_alpha, double **device_dir, double **device_summary);
+int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
+                          double *summary);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size

@@ -1,0 +1,245 @@
+"""numpy restatement (float64) of the adjoint's definition (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h), fed with the
+oracle's binary32 assembly of a record, a force vector and a seed; the dense frozen-set QP it is checked against; and what the adjoint
+tests share: the seeds, the perturbed weights / Alpha_K records of the finite-difference tests and their measured bounds.
+numpy has no fma, so the GPU's chains differ from these by binary64 round-off only.  Z, the slacks and the stance rule are
+feedback_mirror's."""
+import numpy as np
+
+import certificate_mirror as cm
+import feedback_mirror as fm
+from hector_simulation_amd import records
+
+ACT_TOL = fm.ACT_TOL
+MIRROR_TOL = fm.MIRROR_TOL
+# Central differences of l.u* in the dense frozen-set QP (float64, built from powers of Acd and Bcd) at a relative step of FD_DENSE_STEP
+# against grad_x0, grad_traj, grad_weights and grad_alpha, each relative to max(1, max|value|) of its output: the largest error measured
+# over CASES is DENSE_E_MEASURED (tests/test_adjoint_mirror.py prints it per shape); the bound is twice that.
+FD_DENSE_STEP = 1e-6
+DENSE_E_MEASURED = 5.77e-8  # (single_h20, grad_alpha; x0 and the trajectory: 2.4e-9, the weights 5.5e-9)
+DENSE_FD = 2 * DENSE_E_MEASURED
+# Finite differences of the reference's qpOASES on the records of test_feedback_mirror.fd_case against grad_x0.dx + sum grad_traj.dt,
+# relative to max(1, max|u0|), over the kept instances: E measured per shape (tests/test_adjoint_mirror.py prints them); ADJ_FD = 2 x the
+# largest, the factor covering the seed-to-seed spread of the binary32 assembly noise of two independently assembled records (FD_FORCE).
+ADJ_FD_E_MEASURED = 1.10e-5  # (per shape 1.2e-6, 8.2e-8, 1.0e-6, 7.0e-7, 2.8e-8, 3.6e-6, 4.3e-6, 1.1e-5)
+ADJ_FD = 2 * ADJ_FD_E_MEASURED
+# The same for weights and Alpha_K, every entry multiplied by 1 + uniform(-s, s), s = FD_W_STEP halved until at most FD_LEFT_OUT_CAP of
+# the shape is left out: ADJ_FD_W = 2 x the largest E measured; pooled over all kept instances sum|pred - act| / sum|act| < FD_W_POOLED.
+FD_W_STEP = 1e-2
+ADJ_FD_W_E_MEASURED = 7.75e-5  # (per shape 7.0e-6, 4.9e-7, 4.3e-6, 2.4e-6, 1.5e-6, 1.3e-5, 2.7e-5, 7.7e-5; pooled ratio 0.055)
+ADJ_FD_W = 2 * ADJ_FD_W_E_MEASURED
+FD_W_POOLED = 0.5
+KEYS = ("grad_x0", "grad_traj", "grad_weights", "grad_alpha", "dir", "summary")
+
+
+def seeds(nb, h, U, rng_seed=5):
+    """The seeds of the finite-difference tests: per shape one default_rng(5), per instance uniform(-1, 1, (h, U)) over its 1-norm."""
+    rng = np.random.default_rng(rng_seed)
+    out = np.zeros((nb, h, U))
+    for k in range(nb):
+        s = rng.uniform(-1.0, 1.0, (h, U))
+        out[k] = s / np.abs(s).sum()
+    return out
+
+
+def unit_seeds(nb, h, U):
+    """Instance k: e_c at step 0, c = k mod U."""
+    out = np.zeros((nb, h, U))
+    for k in range(nb):
+        out[k, 0, k % U] = 1.0
+    return out
+
+
+def adjoint(Acd, Bcd, x0, weights, traj, alpha, u, Z, seed):
+    """The definition behind the free directions: Z = [Z_0 .. Z_{h-1}] (each U x r_i), u[h, U] the forces, seed[h, U]."""
+    A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+    w, al = np.asarray(weights, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+    u, ell = np.asarray(u, dtype=np.float64), np.asarray(seed, dtype=np.float64)
+    tr = np.asarray(traj, dtype=np.float64).reshape(-1, 12)
+    h, U = len(Z), B.shape[1]
+    q2 = np.concatenate([w + w, [0.0]])
+    Q, R = np.diag(q2), np.diag(al + al)
+    P, p = Q.copy(), np.zeros(13)
+    K, kk = np.zeros((h, U, 13)), np.zeros((h, U))
+    pivmin = 1.0
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for i in range(h - 1, -1, -1):
+            PA, PB = P @ A, P @ B
+            v = ell[i] + B.T @ p
+            Zi = Z[i]
+            if Zi.shape[1] > 0:
+                W = R + B.T @ PB
+                G = Zi.T @ (W @ Zi)
+                L, ratio = fm.cholesky_lower(np.tril(G) + np.tril(G, -1).T)
+                for pr in ratio:
+                    val = 0.0 if np.isnan(pr) else pr
+                    pivmin = val if val < pivmin else pivmin
+                rhs = np.concatenate([Zi.T @ B.T, (Zi.T @ v)[:, None]], axis=1)
+                sol = np.linalg.solve(L.T, np.linalg.solve(L, rhs)) if np.isfinite(L).all() else np.full_like(rhs, np.nan)
+                K[i] = 0.0 - (Zi @ sol[:, :13]) @ PA
+                kk[i] = 0.0 - Zi @ sol[:, 13]
+            M = A + B @ K[i]
+            p = M.T @ p + K[i].T @ ell[i]
+            if i > 0:
+                Pn = Q + PA.T @ M
+                P = np.triu(Pn) + np.triu(Pn, 1).T
+        dx, x = np.zeros(13), np.asarray(x0, dtype=np.float64).copy()
+        du = np.zeros((h, U))
+        gt, gw = np.zeros((h, 12)), np.zeros(12)
+        for i in range(h):
+            du[i] = K[i] @ dx + kk[i]
+            dx = A @ dx + B @ du[i]
+            x = A @ x + B @ u[i]
+            gt[i] = 0.0 - q2[:12] * dx[:12]
+            e = x[:12] - tr[i]
+            gw = gw + (e + e) * dx[:12]
+        ga = ((u + u) * du).sum(axis=0)
+        a = np.abs(du)
+        dmax = float(np.where(np.isnan(a), np.inf, a).max())
+    return dict(grad_x0=p, grad_traj=gt, grad_weights=gw, grad_alpha=ga, dir=du, summary=np.array([pivmin, dmax]))
+
+
+def adjoint_records(oracle, rec, h, nc, forces, seed, mu=None, act_tol=ACT_TOL, gains=None):
+    """The definition over a batch of packed records: dict of grad_x0[b, 13], grad_traj[b, h, 12], grad_weights[b, 12], grad_alpha[b, U],
+    dir[b, h, U], summary[b, 2], and `gains`: feedback_mirror.gains_records on the same forces (Z, stance, active, Acd ...; computed here
+    unless handed in)."""
+    nb, U = rec.shape[0], 6 * nc
+    g = gains if gains is not None else fm.gains_records(oracle, rec, h, nc, forces, mu=mu, act_tol=act_tol)
+    un = records.unpack_records(rec, h, nc)
+    rows = []
+    for k in range(nb):
+        unk = cm.unpacked_row(un, k)
+        rows.append(adjoint(g["Acd"][k], g["Bcd"][k], g["x0"][k], unk["weights"], unk["traj"], unk["Alpha_K"],
+                            np.asarray(forces[k]).reshape(h, U), g["Z"][k], np.asarray(seed[k]).reshape(h, U)))
+    out = {key: np.stack([r[key] for r in rows]) for key in KEYS}
+    out["gains"] = g
+    return out
+
+
+class DenseModel:
+    """The frozen-set QP of one instance in float64: u*(theta) = u0 - Zf (Zf' H Zf)^-1 (Zf' (H u0 + g) - c), H = 2 (Bq' S Bq + diag alpha),
+    g = 2 Bq' S (Aq x0 - traj), built from powers of Acd and Bcd as feedback_mirror.dense_gains does.  c = Zf' (H u0 + g) at the base point
+    (anchor): u0 -- qpOASES' optimum of the binary32 H and g, rounded -- is then this model's optimum at the base point too, as the
+    definition assumes of the forces it is given.  (Without c the float64 model's own optimum lies up to 0.6 N from u0 along the
+    directions Alpha_K alone holds, and d/d weights, d/d Alpha_K of the inverse times that offset enter at 1e-4 .. 6e-3 of the gradient.)"""
+
+    def __init__(self, Acd, Bcd, Z, u0):
+        A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+        h, U = len(Z), B.shape[1]
+        Ap = [np.eye(13)]
+        for _ in range(h):
+            Ap.append(A @ Ap[-1])
+        self.Aq = np.concatenate(Ap[1:], axis=0)
+        self.Bq = np.zeros((13 * h, U * h))
+        for i in range(1, h + 1):
+            for k in range(i):
+                self.Bq[13 * (i - 1):13 * i, U * k:U * (k + 1)] = Ap[i - 1 - k] @ B
+        r = [z.shape[1] for z in Z]
+        self.Zf = np.zeros((U * h, sum(r)))
+        o = 0
+        for i in range(h):
+            self.Zf[U * i:U * (i + 1), o:o + r[i]] = Z[i]
+            o += r[i]
+        self.BZ = self.Bq @ self.Zf
+        self.h, self.U, self.u0 = h, U, np.asarray(u0, dtype=np.float64).reshape(-1)
+        self.Bu0 = self.Bq @ self.u0
+        self.c = np.zeros(self.Zf.shape[1])
+
+    def reduced(self, x0, traj, w, al):
+        """(Zf' H Zf, Zf' (H u0 + g))"""
+        h = self.h
+        s = np.tile(np.concatenate([w, [0.0]]), h)
+        alt = np.tile(al, h)
+        t13 = np.concatenate([np.asarray(traj, dtype=np.float64).reshape(h, 12), np.zeros((h, 1))], axis=1).reshape(-1)
+        G = 2.0 * (self.BZ.T @ (s[:, None] * self.BZ) + self.Zf.T @ (alt[:, None] * self.Zf))
+        resid = 2.0 * (self.BZ.T @ (s * (self.Bu0 + self.Aq @ x0 - t13)) + self.Zf.T @ (alt * self.u0))
+        return G, resid
+
+    def anchor(self, x0, traj, w, al):
+        self.c = self.reduced(np.asarray(x0, dtype=np.float64), traj, w, al)[1]
+        return self
+
+    def solution(self, x0, traj, w, al):
+        if self.Zf.shape[1] == 0:
+            return self.u0.copy()
+        G, resid = self.reduced(x0, traj, w, al)
+        return self.u0 - self.Zf @ np.linalg.solve(G, resid - self.c)
+
+    def direction(self, w, al, ell):
+        """-Zf (Zf' H Zf)^-1 Zf' l, [h, U]"""
+        if self.Zf.shape[1] == 0:
+            return np.zeros((self.h, self.U))
+        s, alt = np.tile(np.concatenate([w, [0.0]]), self.h), np.tile(al, self.h)
+        G = 2.0 * (self.BZ.T @ (s[:, None] * self.BZ) + self.Zf.T @ (alt[:, None] * self.Zf))
+        return (0.0 - self.Zf @ np.linalg.solve(G, self.Zf.T @ np.asarray(ell).reshape(-1))).reshape(self.h, self.U)
+
+    def central_differences(self, x0, traj, w, al, ell, step=FD_DENSE_STEP):
+        """d(l.u*)/d(x0, traj, weights, alpha) by central differences: x0 and the trajectory (l.u* is linear in them) at a step of
+        `step` max(1, |entry|), the weights and Alpha_K (1e-6 .. 1e2 in size) at `step` |entry| (`step` for a zero entry)."""
+        ell = np.asarray(ell, dtype=np.float64).reshape(-1)
+        theta = [np.asarray(v, dtype=np.float64).reshape(-1).copy() for v in (x0, traj, w, al)]
+        out = []
+        for which in range(4):
+            g = np.zeros(theta[which].size)
+            for j in range(g.size):
+                a = abs(theta[which][j])
+                d = step * (max(1.0, a) if which < 2 else (a if a > 0.0 else 1.0))
+                vals = []
+                for sgn in (1.0, -1.0):
+                    th = [t.copy() for t in theta]
+                    th[which][j] += sgn * d
+                    vals.append(float(ell @ self.solution(*th)))
+                g[j] = (vals[0] - vals[1]) / (2.0 * d)
+            out.append(g)
+        return out[0], out[1].reshape(self.h, 12), out[2], out[3]
+
+
+def scaled_records(rec, h, nc, seed, s):
+    """The records with every weight and every Alpha_K multiplied by 1 + uniform(-s, s): (records, dw[b, 12], dalpha[b, U]) with the
+    deltas taken between the binary32 values of both."""
+    rng = np.random.default_rng(seed)
+    un = records.unpack_records(rec, h, nc)
+    f = {k: np.array(v, copy=True) for k, v in un.items()}
+    for key in ("weights", "Alpha_K"):
+        f[key] = (f[key].astype(np.float64) * (1.0 + rng.uniform(-s, s, f[key].shape))).astype(np.float32)
+    dw = f["weights"].astype(np.float64) - np.asarray(un["weights"], dtype=np.float64)
+    da = f["Alpha_K"].astype(np.float64) - np.asarray(un["Alpha_K"], dtype=np.float64)
+    return records.pack_records(f, h, nc), dw.reshape(rec.shape[0], 12), da.reshape(rec.shape[0], 6 * nc)
+
+
+def predicted_change(adj, dx=None, dt=None, dw=None, da=None):
+    """Per instance grad_x0.dx + sum grad_traj.dt + grad_weights.dw + grad_alpha.da over the deltas given."""
+    nb = adj["grad_x0"].shape[0]
+    out = np.zeros(nb)
+    if dx is not None:
+        out += (adj["grad_x0"] * dx).sum(axis=1)
+    if dt is not None:
+        out += (adj["grad_traj"] * dt).reshape(nb, -1).sum(axis=1)
+    if dw is not None:
+        out += (adj["grad_weights"] * dw).sum(axis=1)
+    if da is not None:
+        out += (adj["grad_alpha"] * da).sum(axis=1)
+    return out
+
+
+_fdw = {}
+
+
+def fd_weights_case(oracle, case, base_mirror):
+    """The scaled records of a case, qpOASES on both, the kept instances (equal active sets); shared by tests/test_adjoint_mirror.py and
+    tests/test_gpu_adjoint.py, left unchanged.  base_mirror: feedback_mirror.gains_records of the case at qpOASES' forces."""
+    name, h, nb, nc = case[0], case[2], case[3], case[4]
+    if name in _fdw:
+        return _fdw[name]
+    rec = base_mirror["rec"]
+    u0 = fm.qpoases_forces(oracle, rec, h, nc)
+    s = FD_W_STEP
+    for _ in range(8):
+        rec2, dw, da = scaled_records(rec, h, nc, 2000 + case[5], s)
+        u1 = fm.qpoases_forces(oracle, rec2, h, nc)
+        m2 = fm.gains_records(oracle, rec2, h, nc, u1.astype(np.float32))
+        keep = fm.same_active_sets(base_mirror["m"]["active"], m2["active"])
+        if (~keep).mean() <= fm.FD_LEFT_OUT_CAP:
+            break
+        s *= 0.5
+    _fdw[name] = dict(rec=rec, rec2=rec2, dw=dw, da=da, keep=keep, s=s, u0=u0, u1=u1)
+    return _fdw[name]

@@ -1,0 +1,28 @@
+"""examples/loss_gradient.c (a standing batch solved, the loss "step-0 vertical force of the left foot" seeded, its gradient in the
+reference trajectory printed, one reference entry moved and the predicted change beside a re-solve) compiled against include/hector_mpc.h
+and linked to the in-tree library, on the pattern of tests/test_feedback_example.py: without a GPU it must fail loudly, with one it must
+run."""
+import subprocess
+
+import pytest
+
+from test_examples import _compile, _has_gpu
+
+SRC = ("loss_gradient.c", "gcc", "-std=c11")
+
+
+def test_loss_gradient_example_compiles_and_fails_loudly_without_gpu(tmp_path):
+    exe = _compile(tmp_path, *SRC)
+    if _has_gpu():
+        pytest.skip("GPU present: covered by the gpu-marked test")
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode != 0
+    assert "no HIP device" in (r.stderr + r.stdout)
+
+
+@pytest.mark.gpu
+def test_loss_gradient_example_runs_on_gpu(tmp_path):
+    exe = _compile(tmp_path, *SRC)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "loss gradients of 4 standing robots, reference height moved by 5 mm: 0 problems" in r.stdout
