@@ -3,6 +3,8 @@ the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h
 
     forces = differentiable_solve(mpc, fields, traj, weights, alpha_k)     # CUDA float32 [b, h * 6 contacts]
     loss(forces).backward()                                                # traj.grad, weights.grad, alpha_k.grad
+    forces = differentiable_solve(mpc, fields, traj, weights, alpha_k, r)  # r [b, 3 contacts], the record's order: r.grad as well, by one
+                                                                           # more launch (hmpc_adjoint_model; csrc/hmpc_model_adjoint.hip)
 
 The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
 constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
@@ -31,10 +33,25 @@ def _buffers(mpc, device):
     return buf
 
 
+def _model_buffers(mpc, device):
+    """The same for the model gradients (``set_device_adjoint_model``)."""
+    buf = getattr(mpc, "_autograd_model_buffers", None)
+    if buf is None:
+        b, nc = mpc.max_batch, mpc.contacts
+        shapes = dict(grad_A=(b, 13, 13), grad_B=(b, 13, 6 * nc), grad_r=(b, 3, nc), grad_params=(b, 4), costate=(b, 2, 13))
+        buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_model_buffers = buf
+    if mpc.get_device_adjoint_model() != {k: buf[k].data_ptr() for k in mpc.MODEL_ADJOINT_KEYS}:
+        mpc.set_device_adjoint_model(*[buf[k].data_ptr() for k in mpc.MODEL_ADJOINT_KEYS], keepalive=buf)
+    return buf
+
+
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mpc, fields, traj, weights, alpha_k):
+    def forward(ctx, mpc, fields, traj, weights, alpha_k, r=None):
         f = dict(fields)
+        if r is not None:
+            f["r"] = r.detach().cpu().numpy()
         f["traj"] = traj.detach().cpu().numpy()
         f["weights"] = weights.detach().cpu().numpy()
         f["Alpha_K"] = alpha_k.detach().cpu().numpy()
@@ -45,6 +62,7 @@ class _Solve(torch.autograd.Function):
         forces, _ = mpc.download()  # (the safe pass: repaired forces, in the handle's force buffer as well)
         ctx.mpc, ctx.generation, ctx.device = mpc, mpc.generation, device  # (after the download: the safe pass replaces no batch)
         ctx.meta = [(t.shape, t.dtype, t.device) for t in (traj, weights, alpha_k)]
+        ctx.r_meta = None if r is None else (r.shape, r.dtype, r.device)
         return torch.from_numpy(np.ascontiguousarray(forces)).to(device)
 
     @staticmethod
@@ -54,6 +72,8 @@ class _Solve(torch.autograd.Function):
             raise RuntimeError("differentiable_solve: the handle has solved another batch since this forward; its forces are gone")
         b = mpc.batch
         buf = _buffers(mpc, ctx.device)
+        want_r = ctx.r_meta is not None and ctx.needs_input_grad[5]
+        mbuf = _model_buffers(mpc, ctx.device) if want_r else None  # (before the adjoint: moving buffers makes nothing of it stale)
         seed = grad_output.detach().to(device=ctx.device, dtype=torch.float64).contiguous()
         mpc.solve_adjoint(seed.data_ptr(), torch.cuda.current_stream(ctx.device).cuda_stream)
         grads = []
@@ -61,11 +81,20 @@ class _Solve(torch.autograd.Function):
             # (a copy in every case: a float64 leaf on the handle's device would otherwise get a view of the handle's own buffer as
             #  its .grad, which the next launch overwrites)
             grads.append(buf[key][:b].to(device=dev, dtype=dtype, copy=True).reshape(shape) if need else None)
-        return (None, None) + tuple(grads)
+        grad_r = None
+        if want_r:
+            mpc.adjoint_model(torch.cuda.current_stream(ctx.device).cuda_stream)
+            shape, dtype, dev = ctx.r_meta
+            grad_r = mbuf["grad_r"][:b].to(device=dev, dtype=dtype, copy=True).reshape(shape)
+        return (None, None) + tuple(grads) + ((grad_r,) if ctx.r_meta is not None else ())
 
 
-def differentiable_solve(mpc, fields, traj, weights, alpha_k):
+def differentiable_solve(mpc, fields, traj, weights, alpha_k, r=None):
     """Solves the batch ``fields`` (the dict ``records.pack_records`` takes) with its reference trajectory, tracking weights and Alpha_K
     replaced by the tensors ``traj`` [b, 12 h], ``weights`` [b, 12] and ``alpha_k`` [b, 6 contacts] (any device, any float dtype), and returns
-    the forces as a CUDA float32 tensor [b, h * 6 contacts] that autograd differentiates in those three."""
-    return _Solve.apply(mpc, fields, traj, weights, alpha_k)
+    the forces as a CUDA float32 tensor [b, h * 6 contacts] that autograd differentiates in those three.  With a tensor ``r`` [b, 3 contacts]
+    (the record's order: axis, then contact) the foot positions are replaced as well and the backward returns their gradient too, by one
+    more launch behind the adjoint (hmpc_adjoint_model); with ``r=None`` nothing is launched beyond the adjoint."""
+    if r is None:
+        return _Solve.apply(mpc, fields, traj, weights, alpha_k)
+    return _Solve.apply(mpc, fields, traj, weights, alpha_k, r)

@@ -1088,6 +1088,83 @@ int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, do
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Model gradients: the gradients of the adjoint's loss in Acd, Bcd, the foot positions, the mass and the body inertia
+// (hmpc_model_adjoint.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next model gradients go: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int model_adjoint_buffers(hmpc_handle *h, hmpc::ModelAdjointOut *b) {
+  const size_t mb = (size_t)h->max_batch, u = 6 * (size_t)h->nc;
+  HIP_TRY(h->d_madj_A.ensure(mb * 169));
+  HIP_TRY(h->d_madj_B.ensure(mb * 13 * u));
+  HIP_TRY(h->d_madj_r.ensure(mb * 3 * (size_t)h->nc));
+  HIP_TRY(h->d_madj_params.ensure(mb * hmpc::MADJ_PARAMS));
+  HIP_TRY(h->d_madj_costate.ensure(mb * hmpc::MADJ_COSTATE));
+  *b = {h->d_madj_A.get(), h->d_madj_B.get(), h->d_madj_r.get(), h->d_madj_params.get(), h->d_madj_costate.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_adjoint_model(hmpc_handle *h, double *device_grad_A, double *device_grad_B, double *device_grad_r,
+                                  double *device_grad_params, double *device_costate) {
+  if (!h) return HMPC_E_ARG;
+  h->d_madj_A.set_caller(device_grad_A), h->d_madj_B.set_caller(device_grad_B), h->d_madj_r.set_caller(device_grad_r);
+  h->d_madj_params.set_caller(device_grad_params), h->d_madj_costate.set_caller(device_costate);
+  h->results.retarget_model_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint_model(hmpc_handle *h, double **device_grad_A, double **device_grad_B, double **device_grad_r,
+                                  double **device_grad_params, double **device_costate) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::ModelAdjointOut b;
+  const int rc = model_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_grad_A) *device_grad_A = b.grad_A;
+  if (device_grad_B) *device_grad_B = b.grad_B;
+  if (device_grad_r) *device_grad_r = b.grad_r;
+  if (device_grad_params) *device_grad_params = b.grad_params;
+  if (device_costate) *device_costate = b.costate;
+  return HMPC_OK;
+}
+
+int hmpc_adjoint_model(hmpc_handle *h, void *stream) {
+  if (!h || !h->results.has_adjoint()) return HMPC_E_ARG;  // no adjoint of the last solve of the current batch: dir is another seed's, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::AdjointOut adj;
+  int rc = adjoint_buffers(h, &adj);  // (where that adjoint went: moving them would have made it stale)
+  if (rc != HMPC_OK) return rc;
+  hmpc::ModelAdjointOut b;
+  rc = model_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_model_adjoint(h->nc, a, (double)h->params.mass, adj.dir, b, (hipStream_t)stream));
+  h->results.on_model_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint_model(hmpc_handle *h, double *grad_A, double *grad_B, double *grad_r, double *grad_params, double *costate) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_model_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint of the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::ModelAdjointOut b;
+  const int rc = model_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, u = 6 * (size_t)h->nc, d = sizeof(double);
+  if (grad_A) HIP_TRY(hipMemcpy(grad_A, b.grad_A, n * 169 * d, hipMemcpyDeviceToHost));
+  if (grad_B) HIP_TRY(hipMemcpy(grad_B, b.grad_B, n * 13 * u * d, hipMemcpyDeviceToHost));
+  if (grad_r) HIP_TRY(hipMemcpy(grad_r, b.grad_r, n * 3 * (size_t)h->nc * d, hipMemcpyDeviceToHost));
+  if (grad_params) HIP_TRY(hipMemcpy(grad_params, b.grad_params, n * hmpc::MADJ_PARAMS * d, hipMemcpyDeviceToHost));
+  if (costate) HIP_TRY(hipMemcpy(costate, b.costate, n * hmpc::MADJ_COSTATE * d, hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

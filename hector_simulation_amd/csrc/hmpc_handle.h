@@ -11,6 +11,7 @@
 #include "hmpc_certificate.h"
 #include "hmpc_feedback.h"
 #include "hmpc_adjoint.h"
+#include "hmpc_model_adjoint.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -127,6 +128,10 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // [max_batch][6 nc], dir [max_batch][horizon][6 nc] and summary [max_batch][2] binary64; to the caller's buffers
   // (hmpc_set_device_adjoint) or the handle's own, allocated by the first call that needs them
   OutputBuffer<double> d_adj_x0, d_adj_traj, d_adj_weights, d_adj_alpha, d_adj_dir, d_adj_summary;
+  // model gradients (hmpc_adjoint_model): grad_A [max_batch][13][13], grad_B [max_batch][13][6 nc], grad_r [max_batch][3][nc], grad_params
+  // [max_batch][4] and costate [max_batch][2][13] binary64; to the caller's buffers (hmpc_set_device_adjoint_model) or the handle's own,
+  // allocated by the first call that needs them
+  OutputBuffer<double> d_madj_A, d_madj_B, d_madj_r, d_madj_params, d_madj_costate;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

@@ -476,6 +476,41 @@ class BatchedMPC:
                                                                                            grad_alpha_ptr, dir_ptr, summary_ptr)]),
                "hmpc_set_device_adjoint")
 
+    MODEL_ADJOINT_KEYS = ("grad_A", "grad_B", "grad_r", "grad_params", "costate")
+
+    def adjoint_model(self, stream: int = 0) -> None:
+        """One launch behind ``solve_adjoint`` on ``stream``: from the ``dir`` that adjoint left, the gradients of the same loss in Acd,
+        Bcd, the foot positions, the mass and the body inertia (include/hector_mpc.h hmpc_adjoint_model).  Raises when no adjoint of
+        the last solve of the current batch has been enqueued."""
+        _check(self.L.hmpc_adjoint_model(self.h, C.c_void_p(stream)), "hmpc_adjoint_model")
+
+    def download_adjoint_model(self) -> dict:
+        """grad_A float64[batch, 13, 13], grad_B float64[batch, 13, 6 contacts], grad_r float64[batch, 3, contacts] (the record's order:
+        axis, then contact), grad_params float64[batch, 4] (mass, inertia 0 .. 2) and costate float64[batch, 2, 13].  Waits; runs no safe
+        pass."""
+        b, nc = self.batch, self.contacts
+        out = dict(grad_A=np.zeros((b, 13, 13)), grad_B=np.zeros((b, 13, 6 * nc)), grad_r=np.zeros((b, 3, nc)), grad_params=np.zeros((b, 4)),
+                   costate=np.zeros((b, 2, 13)))
+        _check(self.L.hmpc_download_adjoint_model(self.h, *[out[k].ctypes.data for k in self.MODEL_ADJOINT_KEYS]),
+               "hmpc_download_adjoint_model")
+        return out
+
+    def get_device_adjoint_model(self) -> dict:
+        """Device pointers of where the next model gradients go, by the names of ``download_adjoint_model`` (the handle's own buffers are
+        allocated here if they were not yet)."""
+        ptrs = [C.c_void_p() for _ in self.MODEL_ADJOINT_KEYS]
+        _check(self.L.hmpc_get_device_adjoint_model(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_model")
+        return {k: int(p.value or 0) for k, p in zip(self.MODEL_ADJOINT_KEYS, ptrs)}
+
+    def set_device_adjoint_model(self, grad_A_ptr: int = 0, grad_B_ptr: int = 0, grad_r_ptr: int = 0, grad_params_ptr: int = 0,
+                                 costate_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later model gradients (shapes of ``download_adjoint_model`` with max_batch rows; 0 / None = the
+        handle's own)."""
+        self._keep_madj = keepalive
+        _check(self.L.hmpc_set_device_adjoint_model(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_A_ptr, grad_B_ptr, grad_r_ptr,
+                                                                                                 grad_params_ptr, costate_ptr)]),
+               "hmpc_set_device_adjoint_model")
+
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where
         the last solve handed instance i's working set over and nothing has consumed it yet, else -1."""

@@ -622,7 +622,9 @@ double hmpc_legacy_feedback_gain(int component, int state);
  *        grad_weights[batch][12] = sum_{j=1..h} (e + e) dx_j[s],  e = x_j[s] - traj[12 (j-1) + s]
  *        grad_alpha[batch][U]    = sum_{i<h} (u_i[c] + u_i[c]) du_i[c]
  *        dir[batch][h][U]        = du_i.  It is -Z (Z'HZ)^-1 Z' l of the condensed QP; the gradient in any other parameter theta is
- *                                  sum dir . d(Hu + g)/d theta, left to the caller (r, the orientation, hmpc_params, mu, the caps).
+ *                                  sum dir . d(Hu + g)/d theta: hmpc_adjoint_model below returns it for r, the mass and the body inertia
+ *                                  (gravity is grad_x0[12]); left to the caller are the orientation (through grad_A, grad_B and grad_x0
+ *                                  of these calls), and mu, lt, lh, the caps and the joint angles.
  *        summary[batch][2]       [0] the smallest pivot ratio: hmpc_feedback_gains' summary[0], bit for bit; [1] max |dir| (a NaN
  *                                  entry counts as +inf).
  *   6. Meaning.  The outputs are the derivatives of L(u*(x0, X_d, w, Alpha_K)) with the linearisation (Acd, Bcd, Fc) and the active
@@ -651,6 +653,57 @@ int hmpc_get_device_adjoint(hmpc_handle *h, double **device_grad_x0, double **de
                             double **device_grad_alpha, double **device_dir, double **device_summary);
 int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
                           double *summary);
+/* ---- model gradients of the solve: foot positions, mass, body inertia, Acd and Bcd themselves ----
+ * Behind hmpc_solve_adjoint: the gradient of the same loss in what enters the QP through the prediction model.  With the active set
+ * frozen and du = dir of the last adjoint, dL/dtheta = <G_A, dA/dtheta> + <G_B, dB/dtheta> for every theta that enters through A = Acd
+ * and B = Bcd only; the constraint block does not depend on r, the mass or the inertia, so no multipliers are needed.  Per instance, NC
+ * contacts, U = 6 NC; the assembly enters exactly as for hmpc_solve_adjoint (hmpc_params and hmpc_set_instance_mu included), u_i[U] is step
+ * i of the force buffer as it stands, du_i[U] step i of the adjoint's dir buffer as it stands.  Everything below is binary64.  Every sum
+ * is one ascending chain of explicit fused multiply-adds started at +0; "a ; b" continues chain a with the terms of b; q2 = (w + w, 0).
+ *   1. Forward pass, x_0 = x0, dx_0 = 0.  For i = 0 .. h-1:
+ *        x_{i+1}[s]  = sum_{k<13} A[s][k] x_i[k] ; sum_{c<U} B[s][c] u_i[c]          (exactly hmpc_predict_states', un-rounded)
+ *        dx_{i+1}[s] = sum_{k<13} A[s][k] dx_i[k] ; sum_{c<U} B[s][c] du_i[c]        (item 4 of the adjoint, over the stored dir)
+ *   2. Backward pass, c_{h+1} = d_{h+1} = 0.  For j = h .. 1, with t_c[s] = sum_{k<13} A[k][s] c_{j+1}[k], t_d likewise over d_{j+1}:
+ *        c_j[s] = fma(q2[s], x_j[s] - traj[12 (j-1) + s], t_c[s])   for s < 12;   c_j[12] = t_c[12]
+ *        d_j[s] = fma(q2[s], dx_j[s], t_d[s])                       for s < 12;   d_j[12] = t_d[12]
+ *   3. Accumulation: per entry one chain over i = 0 .. h-1, per step the c term, then the d term:
+ *        G_A[a][b] = sum_i ( c_{i+1}[a] dx_i[b] ; d_{i+1}[a] x_i[b] )                 (13 x 13)
+ *        G_B[a][c] = sum_i ( c_{i+1}[a] du_i[c] ; d_{i+1}[a] u_i[c] )                 (13 x U)
+ *   4. Chain rules.  Mb[a][m] = B[6+a][3 NC + m] is the assembled dt Iinv.  r_c[k] is the record's r[k NC + c] and cm_c = {0, -r_c[2],
+ *      r_c[1]; r_c[2], 0, -r_c[0]; -r_c[1], r_c[0], 0} the cross matrix as the assembly writes it, binary32, widened.  R is the binary32
+ *      rotation the assembly forms from the record's quaternion, widened.
+ *        T_c[m][b]       = sum_{a<3} Mb[a][m] G_B[6+a][3c+b]
+ *        grad_r[.][c]    = (T_c[2][1] - T_c[1][2], T_c[0][2] - T_c[2][0], T_c[1][0] - T_c[0][1])
+ *        grad_mass       = 0 - (s B[9][0]) / mass,  s = +0 + G_B[9][0] + G_B[10][1] + G_B[11][2] + G_B[9][3] + ... (c ascending, then a),
+ *                          mass the handle's hmpc_params value widened
+ *        Gam[a][m]       = per c ascending: + G_B[6+a][3 NC + 3c + m], then ; sum_{b<3} G_B[6+a][3c+b] cm_c[m][b]   (zero entries included)
+ *        w_k[a]          = sum_{m<3} Mb[a][m] R[m][k];   t_k[a] = sum_{m<3} Gam[a][m] w_k[m]
+ *        grad_inertia[k] = 0 - (sum_{a<3} w_k[a] t_k[a]) / dt,  dt widened: exact for an un-normalised quaternion too
+ *   5. Outputs: grad_A[batch][13][13] = G_A;  grad_B[batch][13][U] = G_B;  grad_r[batch][3][NC] in the record's order [axis][contact];
+ *      grad_params[batch][4] = (grad_mass, grad_inertia[0..2]);  costate[batch][2][13] = (c_1, d_1).
+ *   6. Meaning.  d L / d theta of L(u*(theta)) with the active set frozen, theta entering through Acd and Bcd: the foot positions, the
+ *      mass and the inertia as the assembly uses them (first-order; the assembly's binary32 rounding is not differentiated), and through
+ *      grad_A / grad_B the orientation or any parameterisation of the caller's.  A' d_1 is the adjoint's grad_x0 up to rounding.  The
+ *      gradient in the gravity state is grad_x0[12] of the adjoint: nothing new is needed.  A zero seed gives zeros; columns of G_B on a
+ *      contact that is swing at every step are exactly 0 (u and dir are 0 there).  No loop iterates on data, so NaN input ends like any
+ *      other.  The result is a pure function of (record, hmpc_params, per-instance mu, force buffer, dir buffer).
+ *
+ * hmpc_adjoint_model enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It reads
+ * dir where the last adjoint wrote it.  HMPC_E_ARG, nothing enqueued: no adjoint of the last solve of the current batch has been enqueued
+ * (every solve, every new batch and hmpc_set_device_adjoint make an adjoint stale).
+ * hmpc_set_device_adjoint_model: caller-owned device buffers for later calls (any may be NULL = the handle's own, allocated for max_batch
+ * by the first call that needs them; never inside hmpc_solve); moving the buffers makes model gradients already computed stale, as do
+ * every solve, every new batch, every hmpc_solve_adjoint (a new seed) and hmpc_set_device_adjoint.
+ * hmpc_get_device_adjoint_model: where the next model gradients go; any pointer may be NULL.  hmpc_download_adjoint_model waits for the
+ * stream of the last call, then copies (any pointer may be NULL); HMPC_E_ARG when nothing has been computed since the last adjoint.  It
+ * does NOT run the safe pass.  With no batch set (batch = 0) it copies nothing and returns HMPC_OK.
+ * Device groups: per member, through hmpc_group_member.  There is no accessor on the process-global solver. */
+int hmpc_adjoint_model(hmpc_handle *h, void *stream);
+int hmpc_set_device_adjoint_model(hmpc_handle *h, double *device_grad_A, double *device_grad_B, double *device_grad_r,
+                                  double *device_grad_params, double *device_costate);
+int hmpc_get_device_adjoint_model(hmpc_handle *h, double **device_grad_A, double **device_grad_B, double **device_grad_r,
+                                  double **device_grad_params, double **device_costate);
+int hmpc_download_adjoint_model(hmpc_handle *h, double *grad_A, double *grad_B, double *grad_r, double *grad_params, double *costate);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size

@@ -1,0 +1,20 @@
+"""The model-gradient kernel's own source behind the assembly (csrc/hmpc_model_adjoint.h: the two forward chains, the two costate chains,
+the accumulation of G_A and G_B and the chain rules to r, mass and inertia) run on the CPU, no GPU needed: compiled with g++ against a
+stand-in hip_runtime.h that gives every lane a thread (tests/src/hip_lane_shim), checked bit for bit against a plain sequential loop
+(tests/src/model_adjoint_on_host.cpp); a zero dir, a swing contact, a NaN force, a NaN dir and the rotation of an un-normalised quaternion
+included: the run has to end.  The GPU tests (tests/test_gpu_model_adjoint.py) check the machine code; this one keeps the source's logic
+checked where there is no GPU."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_model_adjoint_kernel_source_on_the_host(tmp_path):
+    exe = str(tmp_path / "model_adjoint_on_host")
+    cmd = ["g++", "-std=c++20", "-O1", "-ffp-contract=off", "-pthread", "-I" + os.path.join(ROOT, "tests", "src", "hip_lane_shim"),
+           "-I" + os.path.join(ROOT, "hector_simulation_amd", "csrc"), os.path.join(ROOT, "tests", "src", "model_adjoint_on_host.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "0 problems" in r.stdout, r.stdout + r.stderr
