@@ -38,6 +38,7 @@ EXPORTS = [
     "hmpc_set_device_first_order", "hmpc_download_first_order", "hmpc_legacy_feedback_gain",
     "hmpc_solve_adjoint", "hmpc_set_device_adjoint", "hmpc_get_device_adjoint", "hmpc_download_adjoint",
     "hmpc_adjoint_model", "hmpc_set_device_adjoint_model", "hmpc_get_device_adjoint_model", "hmpc_download_adjoint_model",
+    "hmpc_adjoint_limits", "hmpc_set_device_adjoint_limits", "hmpc_get_device_adjoint_limits", "hmpc_download_adjoint_limits",
 ]
 
 
@@ -237,6 +238,10 @@ def load():
     L.hmpc_set_device_adjoint_model.argtypes = [vp] + [vp] * 5
     L.hmpc_get_device_adjoint_model.argtypes = [vp] + [C.POINTER(vp)] * 5
     L.hmpc_download_adjoint_model.argtypes = [vp] + [vp] * 5
+    L.hmpc_adjoint_limits.argtypes = [vp, vp, vp]
+    L.hmpc_set_device_adjoint_limits.argtypes = [vp] + [vp] * 6
+    L.hmpc_get_device_adjoint_limits.argtypes = [vp] + [C.POINTER(vp)] * 6
+    L.hmpc_download_adjoint_limits.argtypes = [vp] + [vp] * 6
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

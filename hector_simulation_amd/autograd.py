@@ -5,6 +5,8 @@ the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h
     loss(forces).backward()                                                # traj.grad, weights.grad, alpha_k.grad
     forces = differentiable_solve(mpc, fields, traj, weights, alpha_k, r)  # r [b, 3 contacts], the record's order: r.grad as well, by one
                                                                            # more launch (hmpc_adjoint_model; csrc/hmpc_model_adjoint.hip)
+    forces = differentiable_solve_limits(mpc, fields, traj, weights, alpha_k, mu=mu)  # mu [b], the instances' friction parameter: mu.grad
+                                                                                      # as well (hmpc_adjoint_limits; csrc/hmpc_limit_adjoint.hip)
 
 The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
 constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
@@ -46,9 +48,23 @@ def _model_buffers(mpc, device):
     return buf
 
 
+def _limit_buffers(mpc, device):
+    """The same for the limit gradients (``set_device_adjoint_limits``)."""
+    buf = getattr(mpc, "_autograd_limit_buffers", None)
+    if buf is None:
+        b, nc, hz = mpc.max_batch, mpc.contacts, mpc.horizon
+        shapes = dict(grad_limits=(b, 3 + nc), grad_Fc=(b, 8 * nc, 6 * nc), grad_bound=(b, hz, nc, 10), nu=(b, hz, nc, 10), summary=(b, 3))
+        shapes["lambda"] = (b, hz, nc, 10)
+        buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_limit_buffers = buf
+    if mpc.get_device_adjoint_limits() != {k: buf[k].data_ptr() for k in mpc.LIMIT_ADJOINT_KEYS}:
+        mpc.set_device_adjoint_limits(*[buf[k].data_ptr() for k in mpc.LIMIT_ADJOINT_KEYS], keepalive=buf)
+    return buf
+
+
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mpc, fields, traj, weights, alpha_k, r=None):
+    def forward(ctx, mpc, fields, traj, weights, alpha_k, r=None, mu=None):
         f = dict(fields)
         if r is not None:
             f["r"] = r.detach().cpu().numpy()
@@ -57,12 +73,16 @@ class _Solve(torch.autograd.Function):
         f["Alpha_K"] = alpha_k.detach().cpu().numpy()
         device = torch.device("cuda", mpc.device)
         stream = torch.cuda.current_stream(device).cuda_stream
+        if mu is not None:  # (a float32 CUDA tensor of the handle's own; it stays set on the handle)
+            mu32 = mu.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous().clone()
+            mpc.set_instance_mu(mu32.data_ptr(), keepalive=mu32)
         mpc.upload(records.pack_records(f, mpc.horizon, mpc.contacts))
         mpc.solve(stream)
         forces, _ = mpc.download()  # (the safe pass: repaired forces, in the handle's force buffer as well)
         ctx.mpc, ctx.generation, ctx.device = mpc, mpc.generation, device  # (after the download: the safe pass replaces no batch)
         ctx.meta = [(t.shape, t.dtype, t.device) for t in (traj, weights, alpha_k)]
         ctx.r_meta = None if r is None else (r.shape, r.dtype, r.device)
+        ctx.mu_meta = None if mu is None else (mu.shape, mu.dtype, mu.device)
         return torch.from_numpy(np.ascontiguousarray(forces)).to(device)
 
     @staticmethod
@@ -74,6 +94,8 @@ class _Solve(torch.autograd.Function):
         buf = _buffers(mpc, ctx.device)
         want_r = ctx.r_meta is not None and ctx.needs_input_grad[5]
         mbuf = _model_buffers(mpc, ctx.device) if want_r else None  # (before the adjoint: moving buffers makes nothing of it stale)
+        want_mu = ctx.mu_meta is not None and ctx.needs_input_grad[6]
+        lbuf = _limit_buffers(mpc, ctx.device) if want_mu else None
         seed = grad_output.detach().to(device=ctx.device, dtype=torch.float64).contiguous()
         mpc.solve_adjoint(seed.data_ptr(), torch.cuda.current_stream(ctx.device).cuda_stream)
         grads = []
@@ -86,6 +108,13 @@ class _Solve(torch.autograd.Function):
             mpc.adjoint_model(torch.cuda.current_stream(ctx.device).cuda_stream)
             shape, dtype, dev = ctx.r_meta
             grad_r = mbuf["grad_r"][:b].to(device=dev, dtype=dtype, copy=True).reshape(shape)
+        grad_mu = None
+        if want_mu:
+            mpc.adjoint_limits(seed.data_ptr(), torch.cuda.current_stream(ctx.device).cuda_stream)
+            shape, dtype, dev = ctx.mu_meta
+            grad_mu = lbuf["grad_limits"][:b, 0].to(device=dev, dtype=dtype, copy=True).reshape(shape)
+        if ctx.mu_meta is not None:
+            return (None, None) + tuple(grads) + (grad_r, grad_mu)
         return (None, None) + tuple(grads) + ((grad_r,) if ctx.r_meta is not None else ())
 
 
@@ -98,3 +127,14 @@ def differentiable_solve(mpc, fields, traj, weights, alpha_k, r=None):
     if r is None:
         return _Solve.apply(mpc, fields, traj, weights, alpha_k)
     return _Solve.apply(mpc, fields, traj, weights, alpha_k, r)
+
+
+def differentiable_solve_limits(mpc, fields, traj, weights, alpha_k, r=None, mu=None):
+    """``differentiable_solve`` with the instances' friction parameter as one more input (its own entry point: the older function keeps
+    its parameter list).  With a tensor ``mu`` [b] the instances solve under their own friction parameter (``set_instance_mu`` with a
+    float32 CUDA copy, which STAYS SET on the handle after the call: later solves of ``mpc`` use it until ``mpc.set_instance_mu(0)``),
+    and the backward returns its gradient too, by one more launch behind the adjoint (hmpc_adjoint_limits); with ``mu=None`` this is
+    ``differentiable_solve``: the same launches, every bit of the other gradients the same."""
+    if mu is None:
+        return differentiable_solve(mpc, fields, traj, weights, alpha_k, r)
+    return _Solve.apply(mpc, fields, traj, weights, alpha_k, r, mu)

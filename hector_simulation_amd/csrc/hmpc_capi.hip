@@ -1165,6 +1165,87 @@ int hmpc_download_adjoint_model(hmpc_handle *h, double *grad_A, double *grad_B, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Limit gradients: the gradients of the adjoint's loss in the constraint block, the bounds and, through the assembly's rows, mu, lt, lh
+// and the Fz caps (hmpc_limit_adjoint.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next limit gradients go: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int limit_adjoint_buffers(hmpc_handle *h, hmpc::LimitAdjointOut *b) {
+  const size_t mb = (size_t)h->max_batch, nc = (size_t)h->nc, u = 6 * nc, ls = 10 * nc * (size_t)h->setup.horizon;
+  HIP_TRY(h->d_ladj_limits.ensure(mb * (3 + nc)));
+  HIP_TRY(h->d_ladj_Fc.ensure(mb * 8 * nc * u));
+  HIP_TRY(h->d_ladj_bound.ensure(mb * ls));
+  HIP_TRY(h->d_ladj_lambda.ensure(mb * ls));
+  HIP_TRY(h->d_ladj_nu.ensure(mb * ls));
+  HIP_TRY(h->d_ladj_summary.ensure(mb * hmpc::LADJ_SUMMARY));
+  *b = {h->d_ladj_limits.get(), h->d_ladj_Fc.get(), h->d_ladj_bound.get(), h->d_ladj_lambda.get(), h->d_ladj_nu.get(), h->d_ladj_summary.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_adjoint_limits(hmpc_handle *h, double *device_grad_limits, double *device_grad_Fc, double *device_grad_bound,
+                                   double *device_lambda, double *device_nu, double *device_summary) {
+  if (!h) return HMPC_E_ARG;
+  h->d_ladj_limits.set_caller(device_grad_limits), h->d_ladj_Fc.set_caller(device_grad_Fc), h->d_ladj_bound.set_caller(device_grad_bound);
+  h->d_ladj_lambda.set_caller(device_lambda), h->d_ladj_nu.set_caller(device_nu), h->d_ladj_summary.set_caller(device_summary);
+  h->results.retarget_limit_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint_limits(hmpc_handle *h, double **device_grad_limits, double **device_grad_Fc, double **device_grad_bound,
+                                   double **device_lambda, double **device_nu, double **device_summary) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::LimitAdjointOut b;
+  const int rc = limit_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_grad_limits) *device_grad_limits = b.grad_limits;
+  if (device_grad_Fc) *device_grad_Fc = b.grad_Fc;
+  if (device_grad_bound) *device_grad_bound = b.grad_bound;
+  if (device_lambda) *device_lambda = b.lambda;
+  if (device_nu) *device_nu = b.nu;
+  if (device_summary) *device_summary = b.summary;
+  return HMPC_OK;
+}
+
+int hmpc_adjoint_limits(hmpc_handle *h, const double *device_seed, void *stream) {
+  if (!h || !device_seed || !h->results.has_adjoint()) return HMPC_E_ARG;  // no adjoint of the last solve of the current batch: dir is another seed's, or none
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::AdjointOut adj;
+  int rc = adjoint_buffers(h, &adj);  // (where that adjoint went: moving them would have made it stale)
+  if (rc != HMPC_OK) return rc;
+  hmpc::LimitAdjointOut b;
+  rc = limit_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_limit_adjoint(h->nc, a, h->cert_act_tol, adj.dir, device_seed, b, (hipStream_t)stream));
+  h->results.on_limit_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint_limits(hmpc_handle *h, double *grad_limits, double *grad_Fc, double *grad_bound, double *lambda, double *nu,
+                                 double *summary) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_limit_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint of the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::LimitAdjointOut b;
+  const int rc = limit_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, nc = (size_t)h->nc, u = 6 * nc, ls = 10 * nc * (size_t)h->setup.horizon, d = sizeof(double);
+  if (grad_limits) HIP_TRY(hipMemcpy(grad_limits, b.grad_limits, n * (3 + nc) * d, hipMemcpyDeviceToHost));
+  if (grad_Fc) HIP_TRY(hipMemcpy(grad_Fc, b.grad_Fc, n * 8 * nc * u * d, hipMemcpyDeviceToHost));
+  if (grad_bound) HIP_TRY(hipMemcpy(grad_bound, b.grad_bound, n * ls * d, hipMemcpyDeviceToHost));
+  if (lambda) HIP_TRY(hipMemcpy(lambda, b.lambda, n * ls * d, hipMemcpyDeviceToHost));
+  if (nu) HIP_TRY(hipMemcpy(nu, b.nu, n * ls * d, hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, n * hmpc::LADJ_SUMMARY * d, hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

@@ -146,6 +146,49 @@ __device__ __forceinline__ int free_directions(const float *Fc, const int c, con
   return normals;
 }
 
+// The first loop of free_directions once more, for the limit gradients (hmpc_limit_adjoint.h): the same decisions over the same chains,
+// and which rows j' were admitted -- nibble b of `rows` is j_b, ascending.  q[36] receives the admitted normals' orthonormal vectors
+// q_0 .. q_{m-1} only (bit for bit free_directions' first m); returns m.  A function of its own beside free_directions, which does not
+// call it: an out-parameter there would change the machine code of the gains' and the adjoint's kernels (scripts/isa_hash.py --diff).
+// tests/src/limit_adjoint_on_host.cpp pins the two against each other.  Change both or neither.
+template <int NC>
+__device__ __forceinline__ int admitted_normals(const float *Fc, const int c, const double *s, const double act_tol, double *q, unsigned &rows_out) {
+  constexpr int U = 6 * NC;
+  const float *rows = Fc + 8 * c * U;
+  int m = 0;
+  unsigned list = 0;
+  for (int j = 0; j < 10; ++j) {
+    if (!(s[j] <= act_tol)) continue;
+    double v[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = cert_sign(j) * (double)rows[cert_src(j) * U + fb_col<NC>(c, k)];
+    double len2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) len2 = __builtin_fma(v[k], v[k], len2);
+    for (int pass = 0; pass < 2; ++pass)
+      for (int a = 0; a < m; ++a) {
+        const double *qa = q + 6 * a;
+        double d = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) d = __builtin_fma(qa[k], v[k], d);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v[k] = __builtin_fma(0.0 - d, qa[k], v[k]);
+      }
+    double rem2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rem2 = __builtin_fma(v[k], v[k], rem2);
+    if (m < 6 && rem2 > 0.0 && rem2 >= FB_DEPENDENT * len2) {
+      const double len = __builtin_sqrt(rem2);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) q[6 * m + k] = v[k] / len;
+      list |= (unsigned)j << (4 * m);
+      ++m;
+    }
+  }
+  rows_out = list;
+  return m;
+}
+
 // What the adjoint's vector recursion (hmpc_adjoint.h) adds to a step of the backward pass: l_i, p_{i+1}, where p_i and k_i go.  The gains
 // leave it empty.
 struct RiccatiVec {

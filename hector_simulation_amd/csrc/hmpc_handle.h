@@ -12,6 +12,7 @@
 #include "hmpc_feedback.h"
 #include "hmpc_adjoint.h"
 #include "hmpc_model_adjoint.h"
+#include "hmpc_limit_adjoint.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -132,6 +133,10 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // [max_batch][4] and costate [max_batch][2][13] binary64; to the caller's buffers (hmpc_set_device_adjoint_model) or the handle's own,
   // allocated by the first call that needs them
   OutputBuffer<double> d_madj_A, d_madj_B, d_madj_r, d_madj_params, d_madj_costate;
+  // limit gradients (hmpc_adjoint_limits): grad_limits [max_batch][3 + nc], grad_Fc [max_batch][8 nc][6 nc], grad_bound, lambda and nu
+  // [max_batch][horizon][nc][10] and summary [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_limits) or the
+  // handle's own, allocated by the first call that needs them
+  OutputBuffer<double> d_ladj_limits, d_ladj_Fc, d_ladj_bound, d_ladj_lambda, d_ladj_nu, d_ladj_summary;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

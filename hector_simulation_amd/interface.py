@@ -511,6 +511,43 @@ class BatchedMPC:
                                                                                                  grad_params_ptr, costate_ptr)]),
                "hmpc_set_device_adjoint_model")
 
+    LIMIT_ADJOINT_KEYS = ("grad_limits", "grad_Fc", "grad_bound", "lambda", "nu", "summary")
+
+    def adjoint_limits(self, seed_ptr: int, stream: int = 0) -> None:
+        """One launch behind ``solve_adjoint`` on ``stream``: from the ``dir`` that adjoint left and the seed it was given (``seed_ptr``
+        again: float64[batch, horizon, 6 contacts] in HBM), the gradients of the same loss in the constraint block, the bounds, mu, lt, lh
+        and the Fz caps (include/hector_mpc.h hmpc_adjoint_limits).  Raises when no adjoint of the last solve of the current batch has
+        been enqueued."""
+        _check(self.L.hmpc_adjoint_limits(self.h, C.c_void_p(int(seed_ptr or 0)), C.c_void_p(stream)), "hmpc_adjoint_limits")
+
+    def download_adjoint_limits(self) -> dict:
+        """grad_limits float64[batch, 3 + contacts] (mu, lt, lh, the Fz cap of every contact), grad_Fc float64[batch, 8 contacts,
+        6 contacts], grad_bound / lambda / nu float64[batch, horizon, contacts, 10] and summary float64[batch, 3].  Waits; runs no safe
+        pass."""
+        b, nc, hz = self.batch, self.contacts, self.horizon
+        out = dict(grad_limits=np.zeros((b, 3 + nc)), grad_Fc=np.zeros((b, 8 * nc, 6 * nc)), grad_bound=np.zeros((b, hz, nc, 10)),
+                   nu=np.zeros((b, hz, nc, 10)), summary=np.zeros((b, 3)))
+        out["lambda"] = np.zeros((b, hz, nc, 10))
+        _check(self.L.hmpc_download_adjoint_limits(self.h, *[out[k].ctypes.data for k in self.LIMIT_ADJOINT_KEYS]),
+               "hmpc_download_adjoint_limits")
+        return out
+
+    def get_device_adjoint_limits(self) -> dict:
+        """Device pointers of where the next limit gradients go, by the names of ``download_adjoint_limits`` (the handle's own buffers are
+        allocated here if they were not yet)."""
+        ptrs = [C.c_void_p() for _ in self.LIMIT_ADJOINT_KEYS]
+        _check(self.L.hmpc_get_device_adjoint_limits(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_limits")
+        return {k: int(p.value or 0) for k, p in zip(self.LIMIT_ADJOINT_KEYS, ptrs)}
+
+    def set_device_adjoint_limits(self, grad_limits_ptr: int = 0, grad_Fc_ptr: int = 0, grad_bound_ptr: int = 0, lambda_ptr: int = 0,
+                                  nu_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later limit gradients (shapes of ``download_adjoint_limits`` with max_batch rows; 0 / None = the
+        handle's own)."""
+        self._keep_ladj = keepalive
+        _check(self.L.hmpc_set_device_adjoint_limits(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_limits_ptr, grad_Fc_ptr, grad_bound_ptr,
+                                                                                                  lambda_ptr, nu_ptr, summary_ptr)]),
+               "hmpc_set_device_adjoint_limits")
+
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where
         the last solve handed instance i's working set over and nothing has consumed it yet, else -1."""

@@ -623,8 +623,9 @@ double hmpc_legacy_feedback_gain(int component, int state);
  *        grad_alpha[batch][U]    = sum_{i<h} (u_i[c] + u_i[c]) du_i[c]
  *        dir[batch][h][U]        = du_i.  It is -Z (Z'HZ)^-1 Z' l of the condensed QP; the gradient in any other parameter theta is
  *                                  sum dir . d(Hu + g)/d theta: hmpc_adjoint_model below returns it for r, the mass and the body inertia
- *                                  (gravity is grad_x0[12]); left to the caller are the orientation (through grad_A, grad_B and grad_x0
- *                                  of these calls), and mu, lt, lh, the caps and the joint angles.
+ *                                  (gravity is grad_x0[12]) and hmpc_adjoint_limits further below for mu, lt, lh and the Fz caps, which
+ *                                  enter through the constraint block; left to the caller are the orientation and the joint angles
+ *                                  (through grad_A, grad_B, grad_x0 and grad_Fc of these calls).
  *        summary[batch][2]       [0] the smallest pivot ratio: hmpc_feedback_gains' summary[0], bit for bit; [1] max |dir| (a NaN
  *                                  entry counts as +inf).
  *   6. Meaning.  The outputs are the derivatives of L(u*(x0, X_d, w, Alpha_K)) with the linearisation (Acd, Bcd, Fc) and the active
@@ -687,6 +688,7 @@ int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, do
  *      gradient in the gravity state is grad_x0[12] of the adjoint: nothing new is needed.  A zero seed gives zeros; columns of G_B on a
  *      contact that is swing at every step are exactly 0 (u and dir are 0 there).  No loop iterates on data, so NaN input ends like any
  *      other.  The result is a pure function of (record, hmpc_params, per-instance mu, force buffer, dir buffer).
+ *      What enters through the constraint block instead (mu, lt, lh, the Fz caps) is hmpc_adjoint_limits' below.
  *
  * hmpc_adjoint_model enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It reads
  * dir where the last adjoint wrote it.  HMPC_E_ARG, nothing enqueued: no adjoint of the last solve of the current batch has been enqueued
@@ -704,6 +706,74 @@ int hmpc_set_device_adjoint_model(hmpc_handle *h, double *device_grad_A, double 
 int hmpc_get_device_adjoint_model(hmpc_handle *h, double **device_grad_A, double **device_grad_B, double **device_grad_r,
                                   double **device_grad_params, double **device_costate);
 int hmpc_download_adjoint_model(hmpc_handle *h, double *grad_A, double *grad_B, double *grad_r, double *grad_params, double *costate);
+/* ---- limit gradients of the solve: friction, foot length, the Fz caps, the constraint block itself ----
+ * Behind hmpc_solve_adjoint: the gradient of the same loss in what enters the QP through the constraint block.  Per stance leg-step
+ * (i, c), v = u_i[cols(c)], the ten one-sided slacks are s_j'(v) = n_j' . v + beta_j' with n_j' = sigma_j' Fc[8c + src(j')][cols(c)] (src
+ * and sigma of hmpc_kkt_certificate) and beta = (0, 0, 0, 0, 0, (double)0.01f, 0, 0, 0, (double)ub7); the QP is min f(u) s.t. s >= 0.  With
+ * the admitted active normals frozen, stationarity reads grad f = sum lambda_j' n_j'; for the loss L(u) with seed l = dL/du and the
+ * adjoint's dir, rho_i = l_i + (H dir)_i and rho_i[cols(c)] = sum nu_j' n_j' on every stance leg-step (exact when dir and l belong
+ * together), and
+ *   dL/dtheta = (what hmpc_solve_adjoint / hmpc_adjoint_model return)
+ *               - sum_{i,c,j'} lambda_j' (dn_j'/dtheta . dir_i[cols(c)]) - sum_{i,c,j'} nu_j' (dn_j'/dtheta . v + dbeta_j'/dtheta).
+ * One stance leg-step with only the Fz cap active (n_9 = (0, 0, -2, 0, 0, 0)), dir = 0 and the seed e_Fz: nu_9 = -0.5, dL/dub7 = +0.5.
+ * Per instance, NC contacts, U = 6 NC; the assembly enters exactly as for hmpc_solve_adjoint (hmpc_params and hmpc_set_instance_mu
+ * included), u_i[U] is step i of the force buffer as it stands, du_i[U] step i of the adjoint's dir buffer as it stands, l_i[U] step i of
+ * device_seed.  Everything below is binary64.  Every sum is one ascending chain of explicit fused multiply-adds started at +0; trip
+ * counts are fixed by (h, NC) and the number of admitted normals (<= 6): no loop iterates on data.
+ *   1. Forward and backward pass: items 1 and 2 of hmpc_adjoint_model, chain for chain: x_j, dx_j over the stored dir, then c_j, d_j.
+ *   2. Gradient and residual, a2 = alpha + alpha:
+ *        grad_i[k] = fma(a2[k], u_i[k],  sum_{a<13} B[a][k] c_{i+1}[a])
+ *        hd_i[k]   = fma(a2[k], du_i[k], sum_{a<13} B[a][k] d_{i+1}[a])
+ *        rho_i[k]  = l_i[k] + hd_i[k]
+ *   3. Slacks, stance rule, active set: hmpc_constraint_margins' and hmpc_kkt_certificate's (j' active iff s_j' <= act_tol, NaN: not
+ *      active), with the handle's act_tol (hmpc_set_certificate_tolerance).
+ *   4. Admitted normals: the adjoint's own -- the decisions of hmpc_feedback_gains' item 2 (modified Gram-Schmidt applied twice, rule
+ *      1e-12, at most six, ascending j').  q_0 .. q_{m-1} are the orthonormal vectors held, j_0 < .. < j_{m-1} the admitted rows.
+ *   5. Multipliers.  T[a][b] = sum_{k<6} q_a[k] n_{j_b}[k] for a <= b, y_a = sum_{k<6} q_a[k] rhs[k]; for a = m-1 down to 0
+ *        x_a = (y_a - sum_{b = a+1 .. m-1} T[a][b] x_b) / T[a][a].
+ *      rhs = grad_i[cols(c)] gives lambda_{j_a} = x_a: the frozen set's multiplier, no sign constraint, reported as it comes;
+ *      rhs = rho_i[cols(c)] gives nu_{j_a} = x_a.  Rows not admitted and swing leg-steps get exact zeros.
+ *      Residual of either: e[k] = rhs[k] - sum_{b<m} n_{j_b}[k] x_b.
+ *   6. Row gradients.  One chain per entry over i ascending and, inside a step, over the j' of the row ascending (rows 4 and 7 of a
+ *      contact serve two j'), zero multipliers included:
+ *        grad_Fc[8c + src(j')][col_k] <- fma(0 - sigma_j' lambda_j', du_i[col_k], .), then fma(0 - sigma_j' nu_j', (double)u_i[col_k], .)
+ *      Entries outside the row's own cols(c) are exact zeros.
+ *   7. Bound gradients.  grad_bound[i][c][j'] = 0 - nu_j' is dL/dbeta_j', raising beta_j' loosening limit j': index 5 is the Mx window,
+ *      index 9 is ub7.
+ *   8. Chain rules (the assembly's formulas are differentiated, not its binary32 rounding), G = grad_Fc:
+ *        grad_mu     = over c ascending from +0: + G[8c+1][3c] - G[8c+0][3c] + G[8c+3][3c+1] - G[8c+2][3c+1]; also the gradient in the
+ *                      instance's own mu under hmpc_set_instance_mu
+ *        grad_lt     = (sum_c sum_{k<3} G[8c+5][3c+k] (double)Fc[8c+5][3c+k]) / lt;  grad_lh the same over row 6 and lh.  lt, lh: the handle's
+ *                      hmpc_params values widened; a zero lt / lh gives what IEEE division gives (0/0 = NaN, x/0 = +-inf)
+ *        grad_cap[c] = sum_i grad_bound[i][c][9] (double)(float)gait[NC i + c]
+ *        grad_limits[batch][3 + NC] = (mu, lt, lh, cap_0 .. cap_{NC-1}).  f_max is cap_0 + cap_1; the hand's cap is cap_2.
+ *   9. summary[batch][3]: maxima over the stance leg-steps, a NaN candidate counting as +inf, 0 with no candidate:
+ *        [0] |grad - sum lambda n|_inf;  [1] |rho - sum nu n|_inf -- 0 in exact arithmetic when the seed is the one dir was made from: the
+ *        caller's consistency check;  [2] max |grad_Fc|.
+ *  10. Meaning.  The frozen-set derivatives, as for hmpc_feedback_gains, hmpc_solve_adjoint and hmpc_adjoint_model.  At a leg-step
+ *      whose active rows are dependent (an unloaded foot: eight rows, rank 5) the admitted subset's gradient is reported.  Flagged
+ *      instances are computed all the same.  The joint angles and the orientation go through grad_Fc (with grad_A, grad_B, grad_x0).
+ *      The result is a pure function of (record, hmpc_params, per-instance mu, force buffer, dir buffer, seed, act_tol).
+ *
+ * hmpc_adjoint_limits enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It reads
+ * dir where the last adjoint wrote it and device_seed[batch][h][U] (binary64, caller-owned): the seed that adjoint was given, passed again
+ * -- summary[1] tells whether it was.  HMPC_E_ARG, nothing enqueued: device_seed is NULL, or no adjoint of the last solve of the current
+ * batch has been enqueued (every solve, every new batch and hmpc_set_device_adjoint make an adjoint stale).
+ * hmpc_set_device_adjoint_limits: caller-owned device buffers for later calls (any may be NULL = the handle's own, allocated for max_batch
+ * by the first call that needs them; never inside hmpc_solve): grad_limits[max_batch][3 + NC], grad_Fc[max_batch][8 NC][U], grad_bound,
+ * lambda and nu [max_batch][horizon][NC][10], summary[max_batch][3].  Moving the buffers makes limit gradients already computed stale, as
+ * do every solve, every new batch, every hmpc_solve_adjoint (a new seed) and hmpc_set_device_adjoint; hmpc_adjoint_model does not.
+ * hmpc_get_device_adjoint_limits: where the next limit gradients go; any pointer may be NULL.  hmpc_download_adjoint_limits waits for the
+ * stream of the last call, then copies (any pointer may be NULL); HMPC_E_ARG when nothing has been computed since the last adjoint.  It
+ * does NOT run the safe pass.  With no batch set (batch = 0) it copies nothing and returns HMPC_OK.
+ * Device groups: per member, through hmpc_group_member.  There is no accessor on the process-global solver. */
+int hmpc_adjoint_limits(hmpc_handle *h, const double *device_seed, void *stream);
+int hmpc_set_device_adjoint_limits(hmpc_handle *h, double *device_grad_limits, double *device_grad_Fc, double *device_grad_bound,
+                                   double *device_lambda, double *device_nu, double *device_summary);
+int hmpc_get_device_adjoint_limits(hmpc_handle *h, double **device_grad_limits, double **device_grad_Fc, double **device_grad_bound,
+                                   double **device_lambda, double **device_nu, double **device_summary);
+int hmpc_download_adjoint_limits(hmpc_handle *h, double *grad_limits, double *grad_Fc, double *grad_bound, double *lambda, double *nu,
+                                 double *summary);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size

@@ -1,0 +1,408 @@
+"""numpy restatement (float64) of the limit gradients' definition (include/hector_mpc.h hmpc_adjoint_limits; csrc/hmpc_limit_adjoint.h), fed
+with the oracle's binary32 assembly of a record, a force vector, the adjoint mirror's dir and its seed; the dense frozen-set QP with its
+admitted rows as equalities that it is checked against; a float64 restatement of how mu, lt, lh and the caps enter the constraint block;
+and what the limit-gradient tests share: the shapes (test_certificate_mirror.CASES plus three at f_max = 40, where the Fz cap is active)
+and the measured bounds.  numpy has no fma, so the GPU's chains differ from these by binary64 round-off only."""
+import numpy as np
+
+import adjoint_mirror as am
+import certificate_mirror as cm
+import feedback_mirror as fm
+import margins_mirror as mm
+from hector_simulation_amd import records, synthetic
+
+MIRROR_TOL = am.MIRROR_TOL
+ACT_TOL = fm.ACT_TOL
+KEYS = ("grad_limits", "grad_Fc", "grad_bound", "lambda", "nu", "summary")
+MU, LT, LH = 2.0, float(np.float32(0.09)), float(np.float32(0.06))  # hmpc_default_params
+LOW_CAP = 40.0
+# the shapes of test_certificate_mirror.CASES whose Fz cap is active at f_max = 40 (at the default 500 it is active nowhere but at one
+# leg-step of hard_6x): every test that speaks of caps runs these as well
+LOW_CAP_SHAPES = ("standing", "walking", "standing_3c")
+GROUPS = ("mu", "lt", "lh", "cap")
+GROUP_ROWS = dict(mu=(0, 1, 2, 3), lt=(6,), lh=(7,), cap=(9,))  # the j' whose normal or bound the group moves
+# Central differences of l.u* in the dense frozen-set QP (DenseLimits: float64, anchored at the given forces, the admitted rows held as
+# equalities at their found slack values) at a step of FD_DENSE_STEP, each error relative to max(1, |value|) of what it is compared with:
+#   under random dFc inside each row's own cols(c) (uniform(-1, 1) x 1e-2: the rows are of size 1, and l.u* is strongly curved in them)
+#   and random dbeta (uniform(-1, 1)) against <grad_Fc, dFc> + <grad_bound, dbeta>, both, dFc alone, dbeta alone:  DENSE_FC_E_MEASURED
+#   under moves of mu, lt, lh and every cap through constraint_block / bounds below against grad_limits:               DENSE_L_E_MEASURED
+# The largest error measured over ALL_CASES (tests/test_limit_adjoint_mirror.py prints it per shape); each bound is twice that.
+FD_DENSE_STEP = 1e-6
+DFC_SCALE = 1e-2
+DENSE_FC_E_MEASURED = 5.40e-6  # (hard_6x; per entry 4.4e-7, 3.9e-8, 1.5e-7, 4.8e-7, 3.7e-9, 5.1e-7, 3.0e-6, 5.4e-6; cap40: 3.5e-7, 2.3e-8, 1.3e-6)
+DENSE_L_E_MEASURED = 3.74e-5  # (hard_3x, lh; per entry 6.5e-6, 3.1e-7, 8.0e-7, 4.7e-6, 9.1e-9, 4.2e-6, 3.7e-5, 2.8e-5; cap40: 2.7e-6, 1.2e-7,
+#                               2.2e-6; by group: mu <= 3.3e-6, lt <= 4.2e-6, lh <= 3.7e-5, caps <= 1.3e-9.  The step in lh is 6e-8, the smallest:
+#                               the round-off of the dense KKT solve divided by it is what is seen there)
+DENSE_FC = 2 * DENSE_FC_E_MEASURED
+DENSE_L = 2 * DENSE_L_E_MEASURED
+
+
+def all_cases(cases):
+    """[(id, case, f_max)]: every case at the default f_max, then the LOW_CAP_SHAPES at f_max = 40."""
+    out = [(name, case, float(synthetic.F_MAX)) for name, case in cases]
+    return out + [(name + "_cap40", case, LOW_CAP) for name, case in cases if name in LOW_CAP_SHAPES]
+
+
+def caps_row(un, k, nc, f_max):
+    return [np.float32(f_max)] * 2 + ([np.float32(np.asarray(un["f_max_hand"][k]).reshape(-1)[0])] if nc == 3 else [])
+
+
+def reference_forces(oracle, rec, h, nc, f_max):
+    """The reference's qpOASES forces of every record under the feet's cap f_max, rounded to binary32: float32[b, h, 6 nc]."""
+    return qp_forces64(oracle, rec, h, nc, f_max).astype(np.float32)
+
+
+def admitted(N, active):
+    """(rows j_0 < .. < j_{m-1}, [q_0 .. q_{m-1}]): the first loop of feedback_mirror.free_directions, operation for operation, and which
+    rows it admitted (admitted_normals of csrc/hmpc_feedback.h)."""
+    held, rows = [], []
+
+    def reduce(v):
+        v = v.copy()
+        for _ in range(2):
+            for q in held:
+                d = 0.0
+                for k in range(6):
+                    d = d + q[k] * v[k]
+                v = v - d * q
+        return v
+
+    def norm2(v):
+        acc = 0.0
+        for k in range(6):
+            acc = acc + v[k] * v[k]
+        return acc
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for j in active:
+            v = np.asarray(N[:, j], dtype=np.float64)
+            len2 = norm2(v)
+            v = reduce(v)
+            rem2 = norm2(v)
+            if len(held) < 6 and rem2 > 0.0 and rem2 >= fm.DEPENDENT * len2:
+                held.append(v / np.sqrt(rem2))
+                rows.append(j)
+    return rows, held
+
+
+def multipliers(N, rows, Q, rhs):
+    """(x[m], e[6]): T = Q' N upper triangular, back substitution from a = m-1 down; e = rhs - N x."""
+    m = len(rows)
+    x = np.zeros(m)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for a in range(m - 1, -1, -1):
+            acc = 0.0
+            for b in range(a + 1, m):
+                acc = acc + float(Q[a] @ N[:, rows[b]]) * x[b]
+            x[a] = (float(Q[a] @ rhs) - acc) / float(Q[a] @ N[:, rows[a]])
+        acc = np.zeros(6)
+        for b in range(m):
+            acc = acc + N[:, rows[b]] * x[b]
+    return x, rhs - acc
+
+
+def nan_max(values):
+    """max with NaN counting as +inf; 0 with no candidate."""
+    best = 0.0
+    for v in np.asarray(values, dtype=np.float64).reshape(-1):
+        v = np.inf if np.isnan(v) else abs(v)
+        best = v if v > best else best
+    return best
+
+
+def limit_adjoint(Acd, Bcd, x0, weights, traj, alpha, Fc, u, dirn, seed, gait, caps, nc, act_tol=ACT_TOL, lt=LT, lh=LH):
+    """The definition for one instance: u[h, U] the forces, dirn[h, U] the adjoint's dir, seed[h, U]; also `rows` {(i, c): admitted j'}."""
+    A, B = np.asarray(Acd, dtype=np.float64), np.asarray(Bcd, dtype=np.float64)
+    w, al = np.asarray(weights, dtype=np.float64), np.asarray(alpha, dtype=np.float64)
+    F = np.asarray(Fc, dtype=np.float64)
+    u32 = np.asarray(u)
+    u, du, ell = np.asarray(u, dtype=np.float64), np.asarray(dirn, dtype=np.float64), np.asarray(seed, dtype=np.float64)
+    h, U = u.shape
+    tr = np.concatenate([np.asarray(traj, dtype=np.float64).reshape(h, 12), np.zeros((h, 1))], axis=1)
+    q2, a2 = np.concatenate([w + w, [0.0]]), al + al
+    g = np.asarray(gait).reshape(h, nc)
+    slack, _ = mm.slacks(Fc, u32, gait, caps)
+    stance, _ = mm.stance_mask(gait, caps, h, nc)
+    N = [cm.normals(Fc, c, nc) for c in range(nc)]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        x, dx = np.zeros((h + 1, 13)), np.zeros((h + 1, 13))
+        x[0] = np.asarray(x0, dtype=np.float64)
+        for i in range(h):
+            x[i + 1] = A @ x[i] + B @ u[i]
+            dx[i + 1] = A @ dx[i] + B @ du[i]
+        c, d = np.zeros((h + 2, 13)), np.zeros((h + 2, 13))
+        for j in range(h, 0, -1):
+            e = x[j] - tr[j - 1]
+            e[12] = 0.0
+            c[j] = q2 * e + A.T @ c[j + 1]
+            d[j] = q2 * dx[j] + A.T @ d[j + 1]
+        grad, rho = np.zeros((h, U)), np.zeros((h, U))
+        for i in range(h):
+            grad[i] = a2 * u[i] + B.T @ c[i + 1]
+            rho[i] = ell[i] + (a2 * du[i] + B.T @ d[i + 1])
+        lam, nu = np.zeros((h, nc, 10)), np.zeros((h, nc, 10))
+        G = np.zeros((8 * nc, U))
+        rows, e_l, e_n = {}, [], []
+        for i in range(h):
+            for cc in range(nc):
+                if not stance[i, cc]:
+                    continue
+                co = cm.cols(cc, nc)
+                rows[(i, cc)], Q = admitted(N[cc], cm.active_set(slack[i, cc], act_tol))
+                xl, el = multipliers(N[cc], rows[(i, cc)], Q, grad[i, co])
+                xn, en = multipliers(N[cc], rows[(i, cc)], Q, rho[i, co])
+                e_l.append(el), e_n.append(en)
+                for b, j in enumerate(rows[(i, cc)]):
+                    lam[i, cc, j], nu[i, cc, j] = xl[b], xn[b]
+        for i in range(h):  # one chain per entry: i ascending, inside a step j' ascending, the lambda term first
+            for cc in range(nc):
+                co = cm.cols(cc, nc)
+                for j in range(10):
+                    r = 8 * cc + cm.SRC[j]
+                    G[r, co] = G[r, co] + (0.0 - cm.SIGMA[j] * lam[i, cc, j]) * du[i, co]
+                    G[r, co] = G[r, co] + (0.0 - cm.SIGMA[j] * nu[i, cc, j]) * u[i, co]
+        gb = 0.0 - nu
+        lim = np.zeros(3 + nc)
+        for cc in range(nc):
+            lim[0] = lim[0] + G[8 * cc + 1, 3 * cc]
+            lim[0] = lim[0] - G[8 * cc, 3 * cc]
+            lim[0] = lim[0] + G[8 * cc + 3, 3 * cc + 1]
+            lim[0] = lim[0] - G[8 * cc + 2, 3 * cc + 1]
+            for k in range(3):
+                lim[1] = lim[1] + G[8 * cc + 5, 3 * cc + k] * F[8 * cc + 5, 3 * cc + k]
+                lim[2] = lim[2] + G[8 * cc + 6, 3 * cc + k] * F[8 * cc + 6, 3 * cc + k]
+            for i in range(h):
+                lim[3 + cc] = lim[3 + cc] + gb[i, cc, 9] * float(np.float32(g[i, cc]))
+        lim[1], lim[2] = np.float64(lim[1]) / np.float64(lt), np.float64(lim[2]) / np.float64(lh)
+        summary = np.array([nan_max(e_l), nan_max(e_n), nan_max(G)])
+    out = dict(grad_limits=lim, grad_Fc=G, grad_bound=gb, nu=nu, summary=summary, grad=grad, rho=rho, rows=rows, stance=stance, slack=slack)
+    out["lambda"] = lam
+    return out
+
+
+def limit_adjoint_records(oracle, rec, h, nc, forces, dirs, seeds, f_max=synthetic.F_MAX, mu=None, act_tol=ACT_TOL, lt=LT, lh=LH):
+    """The definition over a batch of packed records: dict of the KEYS (stacked) and per instance `rows`, `grad`, `rho`, `stance`, `slack`,
+    `Fc`.  The oracle's assembly is taken under whatever constants it is set to; mu[b]: a per-instance friction parameter."""
+    nb, U = rec.shape[0], 6 * nc
+    un = records.unpack_records(rec, h, nc)
+    res = []
+    for k in range(nb):
+        o = mm.assemble(oracle, rec[k], h, nc, None if mu is None else mu[k])
+        unk = cm.unpacked_row(un, k)
+        d = limit_adjoint(o["Acd"], o["Bcd"], o["x0"], unk["weights"], unk["traj"], unk["Alpha_K"], o["Fc"], np.asarray(forces[k]).reshape(h, U),
+                          np.asarray(dirs[k]).reshape(h, U), np.asarray(seeds[k]).reshape(h, U), unk["gait"], caps_row(un, k, nc, f_max), nc,
+                          act_tol, lt, lh)
+        d["Fc"] = o["Fc"]
+        res.append(d)
+    out = {key: np.stack([r[key] for r in res]) for key in KEYS + ("grad", "rho", "stance", "slack", "Fc")}
+    out["rows"] = [r["rows"] for r in res]
+    return out
+
+
+def coverage(rows_list):
+    """Admitted active rows per parameter group over a batch: {group: count}."""
+    n = {g: 0 for g in GROUPS}
+    for rows in rows_list:
+        for js in rows.values():
+            for g in GROUPS:
+                n[g] += sum(1 for j in js if j in GROUP_ROWS[g])
+    return n
+
+
+def assert_covered(rows_list, groups, what=""):
+    """The condition on a test's input: every group it speaks of has at least one admitted active row in the batch."""
+    n = coverage(rows_list)
+    print(what, "admitted active rows per group", n)
+    for g in groups:
+        assert n[g] > 0, (what, g, n)
+    return n
+
+
+# What each batch can cover: the groups with at least one admitted active row at qpOASES' forces, counted on the CPU (mu, lt, lh, cap):
+# standing 14, 25, 39, 0; walking 0, 6, 21, 0; mixed 5, 22, 24, 0; single_h20 0, 6, 50, 0; walking_h5 1, 0, 3, 0; standing_3c 84, 32, 19, 0;
+# hard_3x 184, 69, 121, 0; hard_6x 383, 107, 160, 1; at f_max = 40: standing 37, 51, 85, 302; walking 33, 29, 62, 160; standing_3c 91, 34,
+# 21, 114.  At the default f_max the cap is active nowhere but at one leg-step of hard_6x, so a default batch must cover what it can and
+# the three low-cap batches, part of every test, cover all four groups.
+COVERS = dict(standing="mu lt lh", walking="lt lh", mixed="mu lt lh", single_h20="lt lh", walking_h5="mu lh", standing_3c="mu lt lh",
+              hard_3x="mu lt lh", hard_6x="mu lt lh cap")
+
+
+def groups_of(name, f_max):
+    """The groups a batch must cover before anything is compared on it: all four at f_max = 40, COVERS at the default."""
+    return GROUPS if f_max == LOW_CAP else tuple(COVERS[name].split())
+
+
+def constraint_block(Fc, nc, mu, lt, lh, lt0=LT, lh0=LH):
+    """The constraint block as a float64 function of mu, lt and lh, as the assembly forms it: rows 0 .. 3 of a contact carry -mu, mu on Fx
+    and -mu, mu on Fy; the force columns of row 5 are -lt times a vector that does not depend on lt, those of row 6 the same with lh."""
+    F = np.asarray(Fc, dtype=np.float64).copy()
+    for c in range(nc):
+        F[8 * c + 0, 3 * c], F[8 * c + 1, 3 * c] = -mu, mu
+        F[8 * c + 2, 3 * c + 1], F[8 * c + 3, 3 * c + 1] = -mu, mu
+        F[8 * c + 5, 3 * c:3 * c + 3] *= lt / lt0
+        F[8 * c + 6, 3 * c:3 * c + 3] *= lh / lh0
+    return F
+
+
+class DenseLimits:
+    """l.u* of the frozen-set QP of one instance in float64 as a function of (Fc, beta): min 1/2 u'Hu + g'u s.t. n_j'(Fc).v + beta_j' = s_j'
+    on every admitted row, s the slack found at the base point, and the variables of swing leg-steps held at their values.  H and g are adjoint_mirror.DenseModel's (powers of Acd and Bcd); g is
+    anchored so that the given forces are the optimum at the base point (what DenseModel.anchor does for its null-space form): the part
+    of H u0 + g outside the span of the admitted normals is taken out of g.  It shares no code with the formulas under test: one dense
+    KKT solve."""
+
+    def __init__(self, Acd, Bcd, x0, traj, w, al, Fc, u0, rows, nc, stance):
+        dm = am.DenseModel(Acd, Bcd, [np.zeros((6 * nc, 0))] * np.asarray(u0).shape[0], u0)
+        h, U = dm.h, dm.U
+        s = np.tile(np.concatenate([np.asarray(w, dtype=np.float64), [0.0]]), h)
+        alt = np.tile(np.asarray(al, dtype=np.float64), h)
+        t13 = np.concatenate([np.asarray(traj, dtype=np.float64).reshape(h, 12), np.zeros((h, 1))], axis=1).reshape(-1)
+        self.H = 2.0 * (dm.Bq.T @ (s[:, None] * dm.Bq) + np.diag(alt))
+        g = 2.0 * (dm.Bq.T @ (s * (dm.Aq @ np.asarray(x0, dtype=np.float64) - t13)))
+        self.h, self.U, self.nc, self.u0 = h, U, nc, dm.u0
+        self.where = [(i, c, j) for (i, c), js in sorted(rows.items()) for j in js]
+        self.swing = [U * i + k for i in range(h) for c in range(nc) if not stance[i, c] for k in cm.cols(c, nc)]  # held at their values
+        self.Fc0 = np.asarray(Fc, dtype=np.float64)
+        E = self.rows_of(self.Fc0)
+        self.s0 = E @ self.u0  # (+ beta at the base point, which value() adds on both sides)
+        grad0 = self.H @ self.u0 + g
+        lam0 = np.linalg.lstsq(E.T, grad0, rcond=None)[0] if E.shape[0] else np.zeros(0)
+        self.g = g - (grad0 - E.T @ lam0)
+
+    def rows_of(self, Fc):
+        E = np.zeros((len(self.where) + len(self.swing), self.U * self.h))
+        for a, (i, c, j) in enumerate(self.where):
+            co = [self.U * i + k for k in cm.cols(c, self.nc)]
+            E[a, co] = cm.SIGMA[j] * Fc[8 * c + cm.SRC[j], cm.cols(c, self.nc)]
+        for a, v in enumerate(self.swing):
+            E[len(self.where) + a, v] = 1.0
+        return E
+
+    def value(self, ell, dFc=None, dbeta=None):
+        """l.u* with the block moved by dFc[8 nc, U] and the bounds by dbeta[h, nc, 10]."""
+        E = self.rows_of(self.Fc0 if dFc is None else self.Fc0 + dFc)
+        b = self.s0.copy()
+        if dbeta is not None:
+            b[:len(self.where)] -= np.array([dbeta[i, c, j] for i, c, j in self.where])
+        n, m = self.U * self.h, E.shape[0]
+        K = np.zeros((n + m, n + m))
+        K[:n, :n], K[:n, n:], K[n:, :n] = self.H, E.T, E
+        sol = np.linalg.solve(K, np.concatenate([0.0 - self.g, b]))
+        return float(np.asarray(ell, dtype=np.float64).reshape(-1) @ sol[:n])
+
+    def central(self, ell, dFc=None, dbeta=None, step=FD_DENSE_STEP):
+        s = lambda m, sg: None if m is None else sg * step * m
+        return (self.value(ell, s(dFc, 1.0), s(dbeta, 1.0)) - self.value(ell, s(dFc, -1.0), s(dbeta, -1.0))) / (2.0 * step)
+
+
+def random_dFc(rng, nc):
+    """uniform(-1, 1) DFC_SCALE inside each row's own cols(c), zero elsewhere."""
+    d = np.zeros((8 * nc, 6 * nc))
+    for c in range(nc):
+        d[8 * c:8 * c + 8][:, cm.cols(c, nc)] = rng.uniform(-1.0, 1.0, (8, 6)) * DFC_SCALE
+    return d
+
+
+def adjoint_dirs(oracle, rec, h, nc, forces, seeds, f_max, mu=None, act_tol=ACT_TOL):
+    """dir[b, h, U] of the adjoint mirror under the feet's cap f_max (adjoint_mirror.adjoint_records has the default cap built in)."""
+    un = records.unpack_records(rec, h, nc)
+    out = np.zeros((rec.shape[0], h, 6 * nc))
+    for k in range(rec.shape[0]):
+        o = mm.assemble(oracle, rec[k], h, nc, None if mu is None else mu[k])
+        unk = cm.unpacked_row(un, k)
+        g = fm.gains_instance(o, unk, forces[k], h, nc, caps_row(un, k, nc, f_max), act_tol)
+        out[k] = am.adjoint(o["Acd"], o["Bcd"], o["x0"], unk["weights"], unk["traj"], unk["Alpha_K"], np.asarray(forces[k]).reshape(h, 6 * nc),
+                            g["Z"], np.asarray(seeds[k]).reshape(h, 6 * nc))["dir"]
+    return out
+
+
+# Finite differences of the reference's qpOASES against grad_limits . dtheta, E = |pred - l.(u1 - u0)| / max(1, max|u0|) over the kept
+# instances (equal active sets), per parameter group, in the protocol of model_adjoint_mirror.fd_model_case: mu, lt, lh multiplied by
+# 1 + s through oracle.set_params, the feet's cap f_max multiplied by 1 + s (pred = (grad_cap_0 + grad_cap_1) df), s = FD_L_STEP halved
+# until at most feedback_mirror.FD_LEFT_OUT_CAP of a batch is left out.  A group runs on the batches that cover it (groups_of).
+# Bounds: 2 x the largest E measured per group (tests/test_limit_adjoint_mirror.py prints them per batch); pooled over all kept
+# instances sum|pred - act| / sum|act| < FD_POOLED.
+FD_L_STEP = 1e-2
+# mu  (s = 1e-2; standing_3c 5e-3): standing 7.6e-7, mixed 5.5e-7, walking_h5 6.9e-7, standing_3c 8.8e-7, hard_3x 2.5e-6, hard_6x 1.02e-5;
+#     cap40: standing 2.5e-6, walking 1.3e-6, standing_3c 3.4e-6; pooled ratio 0.011
+# lt  (s = 1e-2): 4.4e-7, 1.5e-7, 3.8e-7, 1.6e-7 (single_h20), 5.2e-7 (standing_3c), 5.4e-7, 4.9e-7; cap40: 6.9e-7, 2.8e-8, 1.8e-7; pooled 0.0057
+# lh  (s = 1e-2): 2.2e-7, 1.0e-7, 2.7e-7, 3.1e-8, 2.0e-8, 9.9e-8, 2.4e-7, 5.9e-7 (the eight shapes in order); cap40: 2.4e-7, 1.5e-8, 7.3e-8;
+#     pooled 0.0030
+# cap (s = 1e-2; standing_3c_cap40 5e-3): hard_6x 4.5e-9; cap40: standing 9.7e-8, walking 4.8e-9, standing_3c 4.5e-8; pooled 5.0e-5 (l.u* is
+#     nearly linear in a cap that holds Fz)
+# At most 4 of 16 instances of a batch were left out (standing_cap40 under a moved cap); no batch had to be dropped.
+LADJ_FD_E_MEASURED = dict(mu=1.03e-5, lt=6.90e-7, lh=5.90e-7, cap=9.67e-8)
+LADJ_FD = {g: 2 * e for g, e in LADJ_FD_E_MEASURED.items()}
+FD_POOLED = am.FD_W_POOLED
+_fdl = {}
+
+
+def qp_forces64(oracle, rec, h, nc, f_max):
+    """The reference's qpOASES forces of every record under the feet's cap f_max and whatever constants the oracle is set to, float64."""
+    return np.stack([_qp_row(oracle, rec[k], h, nc, f_max) for k in range(rec.shape[0])])
+
+
+def _qp_row(oracle, rec_row, h, nc, f_max):
+    o = oracle.assemble_record(rec_row, h, synthetic.DT_MPC, f_max, reduce=True, nc=nc)
+    x, _, _, _, st = oracle.qpoases_solve(o["H_red"], o["g_red"], o["A_red"], o["lb_red"], o["ub_red"])
+    assert st == 0, st
+    u = np.zeros(6 * nc * h)
+    u[o["var_ind"]] = x
+    return u.reshape(h, 6 * nc)
+
+
+def active_sets(oracle, rec, h, nc, forces32, f_max):
+    """Per instance {leg-step: active j'} at the given forces under the oracle's current constants and the feet's cap f_max."""
+    un = records.unpack_records(rec, h, nc)
+    out = []
+    for k in range(rec.shape[0]):
+        o = mm.assemble(oracle, rec[k], h, nc)
+        caps = caps_row(un, k, nc, f_max)
+        slack, _ = mm.slacks(o["Fc"], np.asarray(forces32[k]).reshape(h, 6 * nc), un["gait"][k], caps)
+        st, _ = mm.stance_mask(un["gait"][k], caps, h, nc)
+        out.append({(i, c): cm.active_set(slack[i, c], ACT_TOL) for i in range(h) for c in range(nc) if st[i, c]})
+    return out
+
+
+def moved_limit(group, s, f_max):
+    """(kwargs of oracle.set_params / BatchedMPC.set_params, the moved f_max, dtheta) with dtheta taken between the binary32 values."""
+    f32 = lambda v: float(np.float32(v))
+    if group == "cap":
+        return {}, f32(f_max * (1.0 + s)), f32(f_max * (1.0 + s)) - f32(f_max)
+    base = dict(mu=MU, lt=LT, lh=LH)[group]
+    return {group: f32(base * (1.0 + s))}, f_max, f32(base * (1.0 + s)) - f32(base)
+
+
+def fd_limits_entry(oracle, entry, d):
+    """Per group the moved problem of an entry, qpOASES on both, the kept instances; shared by tests/test_limit_adjoint_mirror.py and
+    tests/test_gpu_limit_adjoint.py, left unchanged.  d: test_limit_adjoint_mirror.limit_case of the entry."""
+    name, case, f_max = entry
+    h, nc = case[2], case[4]
+    if name in _fdl:
+        return _fdl[name]
+    rec = d["rec"]
+    out = dict(u0=qp_forces64(oracle, rec, h, nc, f_max))
+    base_active = active_sets(oracle, rec, h, nc, d["u32"], f_max)
+    for group in groups_of(name, f_max):
+        s = FD_L_STEP
+        for _ in range(8):
+            kw, f1, dth = moved_limit(group, s, f_max)
+            try:
+                oracle.set_params(**kw)
+                u1 = qp_forces64(oracle, rec, h, nc, f1)
+                act2 = active_sets(oracle, rec, h, nc, u1.astype(np.float32), f1)
+            finally:
+                oracle.set_params()
+            keep = fm.same_active_sets(base_active, act2)
+            if (~keep).mean() <= fm.FD_LEFT_OUT_CAP:
+                break
+            s *= 0.5
+        out[group] = dict(kw=kw, f_max=f1, dtheta=dth, u1=u1, keep=keep, s=s)
+    _fdl[name] = out
+    return out
+
+
+def predicted_change(g, group, dtheta):
+    """Per instance grad_limits . dtheta for a move of one group (the two feet's caps move together)."""
+    gl = g["grad_limits"]
+    return (gl[:, 3] + gl[:, 4]) * dtheta if group == "cap" else gl[:, GROUPS.index(group)] * dtheta
