@@ -39,6 +39,7 @@ EXPORTS = [
     "hmpc_solve_adjoint", "hmpc_set_device_adjoint", "hmpc_get_device_adjoint", "hmpc_download_adjoint",
     "hmpc_adjoint_model", "hmpc_set_device_adjoint_model", "hmpc_get_device_adjoint_model", "hmpc_download_adjoint_model",
     "hmpc_adjoint_limits", "hmpc_set_device_adjoint_limits", "hmpc_get_device_adjoint_limits", "hmpc_download_adjoint_limits",
+    "hmpc_adjoint_record", "hmpc_set_device_adjoint_record", "hmpc_get_device_adjoint_record", "hmpc_download_adjoint_record",
 ]
 
 
@@ -242,6 +243,10 @@ def load():
     L.hmpc_set_device_adjoint_limits.argtypes = [vp] + [vp] * 6
     L.hmpc_get_device_adjoint_limits.argtypes = [vp] + [C.POINTER(vp)] * 6
     L.hmpc_download_adjoint_limits.argtypes = [vp] + [vp] * 6
+    L.hmpc_adjoint_record.argtypes = [vp, vp]
+    L.hmpc_set_device_adjoint_record.argtypes = [vp] + [vp] * 3
+    L.hmpc_get_device_adjoint_record.argtypes = [vp] + [C.POINTER(vp)] * 3
+    L.hmpc_download_adjoint_record.argtypes = [vp] + [vp] * 3
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

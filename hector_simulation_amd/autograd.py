@@ -7,6 +7,9 @@ the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h
                                                                            # more launch (hmpc_adjoint_model; csrc/hmpc_model_adjoint.hip)
     forces = differentiable_solve_limits(mpc, fields, traj, weights, alpha_k, mu=mu)  # mu [b], the instances' friction parameter: mu.grad
                                                                                       # as well (hmpc_adjoint_limits; csrc/hmpc_limit_adjoint.hip)
+    forces = differentiable_solve_fields(mpc, fields)  # any of p, v, q, w, r, joint_angles, weights, Alpha_K, traj (Rhand, f_max_hand) in
+                                                       # ``fields`` a tensor: its .grad, the orientation and the joint angles through the
+                                                       # assembly (hmpc_adjoint_record; csrc/hmpc_pose_adjoint.hip)
 
 The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
 constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
@@ -60,6 +63,59 @@ def _limit_buffers(mpc, device):
     if mpc.get_device_adjoint_limits() != {k: buf[k].data_ptr() for k in mpc.LIMIT_ADJOINT_KEYS}:
         mpc.set_device_adjoint_limits(*[buf[k].data_ptr() for k in mpc.LIMIT_ADJOINT_KEYS], keepalive=buf)
     return buf
+
+
+def _record_buffers(mpc, device):
+    """The same for the record gradients (``set_device_adjoint_record``)."""
+    buf = getattr(mpc, "_autograd_record_buffers", None)
+    if buf is None:
+        b, nc = mpc.max_batch, mpc.contacts
+        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
+        shapes = dict(grad_record=(b, nf + 12 * mpc.horizon), grad_frames=(b, 1 + nc, 3, 3), grad_rpy=(b, 3))
+        buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_record_buffers = buf
+    if mpc.get_device_adjoint_record() != {k: buf[k].data_ptr() for k in mpc.RECORD_ADJOINT_KEYS}:
+        mpc.set_device_adjoint_record(*[buf[k].data_ptr() for k in mpc.RECORD_ADJOINT_KEYS], keepalive=buf)
+    return buf
+
+
+FIELD_NAMES = ("p", "v", "q", "w", "r", "joint_angles", "weights", "Alpha_K", "traj", "Rhand", "f_max_hand")
+
+
+class _SolveFields(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mpc, fields, names, *tensors):
+        f = dict(fields)
+        for name, t in zip(names, tensors):
+            f[name] = t.detach().cpu().numpy()
+        device = torch.device("cuda", mpc.device)
+        mpc.upload(records.pack_records(f, mpc.horizon, mpc.contacts))
+        mpc.solve(torch.cuda.current_stream(device).cuda_stream)
+        forces, _ = mpc.download()  # (the safe pass: repaired forces, in the handle's force buffer as well)
+        ctx.mpc, ctx.generation, ctx.device, ctx.names = mpc, mpc.generation, device, names
+        ctx.meta = [(t.shape, t.dtype, t.device) for t in tensors]
+        return torch.from_numpy(np.ascontiguousarray(forces)).to(device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        mpc = ctx.mpc
+        if mpc.generation != ctx.generation:
+            raise RuntimeError("differentiable_solve_fields: the handle has solved another batch since this forward; its forces are gone")
+        b, nc, hz = mpc.batch, mpc.contacts, mpc.horizon
+        _buffers(mpc, ctx.device), _model_buffers(mpc, ctx.device), _limit_buffers(mpc, ctx.device)  # (before the adjoint, as in _Solve)
+        rbuf = _record_buffers(mpc, ctx.device)
+        seed = grad_output.detach().to(device=ctx.device, dtype=torch.float64).contiguous()
+        stream = torch.cuda.current_stream(ctx.device).cuda_stream
+        mpc.solve_adjoint(seed.data_ptr(), stream)
+        mpc.adjoint_model(stream)
+        mpc.adjoint_limits(seed.data_ptr(), stream)
+        mpc.adjoint_record(stream)
+        _, off, length = records._layout(nc)
+        grads = []
+        for name, (shape, dtype, dev), need in zip(ctx.names, ctx.meta, ctx.needs_input_grad[3:]):
+            n = 12 * hz if name == "traj" else length[name]
+            grads.append(rbuf["grad_record"][:b, off[name]:off[name] + n].to(device=dev, dtype=dtype, copy=True).reshape(shape) if need else None)
+        return (None, None, None) + tuple(grads)
 
 
 class _Solve(torch.autograd.Function):
@@ -138,3 +194,18 @@ def differentiable_solve_limits(mpc, fields, traj, weights, alpha_k, r=None, mu=
     if mu is None:
         return differentiable_solve(mpc, fields, traj, weights, alpha_k, r)
     return _Solve.apply(mpc, fields, traj, weights, alpha_k, r, mu)
+
+
+def differentiable_solve_fields(mpc, fields):
+    """Solves the batch ``fields`` (the dict ``records.pack_records`` takes), any of whose entries ``p, v, q, w, r, joint_angles, weights,
+    Alpha_K, traj`` (and ``Rhand, f_max_hand`` for three contacts) may be a torch tensor (any device, any float dtype, the shape
+    ``pack_records`` takes with a leading batch dimension); the rest are arrays.  Returns the forces as a CUDA float32 tensor [b, h * 6
+    contacts] that autograd differentiates in every tensor given: the backward enqueues adjoint -> model gradients -> limit gradients ->
+    record gradients on torch's current stream into torch-owned buffers and returns, for each tensor that needs it, a copy of its slice
+    of ``grad_record``.  The gradient in ``q`` is the total one -- through the Euler angles of the state, Acd, Bcd and the constraint
+    block -- of the quaternion as given (no normalisation is differentiated)."""
+    names = tuple(k for k in FIELD_NAMES if k in fields and isinstance(fields[k], torch.Tensor))
+    extra = [k for k, v in fields.items() if isinstance(v, torch.Tensor) and k not in names]
+    if extra:
+        raise ValueError(f"differentiable_solve_fields: no gradient is defined in {extra}")
+    return _SolveFields.apply(mpc, fields, names, *[fields[k] for k in names])

@@ -1246,6 +1246,84 @@ int hmpc_download_adjoint_limits(hmpc_handle *h, double *grad_limits, double *gr
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Record gradients: the gradient of the adjoint's loss in every float of the packed record, the quaternion and the joint angles through
+// stage A1 + A2 included (hmpc_pose_adjoint.hip).
+// ------------------------------------------------------------------------------------------------------------------
+// where the next record gradients go: the caller's buffers, else the handle's own (allocated here, for max_batch, on first need)
+static int record_adjoint_buffers(hmpc_handle *h, hmpc::PoseAdjointOut *b) {
+  const size_t mb = (size_t)h->max_batch, nc = (size_t)h->nc;
+  HIP_TRY(h->d_padj_record.ensure(mb * ((size_t)hmpc::rec_fixed_floats(h->nc) + 12 * (size_t)h->setup.horizon)));
+  HIP_TRY(h->d_padj_frames.ensure(mb * (1 + nc) * 9));
+  HIP_TRY(h->d_padj_rpy.ensure(mb * 3));
+  *b = {h->d_padj_record.get(), h->d_padj_frames.get(), h->d_padj_rpy.get()};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_adjoint_record(hmpc_handle *h, double *device_grad_record, double *device_grad_frames, double *device_grad_rpy) {
+  if (!h) return HMPC_E_ARG;
+  h->d_padj_record.set_caller(device_grad_record), h->d_padj_frames.set_caller(device_grad_frames), h->d_padj_rpy.set_caller(device_grad_rpy);
+  h->results.retarget_record_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint_record(hmpc_handle *h, double **device_grad_record, double **device_grad_frames, double **device_grad_rpy) {
+  if (!h) return HMPC_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::PoseAdjointOut b;
+  const int rc = record_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  if (device_grad_record) *device_grad_record = b.grad_record;
+  if (device_grad_frames) *device_grad_frames = b.grad_frames;
+  if (device_grad_rpy) *device_grad_rpy = b.grad_rpy;
+  return HMPC_OK;
+}
+
+int hmpc_adjoint_record(hmpc_handle *h, void *stream) {
+  // the three inputs: an adjoint of the last solve of the current batch, and model and limit gradients behind it; the chain goes through
+  // the handle's own assembly, which an external constraint block is not
+  if (!h || !h->results.can_record_adjoint() || h->d_ext_Fc) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hmpc::AdjointOut adj;
+  int rc = adjoint_buffers(h, &adj);  // (where the three went: moving them would have made them stale)
+  if (rc != HMPC_OK) return rc;
+  hmpc::ModelAdjointOut mo;
+  rc = model_adjoint_buffers(h, &mo);
+  if (rc != HMPC_OK) return rc;
+  hmpc::LimitAdjointOut lo;
+  rc = limit_adjoint_buffers(h, &lo);
+  if (rc != HMPC_OK) return rc;
+  hmpc::PoseAdjointOut b;
+  rc = record_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
+  const hmpc::PoseAdjointIn in = {adj.grad_x0, adj.grad_traj, adj.grad_weights, adj.grad_alpha, mo.grad_A, mo.grad_B, mo.grad_r, lo.grad_limits, lo.grad_Fc};
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_pose_adjoint(h->nc, a, in, b, (hipStream_t)stream));
+  h->results.on_record_adjoint();
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint_record(hmpc_handle *h, double *grad_record, double *grad_frames, double *grad_rpy) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_record_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint, model and limit gradients of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  hmpc::PoseAdjointOut b;
+  const int rc = record_adjoint_buffers(h, &b);
+  if (rc != HMPC_OK) return rc;
+  const size_t n = (size_t)h->batch, nc = (size_t)h->nc, d = sizeof(double);
+  const size_t nrec = (size_t)hmpc::rec_fixed_floats(h->nc) + 12 * (size_t)h->setup.horizon;
+  if (grad_record) HIP_TRY(hipMemcpy(grad_record, b.grad_record, n * nrec * d, hipMemcpyDeviceToHost));
+  if (grad_frames) HIP_TRY(hipMemcpy(grad_frames, b.grad_frames, n * (1 + nc) * 9 * d, hipMemcpyDeviceToHost));
+  if (grad_rpy) HIP_TRY(hipMemcpy(grad_rpy, b.grad_rpy, n * 3 * d, hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

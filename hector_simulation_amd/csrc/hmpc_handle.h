@@ -13,6 +13,7 @@
 #include "hmpc_adjoint.h"
 #include "hmpc_model_adjoint.h"
 #include "hmpc_limit_adjoint.h"
+#include "hmpc_pose_adjoint.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
 
@@ -137,6 +138,10 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // [max_batch][horizon][nc][10] and summary [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_limits) or the
   // handle's own, allocated by the first call that needs them
   OutputBuffer<double> d_ladj_limits, d_ladj_Fc, d_ladj_bound, d_ladj_lambda, d_ladj_nu, d_ladj_summary;
+  // record gradients (hmpc_adjoint_record): grad_record [max_batch][NF + 12 horizon], grad_frames [max_batch][1 + nc][9] and grad_rpy
+  // [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_record) or the handle's own, allocated by the first call
+  // that needs them
+  OutputBuffer<double> d_padj_record, d_padj_frames, d_padj_rpy;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

@@ -141,22 +141,23 @@ inline bool params_ok(const hmpc_params &p) {
 
 // ---------------------------------------------------------------------------------------------------- what is still valid
 // Which results on the device belong to the CURRENT batch and its LAST solve.  The graph: batch -> solve -> prediction -> selection,
-// solve -> margins, solve -> certificate, solve -> gains -> first-order wrench, solve -> adjoint -> model gradients, adjoint -> limit gradients; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the facts.
+// solve -> margins, solve -> certificate, solve -> gains -> first-order wrench, solve -> adjoint -> model gradients, adjoint -> limit gradients, (adjoint, model gradients, limit gradients) -> record gradients; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the facts.
 // (hmpc_resolve_failed repairs the solve in place and invalidates nothing; a bare launch that is no solve -- hmpc_debug_phase_cycles
 //  without device repair -- does not count as one.)
 class ResultState {
  public:
-  void on_batch() { solve_enqueued = predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = false; }          // the handle holds another batch
-  void on_solve() { solve_enqueued = true, predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = false; }    // every solve of a batch: its forces are newer than anything derived
+  void on_batch() { solve_enqueued = predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }          // the handle holds another batch
+  void on_solve() { solve_enqueued = true, predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }    // every solve of a batch: its forces are newer than anything derived
   void on_predict() { predict_enqueued = true, select_enqueued = false; }                      // (a selection made before this prediction read an older one)
   void on_select(int groups) { select_enqueued = true, select_groups = groups; }
   void on_margins() { margins_enqueued = true; }
   void on_certificate() { certificate_enqueued = true; }
   void on_gains() { gains_enqueued = true, first_order_enqueued = false; }  // (a wrench made before these gains read older ones)
   void on_first_order() { first_order_enqueued = true; }
-  void on_adjoint() { adjoint_enqueued = true, model_adjoint_enqueued = limit_adjoint_enqueued = false; }  // (independent of the gains and the wrench; model and limit gradients made before this adjoint read an older dir)
-  void on_model_adjoint() { model_adjoint_enqueued = true; }
-  void on_limit_adjoint() { limit_adjoint_enqueued = true; }  // (independent of the model gradients)
+  void on_adjoint() { adjoint_enqueued = true, model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }  // (independent of the gains and the wrench; model and limit gradients made before this adjoint read an older dir)
+  void on_model_adjoint() { model_adjoint_enqueued = true, record_adjoint_enqueued = false; }  // (record gradients made before these read older ones)
+  void on_limit_adjoint() { limit_adjoint_enqueued = true, record_adjoint_enqueued = false; }  // (independent of the model gradients)
+  void on_record_adjoint() { record_adjoint_enqueued = true; }  // (the C entry point asks can_record_adjoint first)
   // the caller moved a result's buffers: whatever was computed went elsewhere
   void retarget_prediction() { predict_enqueued = select_enqueued = false; }
   void retarget_selection() { select_enqueued = false; }
@@ -164,9 +165,10 @@ class ResultState {
   void retarget_certificate() { certificate_enqueued = false; }
   void retarget_gains() { gains_enqueued = first_order_enqueued = false; }
   void retarget_first_order() { first_order_enqueued = false; }
-  void retarget_adjoint() { adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = false; }
-  void retarget_model_adjoint() { model_adjoint_enqueued = false; }
-  void retarget_limit_adjoint() { limit_adjoint_enqueued = false; }
+  void retarget_adjoint() { adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }
+  void retarget_model_adjoint() { model_adjoint_enqueued = record_adjoint_enqueued = false; }
+  void retarget_limit_adjoint() { limit_adjoint_enqueued = record_adjoint_enqueued = false; }
+  void retarget_record_adjoint() { record_adjoint_enqueued = false; }
 
   bool has_solve() const { return solve_enqueued; }            // a solve of the current batch has been enqueued
   bool has_prediction() const { return predict_enqueued; }     // ... and a prediction behind it
@@ -178,11 +180,14 @@ class ResultState {
   bool has_adjoint() const { return adjoint_enqueued; }          // an adjoint of the last solve of the current batch has been enqueued
   bool has_model_adjoint() const { return model_adjoint_enqueued; }  // ... and model gradients behind that adjoint
   bool has_limit_adjoint() const { return limit_adjoint_enqueued; }  // ... and limit gradients behind that adjoint
+  bool can_record_adjoint() const { return adjoint_enqueued && model_adjoint_enqueued && limit_adjoint_enqueued; }  // all three inputs of the record gradients stand
+  bool has_record_adjoint() const { return record_adjoint_enqueued; }  // ... and record gradients behind all three
   int selected_groups() const { return select_enqueued ? select_groups : 0; }  // groups of that selection
 
  private:
   bool solve_enqueued = false, predict_enqueued = false, select_enqueued = false, margins_enqueued = false, certificate_enqueued = false,
-       gains_enqueued = false, first_order_enqueued = false, adjoint_enqueued = false, model_adjoint_enqueued = false, limit_adjoint_enqueued = false;
+       gains_enqueued = false, first_order_enqueued = false, adjoint_enqueued = false, model_adjoint_enqueued = false, limit_adjoint_enqueued = false,
+       record_adjoint_enqueued = false;
   int select_groups = 0;
 };
 

@@ -548,6 +548,39 @@ class BatchedMPC:
                                                                                                   lambda_ptr, nu_ptr, summary_ptr)]),
                "hmpc_set_device_adjoint_limits")
 
+    RECORD_ADJOINT_KEYS = ("grad_record", "grad_frames", "grad_rpy")
+
+    def adjoint_record(self, stream: int = 0) -> None:
+        """One launch behind ``solve_adjoint``, ``adjoint_model`` and ``adjoint_limits`` on ``stream``: their outputs chained through the
+        assembly, the gradient of the same loss in every float of the packed record (include/hector_mpc.h hmpc_adjoint_record).  Raises
+        unless all three have been enqueued behind the last adjoint of the last solve of the current batch."""
+        _check(self.L.hmpc_adjoint_record(self.h, C.c_void_p(stream)), "hmpc_adjoint_record")
+
+    def download_adjoint_record(self) -> dict:
+        """grad_record float64[batch, fixed floats + 12 horizon] in the float order of the packed record (``records.OFF`` / ``OFF3``),
+        grad_frames float64[batch, 1 + contacts, 3, 3] (the body rotation, then every contact frame) and grad_rpy float64[batch, 3].
+        Waits; runs no safe pass."""
+        b, nc, hz = self.batch, self.contacts, self.horizon
+        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
+        out = dict(grad_record=np.zeros((b, nf + 12 * hz)), grad_frames=np.zeros((b, 1 + nc, 3, 3)), grad_rpy=np.zeros((b, 3)))
+        _check(self.L.hmpc_download_adjoint_record(self.h, *[out[k].ctypes.data for k in self.RECORD_ADJOINT_KEYS]),
+               "hmpc_download_adjoint_record")
+        return out
+
+    def get_device_adjoint_record(self) -> dict:
+        """Device pointers of where the next record gradients go, by the names of ``download_adjoint_record`` (the handle's own buffers
+        are allocated here if they were not yet)."""
+        ptrs = [C.c_void_p() for _ in self.RECORD_ADJOINT_KEYS]
+        _check(self.L.hmpc_get_device_adjoint_record(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_record")
+        return {k: int(p.value or 0) for k, p in zip(self.RECORD_ADJOINT_KEYS, ptrs)}
+
+    def set_device_adjoint_record(self, grad_record_ptr: int = 0, grad_frames_ptr: int = 0, grad_rpy_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later record gradients (shapes of ``download_adjoint_record`` with max_batch rows; 0 / None =
+        the handle's own)."""
+        self._keep_padj = keepalive
+        _check(self.L.hmpc_set_device_adjoint_record(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_record_ptr, grad_frames_ptr, grad_rpy_ptr)]),
+               "hmpc_set_device_adjoint_record")
+
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where
         the last solve handed instance i's working set over and nothing has consumed it yet, else -1."""

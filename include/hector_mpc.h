@@ -625,7 +625,8 @@ double hmpc_legacy_feedback_gain(int component, int state);
  *                                  sum dir . d(Hu + g)/d theta: hmpc_adjoint_model below returns it for r, the mass and the body inertia
  *                                  (gravity is grad_x0[12]) and hmpc_adjoint_limits further below for mu, lt, lh and the Fz caps, which
  *                                  enter through the constraint block; left to the caller are the orientation and the joint angles
- *                                  (through grad_A, grad_B, grad_x0 and grad_Fc of these calls).
+ *                                  (through grad_A, grad_B, grad_x0 and grad_Fc of these calls) by these three alone;
+ *                                  hmpc_adjoint_record, behind all three, chains them through the assembly.
  *        summary[batch][2]       [0] the smallest pivot ratio: hmpc_feedback_gains' summary[0], bit for bit; [1] max |dir| (a NaN
  *                                  entry counts as +inf).
  *   6. Meaning.  The outputs are the derivatives of L(u*(x0, X_d, w, Alpha_K)) with the linearisation (Acd, Bcd, Fc) and the active
@@ -774,6 +775,72 @@ int hmpc_get_device_adjoint_limits(hmpc_handle *h, double **device_grad_limits, 
                                    double **device_lambda, double **device_nu, double **device_summary);
 int hmpc_download_adjoint_limits(hmpc_handle *h, double *grad_limits, double *grad_Fc, double *grad_bound, double *lambda, double *nu,
                                  double *summary);
+/* ---- pose gradients of the solve: orientation, joint angles, the whole record ----
+ * Behind hmpc_solve_adjoint, hmpc_adjoint_model and hmpc_adjoint_limits: their outputs chained through stage A1 + A2 of the assembly, so
+ * that the gradient of the same loss comes back IN EVERY FLOAT OF THE PACKED RECORD: p, v, q, w, r, the joint angles, the weights,
+ * Alpha_K, the trajectory, and for three contacts the hand frame and the hand's cap.  grad_x0[0:3] of the adjoint is the gradient in the
+ * Euler angles with the linearisation frozen; the quaternion also moves Acd (through Rb^-1(yaw, pitch)), Bcd (through I_w^-1 = (R I_b
+ * R')^-1) and Fc (through the rows R Rf_c), and grad_record's q slice is the total.  Per instance, NC contacts, U = 6 NC; the buffers of
+ * the three calls enter as they stand.  Everything below is binary64; every sum is one ascending chain of explicit fused multiply-adds
+ * started at +0; trip counts are fixed by NC.  What is differentiated is the assembly's formula, not its binary32 rounding; the
+ * assembly's own tabulated binary32 values enter widened: (s_k, c_k) the sine and cosine of joint angle k as the assembly holds them,
+ * (s_b, c_b) those of a2 + a3 + a4 of a leg, (cy, sy, cp, sp) of yaw and pitch, R the rotation it forms from the record's quaternion,
+ * Ab = Acd[0:3][6:9], Mb = Bcd[6:9][3 NC .. 3 NC + 2].  G_F = grad_Fc, cf = 3c, cmo = 3 NC + 3c, sigma_c = +1 for c = 1 and -1 otherwise (the
+ * sign of the heel row's moment part), lt, lh, dt, I_b the handle's values widened.
+ *   1. Foot frames.  For a foot c < 2 with joints 0 = 5c .. 4 = 5c + 4, t = s0 s1, v = c0 s1:
+ *        Rf_c = { fma(c0, cb, 0 - t sb), 0 - s0 c1, fma(c0, sb, t cb);  fma(s0, cb, v sb), c0 c1, fma(s0, sb, 0 - v cb);  0 - c1 sb, s1, c1 cb }
+ *      which is Rz(a0) Rx(a1) Ry(a2 + a3 + a4), what the assembly's expanded products equal.  Rf_2 is the record's Rhand, widened.
+ *   2. Constraint block -> frames.  Gg_c[j][0] = G_F[8c+4][cmo+j];  Gg_c[j][1] = G_F[8c+5][cmo+j] + sigma_c G_F[8c+6][cmo+j];
+ *        Gg_c[j][2] = fma(0 - lt, G_F[8c+5][cf+j], (0 - lh) G_F[8c+6][cf+j])                                    (j < 3)
+ *        G_Rf[c][a][m] = sum_{j<3} R[j][a] Gg_c[j][m];      P_c[i][j] = sum_{m<3} Gg_c[i][m] Rf_c[j][m]
+ *   3. Joint angles (c < 2), e = (c1 sb, 0 - s1, 0 - c1 cb), f = (s1 sb, c1, 0 - s1 cb):
+ *        grad_ja[5c]       = sum_{k<3} G_Rf[c][0][k] (0 - Rf_c[1][k]) ; sum_{k<3} G_Rf[c][1][k] Rf_c[0][k]
+ *        grad_ja[5c+1]     = sum_k G_Rf[c][0][k] ((0 - s0) e[k]) ; sum_k G_Rf[c][1][k] (c0 e[k]) ; sum_k G_Rf[c][2][k] f[k]
+ *        grad_ja[5c+2..4]  = sum_{i<3} ( G_Rf[c][i][0] (0 - Rf_c[i][2]) ; G_Rf[c][i][2] Rf_c[i][0] )      one number, three times: the offsets
+ *                            and the fmod of the assembly have derivative 1
+ *   4. Inertia -> body rotation.  Gam as item 4 of hmpc_adjoint_model;  X[m][n] = sum_{a<3} Mb[a][m] Gam[a][n];  Y[m][k] = sum_{n<3}
+ *        X[m][n] Mb[k][n];  G_Iw = 0 - Y / dt;  P_NC[i][k] = (sum_{j<3} (G_Iw[i][j] + G_Iw[j][i]) R[j][k]) I_b[k]
+ *        G_R[i][j] = +0 + P_0[i][j] + .. + P_NC[i][j]
+ *   5. Euler-rate map.  X'[m][n] = sum_a Ab[a][m] grad_A[a][6+n];  Y'[m][k] = sum_n X'[m][n] Ab[k][n];  G_Rb = 0 - Y' / dt;  with Rb =
+ *        {cy cp, -sy, 0; sy cp, cy, 0; -sp, 0, 1} (roll does not enter):
+ *        G_yaw   = G_Rb[0][0] (0 - sy cp) ; G_Rb[0][1] (0 - cy) ; G_Rb[1][0] (cy cp) ; G_Rb[1][1] (0 - sy)
+ *        G_pitch = G_Rb[0][0] (0 - cy sp) ; G_Rb[1][0] (0 - sy sp) ; G_Rb[2][0] (0 - cp)
+ *        grad_rpy = (grad_x0[0], grad_x0[1] + G_pitch, grad_x0[2] + G_yaw)
+ *   6. Euler angles -> quaternion (qw, qx, qy, qz as the record holds them, un-normalised or not; t* = q* + q*).  The assembly's own
+ *      binary32 numerators and denominators, widened: n0 = 2 (qw qx + qy qz), d0 = 1 - 2 (qx qx + qy qy), t = qw qy - qx qz, n2 = 2 (qw qz +
+ *      qx qy), d2 = 1 - 2 (qy qy + qz qz) (d0, d2: the binary32 product subtracted in binary64, as the assembly does).
+ *        J[0][k] = fma(d0, dn0[k], 0 - n0 dd0[k]) / fma(n0, n0, d0 d0),   dn0 = (tx, tw, tz, ty),  dd0 = (0, 0 - 2 tx, 0 - 2 ty, 0)
+ *        J[1][k] = exactly 0 where the assembly's clamp !(2 t < 0.99999) holds, else das[k] / sqrt(fma(0 - 2 t, 2 t, 1)),  das = (ty, 0 - tz, tw, 0 - tx)
+ *        J[2][k] = as J[0] over n2, d2,   dn2 = (tz, ty, tx, tw),  dd2 = (0, 0, 0 - 2 ty, 0 - 2 tz)
+ *        E[k] = J[0][k] grad_rpy[0] ; J[1][k] grad_rpy[1] ; J[2][k] grad_rpy[2]
+ *   7. Body rotation -> quaternion.  grad_q[k] = (sum over (i, j) row-major of G_R[i][j] dR[i][j]/dq_k) + E[k], dR/dq that of the polynomial
+ *      R = {1 - ty qy - tz qz, tx qy - tz qw, ...}, zero entries included; no normalisation is differentiated.
+ *   8. Outputs.  grad_record[batch][NF + 12 h] in the float order of the packed record (NF = 54 for two contacts, 73 for three): p, w, v <-
+ *      grad_x0[3:6], [6:9], [9:12];  q <- grad_q;  r <- grad_r;  joint angles <- grad_ja;  yaw <- +0 (the solve never reads it);  weights <-
+ *      grad_weights;  Alpha_K <- grad_alpha;  Rhand <- G_Rf[2];  f_max_hand <- grad_limits[3 + 2];  trajectory <- grad_traj.
+ *      grad_frames[batch][1 + NC][9] = G_R, then G_Rf[c] per contact, row-major: for callers with their own leg kinematics.
+ *      grad_rpy[batch][3] as item 5: the total gradient in the Euler angles.
+ *   9. Meaning.  The frozen-set derivatives, as for the three calls behind it.  A contact that is swing at every step contributes exact
+ *      zeros; a zero seed upstream gives zeros everywhere; no loop iterates on data, so NaN input ends like any other.  The gradients in
+ *      the gait bytes and in f_max of the feet are not part of it (the latter is grad_limits' cap_0 + cap_1).  The result is a pure
+ *      function of (record, hmpc_params, per-instance mu, the nine upstream buffers).
+ *
+ * hmpc_adjoint_record enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It reads
+ * grad_x0, grad_traj, grad_weights, grad_alpha, grad_A, grad_B, grad_r, grad_limits and grad_Fc where the three calls last wrote them.
+ * HMPC_E_ARG, nothing enqueued: hmpc_solve_adjoint, hmpc_adjoint_model and hmpc_adjoint_limits have not all three been enqueued behind
+ * the last adjoint of the last solve of the current batch, or the handle is inside a solve on an external constraint block.
+ * hmpc_set_device_adjoint_record: caller-owned device buffers for later calls (any may be NULL = the handle's own, allocated for max_batch
+ * by the first call that needs them; never inside hmpc_solve).  Moving the buffers makes record gradients already computed stale, as
+ * does whatever makes one of the three inputs stale or new: every solve, every new batch, every hmpc_solve_adjoint, hmpc_adjoint_model
+ * and hmpc_adjoint_limits, and the three hmpc_set_device_adjoint* calls of theirs.
+ * hmpc_get_device_adjoint_record: where the next record gradients go; any pointer may be NULL.  hmpc_download_adjoint_record waits for
+ * the stream of the last call, then copies (any pointer may be NULL); HMPC_E_ARG when nothing has been computed since.  It does NOT run
+ * the safe pass.  With no batch set (batch = 0) it copies nothing and returns HMPC_OK.
+ * Device groups: per member, through hmpc_group_member.  There is no accessor on the process-global solver. */
+int hmpc_adjoint_record(hmpc_handle *h, void *stream);
+int hmpc_set_device_adjoint_record(hmpc_handle *h, double *device_grad_record, double *device_grad_frames, double *device_grad_rpy);
+int hmpc_get_device_adjoint_record(hmpc_handle *h, double **device_grad_record, double **device_grad_frames, double **device_grad_rpy);
+int hmpc_download_adjoint_record(hmpc_handle *h, double *grad_record, double *grad_frames, double *grad_rpy);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size
