@@ -37,6 +37,8 @@ EXPORTS = [
     "hmpc_feedback_gains", "hmpc_set_device_gains", "hmpc_get_device_gains", "hmpc_download_gains", "hmpc_first_order_wrench",
     "hmpc_set_device_first_order", "hmpc_download_first_order", "hmpc_legacy_feedback_gain",
     "hmpc_solve_adjoint", "hmpc_set_device_adjoint", "hmpc_get_device_adjoint", "hmpc_download_adjoint",
+    "hmpc_solve_adjoint_multi", "hmpc_set_device_adjoint_multi", "hmpc_get_device_adjoint_multi", "hmpc_download_adjoint_multi",
+    "hmpc_select_adjoint_seed",
     "hmpc_adjoint_model", "hmpc_set_device_adjoint_model", "hmpc_get_device_adjoint_model", "hmpc_download_adjoint_model",
     "hmpc_adjoint_limits", "hmpc_set_device_adjoint_limits", "hmpc_get_device_adjoint_limits", "hmpc_download_adjoint_limits",
     "hmpc_adjoint_record", "hmpc_set_device_adjoint_record", "hmpc_get_device_adjoint_record", "hmpc_download_adjoint_record",
@@ -235,6 +237,11 @@ def load():
     L.hmpc_set_device_adjoint.argtypes = [vp] + [vp] * 6
     L.hmpc_get_device_adjoint.argtypes = [vp] + [C.POINTER(vp)] * 6
     L.hmpc_download_adjoint.argtypes = [vp] + [vp] * 6
+    L.hmpc_solve_adjoint_multi.argtypes = [vp, vp, ci, vp]
+    L.hmpc_set_device_adjoint_multi.argtypes = [vp, ci] + [vp] * 6
+    L.hmpc_get_device_adjoint_multi.argtypes = [vp, C.POINTER(ci)] + [C.POINTER(vp)] * 6
+    L.hmpc_download_adjoint_multi.argtypes = [vp] + [vp] * 6
+    L.hmpc_select_adjoint_seed.argtypes = [vp, ci]
     L.hmpc_adjoint_model.argtypes = [vp, vp]
     L.hmpc_set_device_adjoint_model.argtypes = [vp] + [vp] * 5
     L.hmpc_get_device_adjoint_model.argtypes = [vp] + [C.POINTER(vp)] * 5

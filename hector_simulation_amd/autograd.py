@@ -11,6 +11,10 @@ the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h
                                                        # ``fields`` a tensor: its .grad, the orientation and the joint angles through the
                                                        # assembly (hmpc_adjoint_record; csrc/hmpc_pose_adjoint.hip)
 
+    jac, grad_params, grad_limits = wrench_jacobian(mpc, step=0)  # behind a solve: d u_step / d record [b, U, record floats], from ONE
+                                                                  # multi-seed adjoint launch (hmpc_solve_adjoint_multi;
+                                                                  # csrc/hmpc_adjoint_multi.hip) and U downstream chains
+
 The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
 constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
 stay available through ``mpc.download_adjoint()``.  A backward is refused when the ``BatchedMPC`` object has uploaded, solved or been given
@@ -77,6 +81,56 @@ def _record_buffers(mpc, device):
     if mpc.get_device_adjoint_record() != {k: buf[k].data_ptr() for k in mpc.RECORD_ADJOINT_KEYS}:
         mpc.set_device_adjoint_record(*[buf[k].data_ptr() for k in mpc.RECORD_ADJOINT_KEYS], keepalive=buf)
     return buf
+
+
+def _multi_buffers(mpc, device, n_seeds):
+    """The same for the multi-seed adjoint (``set_device_adjoint_multi``), with room for ``n_seeds`` slices of max_batch rows."""
+    buf = getattr(mpc, "_autograd_multi_buffers", None)
+    if buf is None or buf["summary"].shape[0] < n_seeds:
+        b, hz, u = mpc.max_batch, mpc.horizon, 6 * mpc.contacts
+        shapes = dict(grad_x0=(b, 13), grad_traj=(b, hz, 12), grad_weights=(b, 12), grad_alpha=(b, u), dir=(b, hz, u), summary=(b, 2))
+        buf = {k: torch.zeros((n_seeds,) + s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_multi_buffers = buf
+    now = mpc.get_device_adjoint_multi()
+    if {k: now[k] for k in mpc.ADJOINT_KEYS} != {k: buf[k].data_ptr() for k in mpc.ADJOINT_KEYS}:
+        mpc.set_device_adjoint_multi(buf["summary"].shape[0], *[buf[k].data_ptr() for k in mpc.ADJOINT_KEYS], keepalive=buf)
+    return buf
+
+
+def wrench_jacobian(mpc, step=0, generation=None):
+    """Behind a solve of ``mpc``: the Jacobian of the wrench of horizon step ``step`` in every float of the packed record, with the
+    linearisation and the active set frozen.  The unit seeds e_c at ``step`` go on the device, ONE multi-seed launch
+    (hmpc_solve_adjoint_multi) runs the matrix backward pass once for all 6 contacts of them, and for every row c the chain select ->
+    model gradients -> limit gradients -> record gradients follows on torch's current stream into torch-owned buffers.  Returns
+    ``(jac, grad_params, grad_limits)``: float64 CUDA tensors [batch, U, NF + 12 h] (``d u_step[c] / d record``: row c is what
+    ``differentiable_solve_fields`` returns under grad_output = e_c, bit for bit), [batch, U, 4] and [batch, U, 3 + contacts].  With
+    ``generation`` (``mpc.generation`` as it stood behind the solve) the call is refused when the object has uploaded, solved or been
+    given other records or outputs since, as a backward of ``differentiable_solve`` is."""
+    if generation is not None and mpc.generation != generation:
+        raise RuntimeError("wrench_jacobian: the handle has solved another batch since; its forces are gone")
+    b, nc, hz = mpc.batch, mpc.contacts, mpc.horizon
+    u = 6 * nc
+    if not 0 <= step < hz:
+        raise ValueError(f"wrench_jacobian: step {step} outside the horizon")
+    device = torch.device("cuda", mpc.device)
+    _multi_buffers(mpc, device, u)
+    mbuf, lbuf, rbuf = _model_buffers(mpc, device), _limit_buffers(mpc, device), _record_buffers(mpc, device)
+    seeds = torch.zeros((u, b, hz, u), dtype=torch.float64, device=device)
+    seeds[torch.arange(u), :, step, torch.arange(u)] = 1.0
+    stream = torch.cuda.current_stream(device).cuda_stream
+    mpc.solve_adjoint_multi(seeds.data_ptr(), u, stream)
+    jac = torch.empty((b, u, rbuf["grad_record"].shape[1]), dtype=torch.float64, device=device)
+    grad_params = torch.empty((b, u, 4), dtype=torch.float64, device=device)
+    grad_limits = torch.empty((b, u, 3 + nc), dtype=torch.float64, device=device)
+    for c in range(u):
+        mpc.select_adjoint_seed(c)
+        mpc.adjoint_model(stream)
+        mpc.adjoint_limits(seeds[c].data_ptr(), stream)
+        mpc.adjoint_record(stream)
+        jac[:, c] = rbuf["grad_record"][:b]
+        grad_params[:, c] = mbuf["grad_params"][:b]
+        grad_limits[:, c] = lbuf["grad_limits"][:b]
+    return jac, grad_params, grad_limits
 
 
 FIELD_NAMES = ("p", "v", "q", "w", "r", "joint_angles", "weights", "Alpha_K", "traj", "Rhand", "f_max_hand")

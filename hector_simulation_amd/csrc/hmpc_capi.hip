@@ -1067,6 +1067,111 @@ int hmpc_solve_adjoint(hmpc_handle *h, const double *device_seed, void *stream) 
   return HMPC_OK;
 }
 
+// doubles per instance of the six arrays of an adjoint, in the order of AdjointOut
+static void adjoint_row_sizes(const hmpc_handle *h, size_t n[6]) {
+  const size_t u = 6 * (size_t)h->nc, hz = (size_t)h->setup.horizon;
+  n[0] = 13, n[1] = hz * 12, n[2] = 12, n[3] = u, n[4] = hz * u, n[5] = hmpc::ADJ_SUMMARY;
+}
+
+// slice 0 of where the multi-seed adjoint is or goes next: per array the caller's buffer, else the handle's own (NULL before the first
+// launch reserved it)
+static hmpc::AdjointOut adjoint_multi_base(const hmpc_handle *h) {
+  double *p[6];
+  for (int k = 0; k < 6; ++k) p[k] = h->adjm_caller[k] ? h->adjm_caller[k] : h->d_adjm_own[k].get();
+  return {p[0], p[1], p[2], p[3], p[4], p[5]};
+}
+
+// where the CURRENT adjoint is -- the parent of the model, limit and record gradients and what hmpc_download_adjoint returns: the buffers
+// of hmpc_solve_adjoint, or the slice of the multi-seed adjoint that hmpc_select_adjoint_seed chose (pointer arithmetic alone)
+static int current_adjoint(hmpc_handle *h, hmpc::AdjointOut *b) {
+  const int s = h->results.selected_adjoint_seed();
+  if (s < 0) return adjoint_buffers(h, b);
+  size_t n[6];
+  adjoint_row_sizes(h, n);
+  const hmpc::AdjointOut m = adjoint_multi_base(h);
+  const size_t at = (size_t)s * (size_t)h->batch;
+  *b = {m.grad_x0 + at * n[0], m.grad_traj + at * n[1], m.grad_weights + at * n[2], m.grad_alpha + at * n[3], m.dir + at * n[4], m.summary + at * n[5]};
+  return HMPC_OK;
+}
+
+int hmpc_set_device_adjoint_multi(hmpc_handle *h, int n_seeds, double *device_grad_x0, double *device_grad_traj, double *device_grad_weights,
+                                  double *device_grad_alpha, double *device_dir, double *device_summary) {
+  if (!h) return HMPC_E_ARG;
+  double *p[6] = {device_grad_x0, device_grad_traj, device_grad_weights, device_grad_alpha, device_dir, device_summary};
+  bool any = false;
+  for (int k = 0; k < 6; ++k) any = any || p[k];
+  if (any && (n_seeds < 1 || n_seeds > HMPC_ADJOINT_MAX_SEEDS)) return HMPC_E_ARG;
+  for (int k = 0; k < 6; ++k) h->adjm_caller[k] = p[k];
+  h->adjm_caller_seeds = any ? n_seeds : 0;
+  h->results.retarget_adjoint_multi();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint_multi(hmpc_handle *h, int *n_seeds, double **device_grad_x0, double **device_grad_traj, double **device_grad_weights,
+                                  double **device_grad_alpha, double **device_dir, double **device_summary) {
+  if (!h) return HMPC_E_ARG;
+  const hmpc::AdjointOut b = adjoint_multi_base(h);
+  if (n_seeds) *n_seeds = h->results.adjoint_multi_seeds_enqueued();
+  if (device_grad_x0) *device_grad_x0 = b.grad_x0;
+  if (device_grad_traj) *device_grad_traj = b.grad_traj;
+  if (device_grad_weights) *device_grad_weights = b.grad_weights;
+  if (device_grad_alpha) *device_grad_alpha = b.grad_alpha;
+  if (device_dir) *device_dir = b.dir;
+  if (device_summary) *device_summary = b.summary;
+  return HMPC_OK;
+}
+
+int hmpc_solve_adjoint_multi(hmpc_handle *h, const double *device_seeds, int n_seeds, void *stream) {
+  if (!h || !device_seeds || n_seeds < 1 || n_seeds > HMPC_ADJOINT_MAX_SEEDS || !h->results.has_solve() || h->d_ext_Fc) return HMPC_E_ARG;
+  bool caller = false, own = false;
+  for (int k = 0; k < 6; ++k) (h->adjm_caller[k] ? caller : own) = true;
+  if (caller && n_seeds > h->adjm_caller_seeds) return HMPC_E_ARG;  // the caller's buffers hold fewer slices
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (own) {  // the handle's own: room for (n_seeds, max_batch); an older, smaller allocation may still be read on any stream
+    size_t n[6];
+    adjoint_row_sizes(h, n);
+    const bool grows = n_seeds > h->adjm_own_seeds;
+    if (grows) h->results.retarget_adjoint_multi();  // (what the old buffers hold goes with them)
+    for (int k = 0; k < 6; ++k)
+      if (!h->adjm_caller[k]) HIP_TRY(h->d_adjm_own[k].reserve((size_t)n_seeds * (size_t)h->max_batch * n[k] * sizeof(double), (hipStream_t)stream, true));
+    if (grows) h->adjm_own_seeds = n_seeds;
+  }
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (as hmpc_solve_adjoint)
+  set_problem_args(h, a);
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_adjoint_multi(h->nc, a, h->cert_act_tol, device_seeds, n_seeds, adjoint_multi_base(h), (hipStream_t)stream));
+  h->results.on_adjoint_multi(n_seeds);
+  return HMPC_OK;
+}
+
+int hmpc_select_adjoint_seed(hmpc_handle *h, int s) {
+  if (!h || !h->results.has_adjoint_multi() || s < 0 || s >= h->results.adjoint_multi_seeds_enqueued()) return HMPC_E_ARG;
+  h->results.on_select_adjoint(s);
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint_multi(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
+                                double *summary) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_adjoint_multi()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  const hmpc::AdjointOut b = adjoint_multi_base(h);
+  size_t n[6];
+  adjoint_row_sizes(h, n);
+  const size_t rows = (size_t)h->results.adjoint_multi_seeds_enqueued() * (size_t)h->batch, d = sizeof(double);
+  if (grad_x0) HIP_TRY(hipMemcpy(grad_x0, b.grad_x0, rows * n[0] * d, hipMemcpyDeviceToHost));
+  if (grad_traj) HIP_TRY(hipMemcpy(grad_traj, b.grad_traj, rows * n[1] * d, hipMemcpyDeviceToHost));
+  if (grad_weights) HIP_TRY(hipMemcpy(grad_weights, b.grad_weights, rows * n[2] * d, hipMemcpyDeviceToHost));
+  if (grad_alpha) HIP_TRY(hipMemcpy(grad_alpha, b.grad_alpha, rows * n[3] * d, hipMemcpyDeviceToHost));
+  if (dir) HIP_TRY(hipMemcpy(dir, b.dir, rows * n[4] * d, hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, b.summary, rows * n[5] * d, hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
 int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
                           double *summary) {
   if (!h) return HMPC_E_ARG;
@@ -1075,7 +1180,7 @@ int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, do
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
   hmpc::AdjointOut b;
-  const int rc = adjoint_buffers(h, &b);
+  const int rc = current_adjoint(h, &b);
   if (rc != HMPC_OK) return rc;
   const size_t n = (size_t)h->batch, u = 6 * (size_t)h->nc, hz = (size_t)h->setup.horizon, d = sizeof(double);
   if (grad_x0) HIP_TRY(hipMemcpy(grad_x0, b.grad_x0, n * 13 * d, hipMemcpyDeviceToHost));
@@ -1132,7 +1237,7 @@ int hmpc_adjoint_model(hmpc_handle *h, void *stream) {
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   hmpc::AdjointOut adj;
-  int rc = adjoint_buffers(h, &adj);  // (where that adjoint went: moving them would have made it stale)
+  int rc = current_adjoint(h, &adj);  // (where that adjoint went -- a single launch or a selected slice: moving them would have made it stale)
   if (rc != HMPC_OK) return rc;
   hmpc::ModelAdjointOut b;
   rc = model_adjoint_buffers(h, &b);
@@ -1211,7 +1316,7 @@ int hmpc_adjoint_limits(hmpc_handle *h, const double *device_seed, void *stream)
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   hmpc::AdjointOut adj;
-  int rc = adjoint_buffers(h, &adj);  // (where that adjoint went: moving them would have made it stale)
+  int rc = current_adjoint(h, &adj);  // (where that adjoint went -- a single launch or a selected slice: moving them would have made it stale)
   if (rc != HMPC_OK) return rc;
   hmpc::LimitAdjointOut b;
   rc = limit_adjoint_buffers(h, &b);
@@ -1285,7 +1390,7 @@ int hmpc_adjoint_record(hmpc_handle *h, void *stream) {
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   hmpc::AdjointOut adj;
-  int rc = adjoint_buffers(h, &adj);  // (where the three went: moving them would have made them stale)
+  int rc = current_adjoint(h, &adj);  // (where the three went: moving them would have made them stale)
   if (rc != HMPC_OK) return rc;
   hmpc::ModelAdjointOut mo;
   rc = model_adjoint_buffers(h, &mo);

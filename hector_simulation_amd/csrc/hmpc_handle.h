@@ -11,6 +11,7 @@
 #include "hmpc_certificate.h"
 #include "hmpc_feedback.h"
 #include "hmpc_adjoint.h"
+#include "hmpc_adjoint_multi.h"
 #include "hmpc_model_adjoint.h"
 #include "hmpc_limit_adjoint.h"
 #include "hmpc_pose_adjoint.h"
@@ -130,6 +131,13 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // [max_batch][6 nc], dir [max_batch][horizon][6 nc] and summary [max_batch][2] binary64; to the caller's buffers
   // (hmpc_set_device_adjoint) or the handle's own, allocated by the first call that needs them
   OutputBuffer<double> d_adj_x0, d_adj_traj, d_adj_weights, d_adj_alpha, d_adj_dir, d_adj_summary;
+  // multi-seed adjoint (hmpc_solve_adjoint_multi): the six arrays of the adjoint once per seed, seed-major over the CURRENT batch
+  // ([n_seeds][batch][...]), in the order grad_x0, grad_traj, grad_weights, grad_alpha, dir, summary; to the caller's buffers
+  // (hmpc_set_device_adjoint_multi, room for adjm_caller_seeds slices) or the handle's own, reserved for (n_seeds, max_batch) by the
+  // launch that needs them (adjm_own_seeds = what they hold room for)
+  DeviceBuffer<double> d_adjm_own[6];
+  double *adjm_caller[6] = {};
+  int adjm_caller_seeds = 0, adjm_own_seeds = 0;
   // model gradients (hmpc_adjoint_model): grad_A [max_batch][13][13], grad_B [max_batch][13][6 nc], grad_r [max_batch][3][nc], grad_params
   // [max_batch][4] and costate [max_batch][2][13] binary64; to the caller's buffers (hmpc_set_device_adjoint_model) or the handle's own,
   // allocated by the first call that needs them

@@ -476,6 +476,46 @@ class BatchedMPC:
                                                                                            grad_alpha_ptr, dir_ptr, summary_ptr)]),
                "hmpc_set_device_adjoint")
 
+    def solve_adjoint_multi(self, seeds_ptr: int, n_seeds: int, stream: int = 0) -> None:
+        """``solve_adjoint`` under ``n_seeds`` seeds (float64[n_seeds, batch, horizon, 6 contacts] in HBM) behind ONE matrix backward pass:
+        one launch per 6 contacts seeds on ``stream`` (include/hector_mpc.h hmpc_solve_adjoint_multi).  Slice s of every output is bit for
+        bit what ``solve_adjoint`` returns under seed s.  Raises for null seeds, a seed count outside 1 .. 240 and when no solve of the
+        current batch has been enqueued."""
+        _check(self.L.hmpc_solve_adjoint_multi(self.h, C.c_void_p(int(seeds_ptr or 0)), int(n_seeds), C.c_void_p(stream)),
+               "hmpc_solve_adjoint_multi")
+
+    def download_adjoint_multi(self) -> dict:
+        """The arrays of ``download_adjoint`` with a leading axis over the seeds of the last ``solve_adjoint_multi``.  Waits; runs no safe
+        pass."""
+        n = C.c_int(0)
+        _check(self.L.hmpc_get_device_adjoint_multi(self.h, C.byref(n), *[None] * 6), "hmpc_get_device_adjoint_multi")
+        s, b, hz, u = n.value, self.batch, self.horizon, 6 * self.contacts
+        out = dict(grad_x0=np.zeros((s, b, 13)), grad_traj=np.zeros((s, b, hz, 12)), grad_weights=np.zeros((s, b, 12)),
+                   grad_alpha=np.zeros((s, b, u)), dir=np.zeros((s, b, hz, u)), summary=np.zeros((s, b, 2)))
+        _check(self.L.hmpc_download_adjoint_multi(self.h, *[out[k].ctypes.data for k in self.ADJOINT_KEYS]), "hmpc_download_adjoint_multi")
+        return out
+
+    def get_device_adjoint_multi(self) -> dict:
+        """Device pointers of slice 0 of where the multi-seed adjoint is or goes next, by the names of ``download_adjoint`` (0: one of the
+        handle's own that no launch has reserved yet), and ``n_seeds``: the seeds of the one that stands (0: none)."""
+        n, ptrs = C.c_int(0), [C.c_void_p() for _ in self.ADJOINT_KEYS]
+        _check(self.L.hmpc_get_device_adjoint_multi(self.h, C.byref(n), *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_multi")
+        return dict({k: int(p.value or 0) for k, p in zip(self.ADJOINT_KEYS, ptrs)}, n_seeds=n.value)
+
+    def set_device_adjoint_multi(self, n_seeds: int = 0, grad_x0_ptr: int = 0, grad_traj_ptr: int = 0, grad_weights_ptr: int = 0,
+                                 grad_alpha_ptr: int = 0, dir_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
+        """Caller-owned device buffers for later multi-seed adjoints, with room for ``n_seeds`` slices of the current batch (0 / None = the
+        handle's own)."""
+        self._keep_adj_multi = keepalive
+        _check(self.L.hmpc_set_device_adjoint_multi(self.h, int(n_seeds), *[C.c_void_p(int(p or 0)) for p in (
+            grad_x0_ptr, grad_traj_ptr, grad_weights_ptr, grad_alpha_ptr, dir_ptr, summary_ptr)]), "hmpc_set_device_adjoint_multi")
+
+    def select_adjoint_seed(self, s: int) -> None:
+        """Makes slice ``s`` of the last ``solve_adjoint_multi`` the current adjoint: ``adjoint_model``, ``adjoint_limits`` (hand it the
+        seed's own slice), ``adjoint_record`` and ``download_adjoint`` then behave as after ``solve_adjoint`` under that seed.  No launch, no
+        copy.  Raises when ``s`` is out of range or no multi-seed adjoint of the last solve of the current batch stands."""
+        _check(self.L.hmpc_select_adjoint_seed(self.h, int(s)), "hmpc_select_adjoint_seed")
+
     MODEL_ADJOINT_KEYS = ("grad_A", "grad_B", "grad_r", "grad_params", "costate")
 
     def adjoint_model(self, stream: int = 0) -> None:

@@ -638,7 +638,7 @@ double hmpc_legacy_feedback_gain(int component, int state);
  *
  * hmpc_solve_adjoint enqueues ONE launch on `stream` (a kernel of its own, 128 threads per instance) and synchronises nothing.  It
  * reads the forces where the solve wrote them and needs no gains.  HMPC_E_ARG, nothing enqueued: a NULL seed, or no solve of the
- * current batch has been enqueued.  One seed per call.
+ * current batch has been enqueued.  One seed per call (several: hmpc_solve_adjoint_multi below).
  * hmpc_set_device_adjoint: caller-owned device buffers for later adjoints (any may be NULL = the handle's own, allocated for max_batch
  * by the first call that needs them; never inside hmpc_solve); moving the buffers makes an adjoint already computed stale, as do every
  * solve and every new batch.  The gains and the first-order wrench are not touched by any of these calls, nor they by theirs.
@@ -655,6 +655,44 @@ int hmpc_get_device_adjoint(hmpc_handle *h, double **device_grad_x0, double **de
                             double **device_grad_alpha, double **device_dir, double **device_summary);
 int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
                           double *summary);
+/* ---- multi-seed adjoint: several loss gradients of the same solve behind one matrix backward pass ----
+ * hmpc_solve_adjoint under n_seeds seeds at once: the Jacobian of a step's wrench (unit seeds), Gauss-Newton on a vector residual,
+ * several losses on one sweep.  The assembly, the free directions and the matrix backward pass do not depend on the seed and run once
+ * per launch; each seed's vector recursion and forward pass run beside them.
+ *   Definition.  Seed s is, chain for chain, items 3-5 of hmpc_solve_adjoint's contract above: every output of slice s is bit for bit
+ *   what hmpc_solve_adjoint returns under that seed alone (summary[s][.][0] is therefore the same for every s).
+ *   Layouts, seed-major over the CURRENT batch: device_seeds[n_seeds][batch][h][U]; grad_x0[n_seeds][batch][13],
+ *   grad_traj[n_seeds][batch][h][12], grad_weights[n_seeds][batch][12], grad_alpha[n_seeds][batch][U], dir[n_seeds][batch][h][U],
+ *   summary[n_seeds][batch][2], all binary64: slice s of every array has exactly the layout of a single-seed call on the current batch.
+ *   The seeds must not overlap the outputs.
+ * hmpc_solve_adjoint_multi enqueues ceil(n_seeds / (6 NC)) launches on `stream` -- ONE for n_seeds <= U -- and synchronises nothing.
+ * HMPC_E_ARG, nothing enqueued: NULL seeds, n_seeds outside 1 .. HMPC_ADJOINT_MAX_SEEDS, no solve of the current batch, more seeds than
+ * the caller's buffers hold, or inside a solve on an external constraint block.  hmpc_solve_adjoint, its buffers, what
+ * hmpc_get_device_adjoint returns and an adjoint it computed are not touched.
+ * hmpc_set_device_adjoint_multi: caller-owned device buffers with room for n_seeds slices (any may be NULL = the handle's own, reserved
+ * for (n_seeds, max_batch) by the launch that needs them and grown by a later launch with more seeds; never inside hmpc_solve; with all
+ * six NULL n_seeds is not read).  HMPC_E_ARG when a buffer is given and n_seeds lies outside 1 .. HMPC_ADJOINT_MAX_SEEDS.
+ * hmpc_get_device_adjoint_multi: slice 0 of where the multi-seed adjoint is or goes next (one of the handle's own that no launch has
+ * reserved yet: NULL) and the seeds of the one that stands (0: none); any pointer may be NULL.  hmpc_download_adjoint_multi waits for the
+ * stream of the last call, then copies the slices of the seeds enqueued (any pointer may be NULL); HMPC_E_ARG when no multi-seed
+ * adjoint stands; with no batch set it copies nothing and returns HMPC_OK.
+ * A multi-seed adjoint goes stale on every solve, every new batch and every hmpc_set_device_adjoint_multi.
+ * hmpc_select_adjoint_seed(h, s) makes slice s of the multi-seed adjoint that stands the handle's CURRENT adjoint: pointer arithmetic on
+ * the host, no launch, no copy.  hmpc_adjoint_model, hmpc_adjoint_limits, hmpc_adjoint_record and hmpc_download_adjoint then behave
+ * exactly as after hmpc_solve_adjoint under that seed; hmpc_adjoint_limits is handed the seed's own slice, device_seeds + s batch h U.
+ * The current adjoint is whichever came last of hmpc_solve_adjoint and a selection; a selection makes model, limit and record gradients
+ * stale as a new adjoint does, and falls with the multi-seed adjoint it points into (also when a new hmpc_solve_adjoint_multi overwrites
+ * it).  HMPC_E_ARG: s outside 0 .. n_seeds - 1, or no multi-seed adjoint stands.  The three downstream launches stay one seed each.
+ * Device groups: per member, through hmpc_group_member; nothing on the process-global interface. */
+#define HMPC_ADJOINT_MAX_SEEDS 240
+int hmpc_solve_adjoint_multi(hmpc_handle *h, const double *device_seeds, int n_seeds, void *stream);
+int hmpc_set_device_adjoint_multi(hmpc_handle *h, int n_seeds, double *device_grad_x0, double *device_grad_traj, double *device_grad_weights,
+                                  double *device_grad_alpha, double *device_dir, double *device_summary);
+int hmpc_get_device_adjoint_multi(hmpc_handle *h, int *n_seeds, double **device_grad_x0, double **device_grad_traj, double **device_grad_weights,
+                                  double **device_grad_alpha, double **device_dir, double **device_summary);
+int hmpc_download_adjoint_multi(hmpc_handle *h, double *grad_x0, double *grad_traj, double *grad_weights, double *grad_alpha, double *dir,
+                                double *summary);
+int hmpc_select_adjoint_seed(hmpc_handle *h, int s);
 /* ---- model gradients of the solve: foot positions, mass, body inertia, Acd and Bcd themselves ----
  * Behind hmpc_solve_adjoint: the gradient of the same loss in what enters the QP through the prediction model.  With the active set
  * frozen and du = dir of the last adjoint, dL/dtheta = <G_A, dA/dtheta> + <G_B, dB/dtheta> for every theta that enters through A = Acd
