@@ -42,6 +42,7 @@ EXPORTS = [
     "hmpc_adjoint_model", "hmpc_set_device_adjoint_model", "hmpc_get_device_adjoint_model", "hmpc_download_adjoint_model",
     "hmpc_adjoint_limits", "hmpc_set_device_adjoint_limits", "hmpc_get_device_adjoint_limits", "hmpc_download_adjoint_limits",
     "hmpc_adjoint_record", "hmpc_set_device_adjoint_record", "hmpc_get_device_adjoint_record", "hmpc_download_adjoint_record",
+    "hmpc_adjoint_chain_multi", "hmpc_set_device_adjoint_chain_multi", "hmpc_get_device_adjoint_chain_multi", "hmpc_download_adjoint_chain_multi",
 ]
 
 
@@ -53,6 +54,15 @@ class Params(C.Structure):
     """include/hector_mpc.h struct hmpc_params (robot / contact constants; defaults = the reference's literals)."""
     _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 3), ("mu", C.c_float), ("lt", C.c_float), ("lh", C.c_float),
                 ("gravity", C.c_float)]
+
+
+CHAIN_COMPACT = ("grad_record", "grad_frames", "grad_rpy", "grad_params", "grad_limits", "limit_summary")
+CHAIN_DETAIL = ("grad_A", "grad_B", "grad_r", "costate", "grad_Fc", "grad_bound", "lambda", "nu")
+
+
+class AdjointChain(C.Structure):
+    """include/hector_mpc.h struct hmpc_adjoint_chain (the arrays of hmpc_adjoint_chain_multi: six compact, eight detail)."""
+    _fields_ = [(k, C.c_void_p) for k in CHAIN_COMPACT + CHAIN_DETAIL]
 
 
 class TickInputs(C.Structure):
@@ -254,6 +264,10 @@ def load():
     L.hmpc_set_device_adjoint_record.argtypes = [vp] + [vp] * 3
     L.hmpc_get_device_adjoint_record.argtypes = [vp] + [C.POINTER(vp)] * 3
     L.hmpc_download_adjoint_record.argtypes = [vp] + [vp] * 3
+    L.hmpc_adjoint_chain_multi.argtypes = [vp, vp, vp]
+    L.hmpc_set_device_adjoint_chain_multi.argtypes = [vp, ci, C.POINTER(AdjointChain)]
+    L.hmpc_get_device_adjoint_chain_multi.argtypes = [vp, C.POINTER(ci), C.POINTER(AdjointChain)]
+    L.hmpc_download_adjoint_chain_multi.argtypes = [vp, C.POINTER(AdjointChain)]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

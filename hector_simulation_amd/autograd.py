@@ -13,7 +13,8 @@ the adjoint kernel (include/hector_mpc.h hmpc_solve_adjoint; csrc/hmpc_adjoint.h
 
     jac, grad_params, grad_limits = wrench_jacobian(mpc, step=0)  # behind a solve: d u_step / d record [b, U, record floats], from ONE
                                                                   # multi-seed adjoint launch (hmpc_solve_adjoint_multi;
-                                                                  # csrc/hmpc_adjoint_multi.hip) and U downstream chains
+                                                                  # csrc/hmpc_adjoint_multi.hip) and ONE chain launch behind it
+                                                                  # (hmpc_adjoint_chain_multi; csrc/hmpc_adjoint_chain.hip)
 
 The derivatives are those of the QP's solution with its linearisation and the active set frozen (exact wherever the active set is locally
 constant).  Records are packed on the host (device-resident packing is a matter of its own); ``grad_x0`` and ``dir`` of the last backward
@@ -97,15 +98,33 @@ def _multi_buffers(mpc, device, n_seeds):
     return buf
 
 
+def _chain_buffers(mpc, device, n_seeds):
+    """The same for the compact arrays of the multi-seed chain (``set_device_adjoint_chain_multi``); no detail array is asked for."""
+    buf = getattr(mpc, "_autograd_chain_buffers", None)
+    if buf is None or buf["grad_rpy"].shape[0] < n_seeds:
+        b, nc = mpc.max_batch, mpc.contacts
+        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
+        shapes = dict(grad_record=(b, nf + 12 * mpc.horizon), grad_frames=(b, 1 + nc, 3, 3), grad_rpy=(b, 3), grad_params=(b, 4),
+                      grad_limits=(b, 3 + nc), limit_summary=(b, 3))
+        buf = {k: torch.zeros((n_seeds,) + s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        mpc._autograd_chain_buffers = buf
+    now = mpc.get_device_adjoint_chain_multi()
+    want = {k: (buf[k].data_ptr() if k in buf else 0) for k in mpc.CHAIN_KEYS}
+    if {k: now[k] for k in mpc.CHAIN_KEYS} != want:
+        mpc.set_device_adjoint_chain_multi(buf["grad_rpy"].shape[0], keepalive=buf, **{k + "_ptr": buf[k].data_ptr() for k in buf})
+    return buf
+
+
 def wrench_jacobian(mpc, step=0, generation=None):
     """Behind a solve of ``mpc``: the Jacobian of the wrench of horizon step ``step`` in every float of the packed record, with the
-    linearisation and the active set frozen.  The unit seeds e_c at ``step`` go on the device, ONE multi-seed launch
-    (hmpc_solve_adjoint_multi) runs the matrix backward pass once for all 6 contacts of them, and for every row c the chain select ->
-    model gradients -> limit gradients -> record gradients follows on torch's current stream into torch-owned buffers.  Returns
-    ``(jac, grad_params, grad_limits)``: float64 CUDA tensors [batch, U, NF + 12 h] (``d u_step[c] / d record``: row c is what
-    ``differentiable_solve_fields`` returns under grad_output = e_c, bit for bit), [batch, U, 4] and [batch, U, 3 + contacts].  With
-    ``generation`` (``mpc.generation`` as it stood behind the solve) the call is refused when the object has uploaded, solved or been
-    given other records or outputs since, as a backward of ``differentiable_solve`` is."""
+    linearisation and the active set frozen.  The unit seeds e_c at ``step`` go on the device and TWO calls follow on torch's current
+    stream into torch-owned buffers: ONE multi-seed launch (hmpc_solve_adjoint_multi) runs the matrix backward pass once for all 6 contacts
+    of them, and ONE chain launch (hmpc_adjoint_chain_multi) runs model gradients -> limit gradients -> record gradients of every row
+    behind one assembly.  Returns ``(jac, grad_params, grad_limits)``: float64 CUDA tensors [batch, U, NF + 12 h] (``d u_step[c] / d
+    record``: row c is what ``differentiable_solve_fields`` returns under grad_output = e_c, bit for bit), [batch, U, 4] and [batch, U, 3 +
+    contacts].  The call leaves no selection (``select_adjoint_seed``) behind and moves none of the single-seed adjoint, model, limit and
+    record buffers.  With ``generation`` (``mpc.generation`` as it stood behind the solve) the call is refused when the object has
+    uploaded, solved or been given other records or outputs since, as a backward of ``differentiable_solve`` is."""
     if generation is not None and mpc.generation != generation:
         raise RuntimeError("wrench_jacobian: the handle has solved another batch since; its forces are gone")
     b, nc, hz = mpc.batch, mpc.contacts, mpc.horizon
@@ -114,23 +133,19 @@ def wrench_jacobian(mpc, step=0, generation=None):
         raise ValueError(f"wrench_jacobian: step {step} outside the horizon")
     device = torch.device("cuda", mpc.device)
     _multi_buffers(mpc, device, u)
-    mbuf, lbuf, rbuf = _model_buffers(mpc, device), _limit_buffers(mpc, device), _record_buffers(mpc, device)
+    cbuf = _chain_buffers(mpc, device, u)
     seeds = torch.zeros((u, b, hz, u), dtype=torch.float64, device=device)
     seeds[torch.arange(u), :, step, torch.arange(u)] = 1.0
     stream = torch.cuda.current_stream(device).cuda_stream
     mpc.solve_adjoint_multi(seeds.data_ptr(), u, stream)
-    jac = torch.empty((b, u, rbuf["grad_record"].shape[1]), dtype=torch.float64, device=device)
-    grad_params = torch.empty((b, u, 4), dtype=torch.float64, device=device)
-    grad_limits = torch.empty((b, u, 3 + nc), dtype=torch.float64, device=device)
-    for c in range(u):
-        mpc.select_adjoint_seed(c)
-        mpc.adjoint_model(stream)
-        mpc.adjoint_limits(seeds[c].data_ptr(), stream)
-        mpc.adjoint_record(stream)
-        jac[:, c] = rbuf["grad_record"][:b]
-        grad_params[:, c] = mbuf["grad_params"][:b]
-        grad_limits[:, c] = lbuf["grad_limits"][:b]
-    return jac, grad_params, grad_limits
+    mpc.adjoint_chain_multi(seeds.data_ptr(), stream)
+
+    def rows(key):  # slices [u][batch][...] of the current batch -> [batch, u, ...]: one transposing copy
+        flat = cbuf[key].reshape(-1)
+        n = flat.numel() // (cbuf[key].shape[0] * mpc.max_batch)
+        return flat[:u * b * n].reshape(u, b, n).transpose(0, 1).contiguous()
+
+    return rows("grad_record"), rows("grad_params"), rows("grad_limits")
 
 
 FIELD_NAMES = ("p", "v", "q", "w", "r", "joint_angles", "weights", "Alpha_K", "traj", "Rhand", "f_max_hand")

@@ -1429,6 +1429,105 @@ int hmpc_download_adjoint_record(hmpc_handle *h, double *grad_record, double *gr
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Chain of the multi-seed adjoint: the model, limit and record gradients of every seed behind one assembly (hmpc_adjoint_chain.hip).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int CHAIN_ARRAYS = 14, CHAIN_COMPACT = 6;
+static_assert(sizeof(hmpc_adjoint_chain) == CHAIN_ARRAYS * sizeof(double *), "struct hmpc_adjoint_chain is fourteen pointers, in the order of the rows below");
+
+// doubles per instance of the fourteen arrays of a chain, in the member order of struct hmpc_adjoint_chain
+static void chain_row_sizes(const hmpc_handle *h, size_t n[CHAIN_ARRAYS]) {
+  const size_t nc = (size_t)h->nc, u = 6 * nc, hz = (size_t)h->setup.horizon, ls = 10 * nc * hz;
+  const size_t rows[CHAIN_ARRAYS] = {(size_t)hmpc::rec_fixed_floats(h->nc) + 12 * hz, (1 + nc) * 9, 3, hmpc::MADJ_PARAMS, 3 + nc, hmpc::LADJ_SUMMARY,
+                                     169, 13 * u, 3 * nc, hmpc::MADJ_COSTATE, 8 * nc * u, ls, ls, ls};
+  for (int k = 0; k < CHAIN_ARRAYS; ++k) n[k] = rows[k];
+}
+
+// slice 0 of where the chain is or goes next: per compact array the caller's buffer, else the handle's own (NULL before the first launch
+// reserved it); per detail array the caller's buffer, else NULL (not written)
+static void chain_base(const hmpc_handle *h, double *p[CHAIN_ARRAYS]) {
+  for (int k = 0; k < CHAIN_ARRAYS; ++k) p[k] = h->chain_caller[k] ? h->chain_caller[k] : (k < CHAIN_COMPACT ? h->d_chain_own[k].get() : nullptr);
+}
+
+int hmpc_set_device_adjoint_chain_multi(hmpc_handle *h, int n_seeds, const struct hmpc_adjoint_chain *device_buffers) {
+  if (!h) return HMPC_E_ARG;
+  double *p[CHAIN_ARRAYS] = {};
+  if (device_buffers) memcpy(p, device_buffers, sizeof(p));
+  bool any = false;
+  for (int k = 0; k < CHAIN_ARRAYS; ++k) any = any || p[k];
+  if (any && (n_seeds < 1 || n_seeds > HMPC_ADJOINT_MAX_SEEDS)) return HMPC_E_ARG;
+  for (int k = 0; k < CHAIN_ARRAYS; ++k) h->chain_caller[k] = p[k];
+  h->chain_caller_seeds = any ? n_seeds : 0;
+  h->results.retarget_adjoint_chain();
+  return HMPC_OK;
+}
+
+int hmpc_get_device_adjoint_chain_multi(hmpc_handle *h, int *n_seeds, struct hmpc_adjoint_chain *device_buffers) {
+  if (!h) return HMPC_E_ARG;
+  if (n_seeds) *n_seeds = h->results.has_adjoint_chain() ? h->results.adjoint_multi_seeds_enqueued() : 0;
+  if (device_buffers) {
+    double *p[CHAIN_ARRAYS];
+    chain_base(h, p);
+    memcpy(device_buffers, p, sizeof(p));
+  }
+  return HMPC_OK;
+}
+
+int hmpc_adjoint_chain_multi(hmpc_handle *h, const double *device_seeds, void *stream) {
+  // the chain goes through the handle's own assembly, which an external constraint block is not
+  if (!h || !device_seeds || !h->results.has_adjoint_multi() || h->d_ext_Fc) return HMPC_E_ARG;
+  const int n_seeds = h->results.adjoint_multi_seeds_enqueued();
+  bool caller = false, own = false;
+  for (int k = 0; k < CHAIN_ARRAYS; ++k)
+    if (h->chain_caller[k]) caller = true;
+    else if (k < CHAIN_COMPACT) own = true;
+  if (caller && n_seeds > h->chain_caller_seeds) return HMPC_E_ARG;  // the caller's buffers hold fewer slices
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  size_t n[CHAIN_ARRAYS];
+  chain_row_sizes(h, n);
+  if (own) {  // the handle's own: room for (n_seeds, max_batch); an older, smaller allocation may still be read on any stream
+    const bool grows = n_seeds > h->chain_own_seeds;
+    if (grows) h->results.retarget_adjoint_chain();  // (what the old buffers hold goes with them)
+    for (int k = 0; k < CHAIN_COMPACT; ++k)
+      if (!h->chain_caller[k]) HIP_TRY(h->d_chain_own[k].reserve((size_t)n_seeds * (size_t)h->max_batch * n[k] * sizeof(double), (hipStream_t)stream, true));
+    if (grows) h->chain_own_seeds = n_seeds;
+  }
+  const hmpc::AdjointOut m = adjoint_multi_base(h);  // (where that adjoint went: moving it would have made it stale)
+  const hmpc::AdjointChainIn in = {device_seeds, m.dir, m.grad_x0, m.grad_traj, m.grad_weights, m.grad_alpha};
+  double *p[CHAIN_ARRAYS];
+  chain_base(h, p);
+  const hmpc::AdjointChainOut out = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12], p[13]};
+  hmpc::KernelArgs a;
+  memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
+  set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
+  h->last_stream = (hipStream_t)stream;
+  HIP_TRY(hmpc::launch_adjoint_chain(h->nc, a, h->cert_act_tol, (double)h->params.mass, in, n_seeds, out, (hipStream_t)stream));
+  for (int k = 0; k < CHAIN_ARRAYS; ++k) h->chain_written[k] = p[k] != nullptr;
+  h->results.on_adjoint_chain();
+  return HMPC_OK;
+}
+
+int hmpc_download_adjoint_chain_multi(hmpc_handle *h, const struct hmpc_adjoint_chain *host_buffers) {
+  if (!h) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  if (!h->results.has_adjoint_chain()) return HMPC_E_ARG;  // nothing computed from the multi-seed adjoint that stands
+  double *dst[CHAIN_ARRAYS] = {};
+  if (host_buffers) memcpy(dst, host_buffers, sizeof(dst));
+  for (int k = 0; k < CHAIN_ARRAYS; ++k)
+    if (dst[k] && !h->chain_written[k]) return HMPC_E_ARG;  // a detail array that was not written
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  double *src[CHAIN_ARRAYS];
+  chain_base(h, src);
+  size_t n[CHAIN_ARRAYS];
+  chain_row_sizes(h, n);
+  const size_t rows = (size_t)h->results.adjoint_multi_seeds_enqueued() * (size_t)h->batch;
+  for (int k = 0; k < CHAIN_ARRAYS; ++k)
+    if (dst[k]) HIP_TRY(hipMemcpy(dst[k], src[k], rows * n[k] * sizeof(double), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Selection: the best command of every sweep group, from the last solve's status and forces and the last prediction (hmpc_select.hip).
 // ------------------------------------------------------------------------------------------------------------------
 struct SelectionBuffers {

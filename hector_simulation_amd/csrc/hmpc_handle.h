@@ -12,6 +12,7 @@
 #include "hmpc_feedback.h"
 #include "hmpc_adjoint.h"
 #include "hmpc_adjoint_multi.h"
+#include "hmpc_adjoint_chain.h"
 #include "hmpc_model_adjoint.h"
 #include "hmpc_limit_adjoint.h"
 #include "hmpc_pose_adjoint.h"
@@ -150,6 +151,14 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   // [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_record) or the handle's own, allocated by the first call
   // that needs them
   OutputBuffer<double> d_padj_record, d_padj_frames, d_padj_rpy;
+  // chain of the multi-seed adjoint (hmpc_adjoint_chain_multi): the fourteen arrays of struct hmpc_adjoint_chain in its member order,
+  // seed-major over the CURRENT batch; the six compact ones to the caller's buffers (hmpc_set_device_adjoint_chain_multi, room for
+  // chain_caller_seeds slices) or the handle's own, reserved for (n_seeds, max_batch) by the launch that needs them (chain_own_seeds =
+  // what they hold room for); the eight detail ones to the caller's buffers only.  chain_written = the arrays the chain that stands wrote.
+  DeviceBuffer<double> d_chain_own[6];
+  double *chain_caller[14] = {};
+  int chain_caller_seeds = 0, chain_own_seeds = 0;
+  bool chain_written[14] = {};
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

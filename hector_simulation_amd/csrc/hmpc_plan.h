@@ -141,13 +141,13 @@ inline bool params_ok(const hmpc_params &p) {
 
 // ---------------------------------------------------------------------------------------------------- what is still valid
 // Which results on the device belong to the CURRENT batch and its LAST solve.  The graph: batch -> solve -> prediction -> selection,
-// solve -> margins, solve -> certificate, solve -> gains -> first-order wrench, solve -> adjoint -> model gradients, adjoint -> limit gradients, solve -> multi-seed adjoint -> (a selected slice as the adjoint), (adjoint, model gradients, limit gradients) -> record gradients; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the facts.
+// solve -> margins, solve -> certificate, solve -> gains -> first-order wrench, solve -> adjoint -> model gradients, adjoint -> limit gradients, solve -> multi-seed adjoint -> (a selected slice as the adjoint), multi-seed adjoint -> chain (the model, limit and record gradients of every seed), (adjoint, model gradients, limit gradients) -> record gradients; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the facts.
 // (hmpc_resolve_failed repairs the solve in place and invalidates nothing; a bare launch that is no solve -- hmpc_debug_phase_cycles
 //  without device repair -- does not count as one.)
 class ResultState {
  public:
-  void on_batch() { solve_enqueued = predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = false, adjoint_selected = -1; }          // the handle holds another batch
-  void on_solve() { solve_enqueued = true, predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = false, adjoint_selected = -1; }    // every solve of a batch: its forces are newer than anything derived
+  void on_batch() { solve_enqueued = predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = adjoint_chain_enqueued = false, adjoint_selected = -1; }          // the handle holds another batch
+  void on_solve() { solve_enqueued = true, predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = adjoint_chain_enqueued = false, adjoint_selected = -1; }    // every solve of a batch: its forces are newer than anything derived
   void on_predict() { predict_enqueued = true, select_enqueued = false; }                      // (a selection made before this prediction read an older one)
   void on_select(int groups) { select_enqueued = true, select_groups = groups; }
   void on_margins() { margins_enqueued = true; }
@@ -162,8 +162,12 @@ class ResultState {
   // and record gradients -- is whichever came last of a single launch (on_adjoint) and a selected slice of the multi-seed one
   // (on_select_adjoint; the C entry point asks has_adjoint_multi and the range of s first).  A new multi-seed launch or new buffers for it
   // overwrite or move a selected slice, so a current adjoint that is a selection falls with them; one from a single launch does not.
-  void on_adjoint_multi(int seeds) { adjoint_multi_enqueued = true, adjoint_multi_seeds = seeds, drop_selection(); }
+  void on_adjoint_multi(int seeds) { adjoint_multi_enqueued = true, adjoint_multi_seeds = seeds, adjoint_chain_enqueued = false, drop_selection(); }
   void on_select_adjoint(int s) { adjoint_enqueued = true, adjoint_selected = s, model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }
+  // The chain of the multi-seed adjoint (hmpc_adjoint_chain_multi) is a node behind it alone, in buffers of its own: it reads the multi-seed
+  // adjoint's slices where they stand and touches neither the current adjoint, a selection, nor the single-seed model, limit and record
+  // nodes; none of those touches it.  (The C entry point asks has_adjoint_multi first.)
+  void on_adjoint_chain() { adjoint_chain_enqueued = true; }
   // the caller moved a result's buffers: whatever was computed went elsewhere
   void retarget_prediction() { predict_enqueued = select_enqueued = false; }
   void retarget_selection() { select_enqueued = false; }
@@ -172,7 +176,8 @@ class ResultState {
   void retarget_gains() { gains_enqueued = first_order_enqueued = false; }
   void retarget_first_order() { first_order_enqueued = false; }
   void retarget_adjoint() { adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false, adjoint_selected = -1; }  // (a selection goes too: the current adjoint is gone either way)
-  void retarget_adjoint_multi() { adjoint_multi_enqueued = false, drop_selection(); }
+  void retarget_adjoint_multi() { adjoint_multi_enqueued = adjoint_chain_enqueued = false, drop_selection(); }
+  void retarget_adjoint_chain() { adjoint_chain_enqueued = false; }
   void retarget_model_adjoint() { model_adjoint_enqueued = record_adjoint_enqueued = false; }
   void retarget_limit_adjoint() { limit_adjoint_enqueued = record_adjoint_enqueued = false; }
   void retarget_record_adjoint() { record_adjoint_enqueued = false; }
@@ -191,13 +196,14 @@ class ResultState {
   bool has_record_adjoint() const { return record_adjoint_enqueued; }  // ... and record gradients behind all three
   bool has_adjoint_multi() const { return adjoint_multi_enqueued; }  // a multi-seed adjoint of the last solve of the current batch has been enqueued
   int adjoint_multi_seeds_enqueued() const { return adjoint_multi_enqueued ? adjoint_multi_seeds : 0; }  // ... and its seeds
+  bool has_adjoint_chain() const { return adjoint_multi_enqueued && adjoint_chain_enqueued; }  // ... and the chain of every seed behind it
   int selected_adjoint_seed() const { return adjoint_enqueued ? adjoint_selected : -1; }  // the slice the current adjoint is (-1: a single launch's, or none)
   int selected_groups() const { return select_enqueued ? select_groups : 0; }  // groups of that selection
 
  private:
   bool solve_enqueued = false, predict_enqueued = false, select_enqueued = false, margins_enqueued = false, certificate_enqueued = false,
        gains_enqueued = false, first_order_enqueued = false, adjoint_enqueued = false, model_adjoint_enqueued = false, limit_adjoint_enqueued = false,
-       record_adjoint_enqueued = false, adjoint_multi_enqueued = false;
+       record_adjoint_enqueued = false, adjoint_multi_enqueued = false, adjoint_chain_enqueued = false;
   int select_groups = 0, adjoint_multi_seeds = 0, adjoint_selected = -1;
   void drop_selection() {
     if (adjoint_selected >= 0) adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false, adjoint_selected = -1;

@@ -621,6 +621,57 @@ class BatchedMPC:
         _check(self.L.hmpc_set_device_adjoint_record(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_record_ptr, grad_frames_ptr, grad_rpy_ptr)]),
                "hmpc_set_device_adjoint_record")
 
+    CHAIN_KEYS = _lib.CHAIN_COMPACT + _lib.CHAIN_DETAIL
+
+    def _chain_shapes(self, n_seeds: int) -> dict:
+        s, b, nc, hz = n_seeds, self.batch, self.contacts, self.horizon
+        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
+        shapes = dict(grad_record=(s, b, nf + 12 * hz), grad_frames=(s, b, 1 + nc, 3, 3), grad_rpy=(s, b, 3), grad_params=(s, b, 4),
+                      grad_limits=(s, b, 3 + nc), limit_summary=(s, b, 3), grad_A=(s, b, 13, 13), grad_B=(s, b, 13, 6 * nc), grad_r=(s, b, 3, nc),
+                      costate=(s, b, 2, 13), grad_Fc=(s, b, 8 * nc, 6 * nc), grad_bound=(s, b, hz, nc, 10), nu=(s, b, hz, nc, 10))
+        shapes["lambda"] = (s, b, hz, nc, 10)
+        return shapes
+
+    def adjoint_chain_multi(self, seeds_ptr: int, stream: int = 0) -> None:
+        """Behind ``solve_adjoint_multi``: for every seed of it the chain ``adjoint_model`` -> ``adjoint_limits`` -> ``adjoint_record``,
+        one launch per 6 contacts seeds on ``stream`` behind ONE assembly, forward chain and active set (include/hector_mpc.h
+        hmpc_adjoint_chain_multi).  ``seeds_ptr``: the seeds that adjoint was given, again.  Slice s of every output is bit for bit what the
+        three calls leave behind ``select_adjoint_seed(s)``; neither a selection nor the single-seed results are touched.  Raises for null
+        seeds and when no multi-seed adjoint of the last solve of the current batch stands."""
+        _check(self.L.hmpc_adjoint_chain_multi(self.h, C.c_void_p(int(seeds_ptr or 0)), C.c_void_p(stream)), "hmpc_adjoint_chain_multi")
+
+    def get_device_adjoint_chain_multi(self) -> dict:
+        """Device pointers of slice 0 of where the chain is or goes next, by ``CHAIN_KEYS`` (0: a compact array of the handle's own that
+        no launch has reserved yet, or a detail array not given), and ``n_seeds``: the seeds of the chain that stands (0: none)."""
+        n, b = C.c_int(0), _lib.AdjointChain()
+        _check(self.L.hmpc_get_device_adjoint_chain_multi(self.h, C.byref(n), C.byref(b)), "hmpc_get_device_adjoint_chain_multi")
+        return dict({k: int(getattr(b, k) or 0) for k in self.CHAIN_KEYS}, n_seeds=n.value)
+
+    def download_adjoint_chain_multi(self, detail: bool = False) -> dict:
+        """The compact arrays of the last ``adjoint_chain_multi`` -- grad_record, grad_frames, grad_rpy (``download_adjoint_record``'s),
+        grad_params (``download_adjoint_model``'s), grad_limits and limit_summary (``download_adjoint_limits``') -- with a leading axis
+        over the seeds; with ``detail`` the eight detail arrays as well (raises unless buffers were given for all of them).  Waits; runs
+        no safe pass."""
+        n = C.c_int(0)
+        _check(self.L.hmpc_get_device_adjoint_chain_multi(self.h, C.byref(n), None), "hmpc_get_device_adjoint_chain_multi")
+        shapes = self._chain_shapes(n.value)
+        out = {k: np.zeros(shapes[k]) for k in (self.CHAIN_KEYS if detail else _lib.CHAIN_COMPACT)}
+        b = _lib.AdjointChain(**{k: v.ctypes.data for k, v in out.items()})
+        _check(self.L.hmpc_download_adjoint_chain_multi(self.h, C.byref(b)), "hmpc_download_adjoint_chain_multi")
+        return out
+
+    def set_device_adjoint_chain_multi(self, n_seeds: int = 0, keepalive=None, **ptrs) -> None:
+        """Caller-owned device buffers for later chains, with room for ``n_seeds`` slices of the current batch, by ``CHAIN_KEYS`` with
+        ``_ptr`` appended (``grad_record_ptr=...``, ``lambda_ptr=...``).  A compact array left out or 0 is the handle's own; a detail
+        array left out or 0 is not written."""
+        names = {k + "_ptr": k for k in self.CHAIN_KEYS}
+        unknown = [k for k in ptrs if k not in names]
+        if unknown:
+            raise TypeError(f"set_device_adjoint_chain_multi: unknown buffers {unknown}")
+        self._keep_chain = keepalive
+        b = _lib.AdjointChain(**{names[k]: int(v or 0) or None for k, v in ptrs.items()})
+        _check(self.L.hmpc_set_device_adjoint_chain_multi(self.h, int(n_seeds), C.byref(b)), "hmpc_set_device_adjoint_chain_multi")
+
     def debug_handover_slots(self) -> np.ndarray:
         """Test hook (hmpc_debug_handover_slots): the hand-over slot table of the current batch, int32[batch]; entry i == i where
         the last solve handed instance i's working set over and nothing has consumed it yet, else -1."""

@@ -682,7 +682,8 @@ int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, do
  * exactly as after hmpc_solve_adjoint under that seed; hmpc_adjoint_limits is handed the seed's own slice, device_seeds + s batch h U.
  * The current adjoint is whichever came last of hmpc_solve_adjoint and a selection; a selection makes model, limit and record gradients
  * stale as a new adjoint does, and falls with the multi-seed adjoint it points into (also when a new hmpc_solve_adjoint_multi overwrites
- * it).  HMPC_E_ARG: s outside 0 .. n_seeds - 1, or no multi-seed adjoint stands.  The three downstream launches stay one seed each.
+ * it).  HMPC_E_ARG: s outside 0 .. n_seeds - 1, or no multi-seed adjoint stands.  Behind a selection the three downstream launches are one
+ * seed each; hmpc_adjoint_chain_multi below runs them for every seed at once.
  * Device groups: per member, through hmpc_group_member; nothing on the process-global interface. */
 #define HMPC_ADJOINT_MAX_SEEDS 240
 int hmpc_solve_adjoint_multi(hmpc_handle *h, const double *device_seeds, int n_seeds, void *stream);
@@ -879,6 +880,54 @@ int hmpc_adjoint_record(hmpc_handle *h, void *stream);
 int hmpc_set_device_adjoint_record(hmpc_handle *h, double *device_grad_record, double *device_grad_frames, double *device_grad_rpy);
 int hmpc_get_device_adjoint_record(hmpc_handle *h, double **device_grad_record, double **device_grad_frames, double **device_grad_rpy);
 int hmpc_download_adjoint_record(hmpc_handle *h, double *grad_record, double *grad_frames, double *grad_rpy);
+/* ---- the chain of the multi-seed adjoint: model, limit and record gradients of every seed behind one assembly ----
+ * Behind hmpc_solve_adjoint_multi: for every seed of the multi-seed adjoint that stands, the chain hmpc_adjoint_model ->
+ * hmpc_adjoint_limits -> hmpc_adjoint_record, so that the Jacobian of a step's wrench in every float of the record is two calls.  The
+ * record load, the assembly, the forward chain x_j, the tracking costate c_j, grad_i, the slacks, the active set, the admitted normals
+ * and lambda do not depend on the seed and are formed once per launch; each seed's dx_j, d_j, rho, nu, outer-product sums and chain
+ * rules run beside them, their intermediates never leaving the chip unless a detail buffer asks for them.
+ *   Definition, by reference: no arithmetic of its own.  Were the handle's state hmpc_select_adjoint_seed(h, s), then hmpc_adjoint_model,
+ *   then hmpc_adjoint_limits(h, device_seeds + s batch h U), then hmpc_adjoint_record, slice s of every array below is bit for bit what
+ *   the matching array of those three calls holds (items 1-5 of the model gradients, 1-9 of the limit gradients, 1-8 of the record
+ *   gradients).  lambda, costate[.][0] and limit_summary[.][0] therefore carry the same bits in every slice.
+ *   Layouts, seed-major over the CURRENT batch, all binary64; slice s of every array has exactly the layout of the single-seed call on
+ *   the current batch.  Compact (always produced): grad_record[n_seeds][batch][NF + 12 h], grad_frames[n_seeds][batch][1 + NC][9],
+ *   grad_rpy[n_seeds][batch][3] (hmpc_adjoint_record's), grad_params[n_seeds][batch][4] (hmpc_adjoint_model's),
+ *   grad_limits[n_seeds][batch][3 + NC], limit_summary[n_seeds][batch][3] (hmpc_adjoint_limits').  Detail (written only where the caller
+ *   gives a buffer): grad_A[..][13][13], grad_B[..][13][U], grad_r[..][3][NC], costate[..][2][13] (hmpc_adjoint_model's); grad_Fc[..][8 NC][U],
+ *   grad_bound, lambda, nu[..][h][NC][10] (hmpc_adjoint_limits').
+ *   Inputs: dir, grad_x0, grad_traj, grad_weights and grad_alpha of the multi-seed adjoint, where it last wrote them; device_seeds
+ *   [n_seeds][batch][h][U], the seeds that adjoint was given, passed again (limit_summary[s][.][1] tells whether they were); the force
+ *   buffer, the record, hmpc_params, the per-instance mu and the certificate tolerance, as the single-seed calls read them.  The seeds
+ *   must not overlap the outputs.
+ * hmpc_adjoint_chain_multi enqueues ceil(n_seeds / (6 NC)) launches on `stream` -- ONE for n_seeds <= U -- and synchronises nothing.
+ * HMPC_E_ARG, nothing enqueued and no buffer touched: NULL seeds, no multi-seed adjoint of the last solve of the current batch stands,
+ * caller-owned buffers that hold fewer seeds than that adjoint has, or inside a solve on an external constraint block.
+ * hmpc_set_device_adjoint_chain_multi: caller-owned device buffers with room for n_seeds slices.  A NULL compact member is the handle's
+ * own buffer, reserved for (n_seeds, max_batch) by the launch that needs it and grown by a later launch with more seeds, never inside
+ * hmpc_solve; a NULL detail member means "not written".  NULL device_buffers: all members NULL (n_seeds is not read then).  HMPC_E_ARG
+ * when a buffer is given and n_seeds lies outside 1 .. HMPC_ADJOINT_MAX_SEEDS.
+ * hmpc_get_device_adjoint_chain_multi: slice 0 of where the chain is or goes next (a compact member of the handle's own that no launch
+ * has reserved yet, and a detail member not given: NULL) and the seeds of the chain that stands (0: none); either pointer may be NULL.
+ * hmpc_download_adjoint_chain_multi waits for the stream of the last call, then copies the slices of the seeds enqueued; any member may be
+ * NULL.  HMPC_E_ARG, nothing copied: no chain stands, or a detail array is asked for that was not written.  With no batch set it copies
+ * nothing and returns HMPC_OK.  It runs no safe pass.
+ * The chain goes stale on every solve, every new batch, every hmpc_solve_adjoint_multi, every hmpc_set_device_adjoint_multi and every
+ * hmpc_set_device_adjoint_chain_multi.  It touches neither the current adjoint, a selection, nor the single-seed model, limit and record
+ * gradients and their buffers, and none of those touches it: hmpc_select_adjoint_seed keeps working beside it, with the bits it has.
+ * For one or two seeds the selection and the three single-seed launches remain the advice (DESIGN.md section 4.21 has the break-even).
+ * Device groups: per member, through hmpc_group_member; nothing on the process-global interface. */
+struct hmpc_adjoint_chain {
+  /* compact: always produced */
+  double *grad_record, *grad_frames, *grad_rpy, *grad_params, *grad_limits, *limit_summary;
+  /* detail: written only where the caller gives a buffer */
+  double *grad_A, *grad_B, *grad_r, *costate;
+  double *grad_Fc, *grad_bound, *lambda, *nu;
+};
+int hmpc_adjoint_chain_multi(hmpc_handle *h, const double *device_seeds, void *stream);
+int hmpc_set_device_adjoint_chain_multi(hmpc_handle *h, int n_seeds, const struct hmpc_adjoint_chain *device_buffers);
+int hmpc_get_device_adjoint_chain_multi(hmpc_handle *h, int *n_seeds, struct hmpc_adjoint_chain *device_buffers);
+int hmpc_download_adjoint_chain_multi(hmpc_handle *h, const struct hmpc_adjoint_chain *host_buffers);
 /* ---- the best command of every sweep group, picked on the device ----
  * A command sweep solves one robot state under many candidate commands and the prediction scores each (cost[batch][2]); these calls
  * take the planner's last step without a trip to the host.  The current batch is G = batch / group_size groups of group_size
