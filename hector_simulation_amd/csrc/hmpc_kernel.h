@@ -43,6 +43,7 @@
 #include "hmpc_kernel_args.h"
 #include "hmpc_record.h"  // RecLayout (RL:: below), stance()
 #include "hmpc_schur_tiles.h"  // the deal of the tiles to the waves (mfs_owner, MfsTiles); index arithmetic of the Schur tiles
+#include "hmpc_matvec_index.h"  // lane constants and coefficients of gather_w
 
 namespace hmpc {
 // per-phase shader-clock profile of developer builds (-DHMPC_PROFILE, scripts/phase_profile.py); an empty object otherwise
@@ -308,8 +309,15 @@ struct VariantTraits {
   static constexpr bool THREE_WAVES = BPT == 1 && !EIGHT_WAVES && sizeof(SM) * (size_t)(3 * 256 / NT) <= (size_t)160 * 1024;
   static constexpr int WAVES_PER_EU = THREE_WAVES ? 3 : 2;
   // Per-thread constants recomputed at every use instead of held in a register (LazyInt below): LAZY, with two blocks per thread (144 registers of matrix);
-  // LAZY_IDX, the integer roles only, also FAST, SWEEP and CONT on the hand-over shape (exactly on their 168-register budget), not its SAFE variants
+  // LAZY_IDX, the integer roles only, also FAST, SWEEP and CONT on the hand-over shape, not its SAFE variants.  (Round 4 put them there "exactly on their
+  // 168-register budget"; since round 15 FAST stands at 159 and SWEEP at 162 VGPRs.  Round 26 tried LAZY_IDX = false for them again: 164 / 166 / 166 VGPRs,
+  // no spill, the same bits and a kernel time within 0.3 % of the lazy build's, headline ranges overlapping (profiles/r26) -- not worth the last registers.
+  // What a lazy index costs where it is used eight times in a row is paid once per call instead: gather_w forms its lane constants behind ONE opaque copy.)
   static constexpr bool LAZY = BPT == 2, LAZY_IDX = LAZY || (HANDOVER_SHAPE && ROLE != Role::SAFE);
+  // gather_w forms its lane constants once per call and its coefficients without selects (hmpc_matvec_index.h).  Not the wide SAFE variant
+  // <240, 20, 512, 0>, which sits on 256 VGPRs with 8 spilled registers (36 B of scratch): with the new gather_w the allocator spills 10 (44 B; 92 B
+  // without rmatvec's ng == NG branch, which every variant has), so it keeps the code it had
+  static constexpr bool GATHER_ONCE = !(WIDE_SHAPE && ROLE == Role::SAFE);
 
   // ---- the role: command sweeps, hand-over of a full working set (KernelArgs::spill, SpillLayout), passes over a list of flagged instances
   static constexpr bool SWEEP = ROLE == Role::SWEEP;  // the two sweep phases (see hmpc_kernel); otherwise the FAST variant of its shape
@@ -2392,20 +2400,27 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
           // (BPT == 2: the rows are read in chunks -- 30-40 registers of partials in flight at once, next to two register blocks,
           //  is what the allocator answers with spills; same summation order either way: even sources into s0, odd into s1)
           constexpr int CH = (BPT == 2) ? 6 : HB;
+          // every leg-step in stance (ng == NG, uniform: the nominal double-support solve): nothing to mask, the sum takes the rows as
+          // they are; otherwise the selects.  The same values in the same order either way.
+          auto sum_rows = [&](auto FULL) __attribute__((always_inline)) {
 #pragma unroll
-          for (int r0 = 0; r0 < HB; r0 += CH) {
-            double sv[CH];
+            for (int r0 = 0; r0 < HB; r0 += CH) {
+              double sv[CH];
 #pragma unroll
-            for (int r = 0; r < CH; ++r)
-              if (r0 + r < HB) sv[r] = Q.ST[((SM::STH == 1) ? hb * HB : 0) + r0 + r][tid];
+              for (int r = 0; r < CH; ++r)
+                if (r0 + r < HB) sv[r] = Q.ST[((SM::STH == 1) ? hb * HB : 0) + r0 + r][tid];
 #pragma unroll
-            for (int r = 0; r < CH; ++r)
-              if (r0 + r < HB) {
-                if (((r0 + r) & 1) == 0) s0 += (hbase + r0 + r < ng) ? sv[r] : 0.0;
-                else s1 += (hbase + r0 + r < ng) ? sv[r] : 0.0;
-              }
-            if constexpr (BPT == 2) asm volatile("" ::: "memory");  // (keeps the chunks' reads from being hoisted together again)
-          }
+              for (int r = 0; r < CH; ++r)
+                if (r0 + r < HB) {
+                  const double v = (decltype(FULL)::value || hbase + r0 + r < ng) ? sv[r] : 0.0;
+                  if (((r0 + r) & 1) == 0) s0 += v;
+                  else s1 += v;
+                }
+              if constexpr (BPT == 2) asm volatile("" ::: "memory");  // (keeps the chunks' reads from being hoisted together again)
+            }
+          };
+          if (ng == NG) sum_rows(std::true_type());
+          else sum_rows(std::false_type());
         }
         if (st + 1 == SM::STH) Q.z[tid] = s0 + s1;
       }
@@ -2540,25 +2555,55 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
     return (sl <= ssu) ? sl : ssu;
   };
   // w_i = sum over the active rows of variable i's leg-step of coef(row) * a_row[i]  (+ extra)
-  auto gather_w = [&](const double *coefv, double sgn, double extra) __attribute__((always_inline)) {
-    if (is_v) {
-      const unsigned long long am = *reinterpret_cast<const unsigned long long *>(&Q.act[8 * v_e]);
-      const unsigned long long sm = *reinterpret_cast<const unsigned long long *>(&Q.slot[8 * v_e]);
-      double acc0 = extra, acc1 = 0.0;
-      const int vleg = var_leg();
+  // The lane's constants -- leg-step e, position k, the column of its leg's normals in Cn, its leg-step's act / slot words -- are formed
+  // once per call (hmpc_matvec_index.h) and live only inside it: the eight rows are then immediate offsets from one LDS address each, and
+  // a coefficient is sgn * cf, its negation or +0.0 by bit operations on cf.  extra(lane, column of Cn) is the lane's own addend.
+  // (VT::GATHER_ONCE == false: the code as it was, a LazyInt per use and selects, with the addend handed in as a value)
+  auto gather_w = [&](const double *coefv, double sgn, auto extra, double extra_value) __attribute__((always_inline)) {
+    if constexpr (!VT::GATHER_ONCE) {
+      if (is_v) {
+        const unsigned long long am = *reinterpret_cast<const unsigned long long *>(&Q.act[8 * v_e]);
+        const unsigned long long sm = *reinterpret_cast<const unsigned long long *>(&Q.slot[8 * v_e]);
+        double acc0 = extra_value, acc1 = 0.0;
+        const int vleg = var_leg();
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) {
+          const int ac = (int)(signed char)((am >> (8 * rr)) & 0xff);
+          const int sl = (int)((sm >> (8 * rr)) & 0xff);
+          const double cf = coefv[sl];
+          const double coef = (ac == 0) ? 0.0 : ((ac > 0) ? sgn * cf : -sgn * cf);
+          const double cv = S.Cn[vleg][rr][v_k];
+          if (rr & 1) acc1 = dfma(coef, cv, acc1);
+          else acc0 = dfma(coef, cv, acc0);
+        }
+        Q.w[tid] = acc0 + acc1;
+      }
+    } else if (is_v) {
+      int e, k;
+      if constexpr (VT::LAZY_IDX) {  // (one opaque copy per call: nothing here is hoisted into a register that lives for the whole solve)
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        e = mv_var_e(t), k = mv_var_k(t);
+      } else {
+        e = v_e, k = v_k;
+      }
+      const int vleg = VT::LAZY_IDX ? (int)S.ls_leg[e] : v_leg_r;
+      const MvLane L = mv_lane(e, k, vleg);
+      const double *cncol = &S.Cn[0][0][0] + L.cn_col;
+      const unsigned long long am = *reinterpret_cast<const unsigned long long *>(&Q.act[L.row0]);
+      const unsigned long long sm = *reinterpret_cast<const unsigned long long *>(&Q.slot[L.row0]);
+      double acc0 = extra(L, cncol), acc1 = 0.0;
 #pragma unroll
       for (int rr = 0; rr < 8; ++rr) {
-        const int ac = (int)(signed char)((am >> (8 * rr)) & 0xff);
-        const int sl = (int)((sm >> (8 * rr)) & 0xff);
-        const double cf = coefv[sl];
-        const double coef = (ac == 0) ? 0.0 : ((ac > 0) ? sgn * cf : -sgn * cf);
-        const double cv = S.Cn[vleg][rr][v_k];
+        const double coef = mv_coef(am, rr, sgn < 0.0, coefv[mv_slot(sm, rr)]);
+        const double cv = cncol[mv_cn_row(rr)];
         if (rr & 1) acc1 = dfma(coef, cv, acc1);
         else acc0 = dfma(coef, cv, acc0);
       }
       Q.w[tid] = acc0 + acc1;
     }
   };
+  auto no_extra = [](const MvLane &, const double *) __attribute__((always_inline)) -> double { return 0.0; };
   // rout[j] (+)= sum_i E(j,i) din[i] for j < q: 4 lanes per row, quad reduction; optional dual ratio test on the result
   auto e_times = [&](const double *din, double *rout, bool accumulate, double &t1c, int &t1j, bool ratio) __attribute__((always_inline)) {
     for (int jb = 0; jb < q; jb += NT / 4) {
@@ -3046,7 +3091,7 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
       PROF_MARK(P_B_DROP);
       // (e) x = x_u + M N' u
       if (q > 0) {
-        gather_w(Q.u, 1.0, 0.0);
+        gather_w(Q.u, 1.0, no_extra, 0.0);
         __syncthreads();
         rmatvec(Q.w);
         if (is_v) Q.x[tid] = Q.xu[tid] + Q.z[tid];
@@ -3280,7 +3325,12 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
         __syncthreads();
         PROF_MARK(P_ED);
         // (4) w = n+ - N_W' r
-        gather_w(Q.r, -1.0, (is_v && v_e == ep) ? np[v_k] : 0.0);
+        // (a lane of leg-step ep reads its own entry of n+ = sg * (row p of its leg's normals) from Cn: the value np[k] holds)
+        double np_own = 0.0;
+        if constexpr (!VT::GATHER_ONCE) np_own = (is_v && v_e == ep) ? np[v_k] : 0.0;
+        gather_w(Q.r, -1.0, [&](const MvLane &L, const double *cncol) __attribute__((always_inline)) -> double {
+          return (L.e == ep) ? sg * cncol[MV_GS * (p & 7)] : 0.0;
+        }, np_own);
         __syncthreads();
         PROF_MARK(P_W);
         // (5) z = M w
@@ -3381,7 +3431,7 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
       //  step by step, and what the correction is there to remove is the drift of E's rank-one updates, orders of magnitude above
       //  the difference between that x and x(u) -- instead of recomputing x(u) first: one gather + one product with M less)
       if (!(!VT::LONGRUN && it == 0 && HMPC_REFINE > 0)) {
-      gather_w(Q.u, 1.0, 0.0);
+      gather_w(Q.u, 1.0, no_extra, 0.0);
       __syncthreads();
       rmatvec(Q.w);
       if (is_v) Q.x[tid] = Q.xu[tid] + Q.z[tid];
@@ -3496,7 +3546,7 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
       e_times(Q.d, Q.u, true, dmy, dj, false);
     }
     __syncthreads();
-    gather_w(Q.u, 1.0, 0.0);
+    gather_w(Q.u, 1.0, no_extra, 0.0);
     __syncthreads();
     rmatvec(Q.w);
     if (is_v) Q.x[tid] = Q.xu[tid] + Q.z[tid];
