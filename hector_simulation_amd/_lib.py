@@ -43,6 +43,8 @@ EXPORTS = [
     "hmpc_adjoint_limits", "hmpc_set_device_adjoint_limits", "hmpc_get_device_adjoint_limits", "hmpc_download_adjoint_limits",
     "hmpc_adjoint_record", "hmpc_set_device_adjoint_record", "hmpc_get_device_adjoint_record", "hmpc_download_adjoint_record",
     "hmpc_adjoint_chain_multi", "hmpc_set_device_adjoint_chain_multi", "hmpc_get_device_adjoint_chain_multi", "hmpc_download_adjoint_chain_multi",
+    "hmpc_default_plant", "hmpc_plant_step_device", "hmpc_rollout_device", "hmpc_set_device_rollout", "hmpc_get_device_rollout",
+    "hmpc_download_rollout",
 ]
 
 
@@ -73,6 +75,21 @@ class TickInputs(C.Structure):
                 ("yaw_rate_des", C.c_double), ("roll_des", C.c_double), ("pitch_des", C.c_double),
                 ("world_position_desired", C.c_double * 2), ("gait_offsets", C.c_int * 2),
                 ("gait_durations", C.c_int * 2), ("gait_iteration", C.c_int), ("flags", C.c_int)]
+
+
+class Plant(C.Structure):
+    """include/hector_mpc.h struct hmpc_plant (the plant's own constants; hmpc_default_plant fills the defaults)."""
+    _fields_ = [("dt_tick", C.c_double), ("dtMPC", C.c_double), ("substeps", C.c_int), ("advance_gait", C.c_int), ("flags", C.c_int),
+                ("reserved", C.c_int), ("mass", C.c_double), ("inertia", C.c_double * 3), ("gravity", C.c_double),
+                ("hip", (C.c_double * 3) * 2), ("fall_cos", C.c_double), ("device_mass", C.c_void_p), ("device_ext_wrench", C.c_void_p)]
+
+
+ROLLOUT_LOG = ("state", "wrench", "status", "tau", "summary")
+
+
+class RolloutLog(C.Structure):
+    """include/hector_mpc.h struct hmpc_rollout_log (device pointers of a rollout's log; each may be NULL)."""
+    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_LOG]
 
 
 class Command(C.Structure):
@@ -268,6 +285,13 @@ def load():
     L.hmpc_set_device_adjoint_chain_multi.argtypes = [vp, ci, C.POINTER(AdjointChain)]
     L.hmpc_get_device_adjoint_chain_multi.argtypes = [vp, C.POINTER(ci), C.POINTER(AdjointChain)]
     L.hmpc_download_adjoint_chain_multi.argtypes = [vp, C.POINTER(AdjointChain)]
+    L.hmpc_default_plant.argtypes = [C.POINTER(Plant)]
+    L.hmpc_default_plant.restype = None
+    L.hmpc_plant_step_device.argtypes = [vp, vp, ci, C.POINTER(Plant), vp, ci, vp, vp, vp, vp]
+    L.hmpc_rollout_device.argtypes = [vp, vp, ci, ci, cd, ci, ci, C.POINTER(Plant), C.POINTER(RolloutLog), vp]
+    L.hmpc_set_device_rollout.argtypes = [vp, C.POINTER(RolloutLog)]
+    L.hmpc_get_device_rollout.argtypes = [vp, ci, C.POINTER(RolloutLog)]
+    L.hmpc_download_rollout.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

@@ -159,6 +159,16 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   double *chain_caller[14] = {};
   int chain_caller_seeds = 0, chain_own_seeds = 0;
   bool chain_written[14] = {};
+  // closed loop (hmpc_rollout_device, hmpc_plant.hip): a tick's clamped world_position_desired [max_batch][2] and torques [max_batch][10]
+  // between its solve and its plant step; the handle's own log buffers, for max_batch x roll_own_ticks rows (hmpc_get_device_rollout);
+  // the caller's (hmpc_set_device_rollout); and where the last rollout logged, which is what hmpc_download_rollout copies
+  DeviceBuffer<double> d_roll_wpd, d_roll_tau, d_roll_state, d_roll_taulog;
+  DeviceBuffer<float> d_roll_wrench;
+  DeviceBuffer<uint32_t> d_roll_status;
+  DeviceBuffer<int32_t> d_roll_summary;
+  int roll_own_ticks = 0;
+  hmpc_rollout_log roll_caller{}, roll_last{};
+  int roll_last_batch = 0, roll_last_ticks = 0;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

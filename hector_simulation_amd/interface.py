@@ -22,6 +22,26 @@ TICK_DTYPE = np.dtype([("position", "f8", 3), ("vWorld", "f8", 3), ("omegaWorld"
 COMMAND_DTYPE = np.dtype([("v_des_robot", "f8", 2), ("yaw_rate_des", "f8"), ("roll_des", "f8"), ("pitch_des", "f8")], align=True)
 SELECT_NONE = 0xFFFFFFFF  # HMPC_SELECT_NONE: the status word of a group without a winner
 
+TICK_LEG_Q_MOTOR, TICK_FALLEN = 1, 2       # HMPC_TICK_* bits of hmpc_tick_inputs.flags
+PLANT_GYRO, PLANT_PLACE_FEET = 1, 2        # HMPC_PLANT_* bits of hmpc_plant.flags
+
+
+def default_plant(**fields):
+    """``struct hmpc_plant`` with the defaults of ``hmpc_default_plant``; keyword arguments overwrite scalar fields (dt_tick, dtMPC,
+    substeps, advance_gait, flags, mass, gravity, fall_cos) and ``inertia`` (3 values) / ``hip`` (2 x 3)."""
+    p = _lib.Plant()
+    _lib.load().hmpc_default_plant(C.byref(p))
+    for k, v in fields.items():
+        if k == "inertia":
+            p.inertia[:] = [float(x) for x in v]
+        elif k == "hip":
+            for leg in range(2):
+                p.hip[leg][:] = [float(x) for x in v[leg]]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "too_large", 4: "kkt", 5: "working_set_full", 6: "ok_relaxed", 7: "sweep_mismatch", 8: "hessian_not_positive_definite", 9: "regularisation_step"}
 
 
@@ -114,6 +134,7 @@ class BatchedMPC:
         self.stride = int(self.L.hmpc_record_stride_ex(self.horizon, self.contacts))
         self._keep = None
         self._keep_out = None
+        self.dt_mpc = float(dt)  # (binary64, as given: what rollout() passes as dtMPC by default)
         self.generation = 0  # counts the calls of this object that replace the batch or its forces (autograd.py compares it)
 
     def close(self):
@@ -723,6 +744,93 @@ class BatchedMPC:
         _check(self.L.hmpc_leg_torques(self.h, rb.ctypes.data, lq.ctypes.data, fff.ctypes.data, tau.ctypes.data),
                "hmpc_leg_torques")
         return fff, tau
+
+    # ---- closed loop on the device (include/hector_mpc.h hmpc_plant_step_device / hmpc_rollout_device)
+    def _stage_plant(self, plant, batch: int, instance_mass, ext_wrench):
+        """A copy of ``plant`` (default: ``default_plant()``) whose per-instance arrays, given as numpy, live in HBM; + what keeps them alive."""
+        import torch
+
+        p = _lib.Plant.from_buffer_copy(plant if plant is not None else default_plant())
+        keep = []
+        for name, arr, shape in (("device_mass", instance_mass, (batch,)), ("device_ext_wrench", ext_wrench, (batch, 6))):
+            if arr is not None:
+                t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64).reshape(shape).copy()).cuda(self.device)
+                keep.append(t)
+                setattr(p, name, t.data_ptr())
+        return p, keep
+
+    def plant_step(self, ticks, plant=None, forces=None, status=None, wpd=None, summary=None, device: bool = False, batch: int = 0,
+                   force_stride: int = 12, stream: int = 0, instance_mass=None, ext_wrench=None):
+        """One plant step: the ticks advanced by one MPC tick under the step-0 forces (include/hector_mpc.h hmpc_plant_step_device).
+        ``device=False``: ``ticks`` is a ``TICK_DTYPE`` array, ``forces`` float32[batch, >= 12], ``status`` uint32[batch], ``wpd``
+        float64[batch, 2], ``summary`` int32[batch, 4] (``None``: the handle's force / status buffers, the tick's own
+        world_position_desired, rows {0, -1, 0, 0}), ``instance_mass`` / ``ext_wrench`` numpy arrays for the plant's per-instance
+        pointers; everything is staged through HBM and the call waits: returns (new ticks, new summary).  ``device=True``: ``ticks``,
+        ``forces``, ``status``, ``wpd``, ``summary`` are device pointers (0 / None as in C), ``batch`` and ``force_stride`` as in C; the
+        launch is enqueued on ``stream`` and nothing is returned."""
+        if device:
+            p = plant if plant is not None else default_plant()
+            _check(self.L.hmpc_plant_step_device(self.h, C.c_void_p(int(ticks)), int(batch), C.byref(p), C.c_void_p(int(forces or 0)),
+                                                 int(force_stride), C.c_void_p(int(status or 0)), C.c_void_p(int(wpd or 0)),
+                                                 C.c_void_p(int(summary or 0)), C.c_void_p(stream)), "hmpc_plant_step_device")
+            return None
+        import torch
+
+        ticks = np.ascontiguousarray(ticks, dtype=TICK_DTYPE)
+        nb = ticks.shape[0]
+        p, keep = self._stage_plant(plant, nb, instance_mass, ext_wrench)
+        dev = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt).copy()).cuda(self.device)
+        d_t = torch.from_numpy(ticks.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
+        d_f, d_w = dev(forces, np.float32), dev(wpd, np.float64)
+        d_s = None if status is None else dev(np.ascontiguousarray(status, dtype=np.uint32).view(np.int32), np.int32)
+        if summary is None:
+            summary = np.tile(np.array([0, -1, 0, 0], dtype=np.int32), (nb, 1))
+        d_sum = dev(summary, np.int32)
+        stride = 12 if d_f is None else int(np.asarray(forces).reshape(nb, -1).shape[1])
+        ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_plant_step_device(self.h, ptr(d_t), nb, C.byref(p), ptr(d_f), stride, ptr(d_s), ptr(d_w), ptr(d_sum),
+                                             C.c_void_p(stream)), "hmpc_plant_step_device")
+        torch.cuda.synchronize(self.device)
+        del keep
+        return d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy(), d_sum.cpu().numpy()
+
+    def download_rollout(self, batch: int, n_ticks: int) -> dict:
+        """The log of the last rollout (waits): state float64[batch, n_ticks, 12] (rpy, position, omegaWorld, vWorld after each tick),
+        wrench float32[batch, n_ticks, 12], status uint32[batch, n_ticks], tau float64[batch, n_ticks, 10], summary int32[batch, 4]."""
+        out = dict(state=np.zeros((batch, n_ticks, 12), dtype=np.float64), wrench=np.zeros((batch, n_ticks, 12), dtype=np.float32),
+                   status=np.zeros((batch, n_ticks), dtype=np.uint32), tau=np.zeros((batch, n_ticks, 10), dtype=np.float64),
+                   summary=np.zeros((batch, 4), dtype=np.int32))
+        _check(self.L.hmpc_download_rollout(self.h, *[out[k].ctypes.data for k in _lib.ROLLOUT_LOG]), "hmpc_download_rollout")
+        return out
+
+    def rollout(self, ticks, n_ticks: int, ticks_per_step: int = 8, subtick0: int = 0, plant=None, device: bool = False, batch: int = 0,
+                dt_mpc: float | None = None, stream: int = 0, instance_mass=None, ext_wrench=None):
+        """``n_ticks`` closed-loop ticks on one stream, nothing leaving the device in between: solve, then plant step, per tick
+        (include/hector_mpc.h hmpc_rollout_device).  ``device=False``: ``ticks`` is a ``TICK_DTYPE`` array; the call uploads it, waits and
+        returns the log of ``download_rollout`` plus ``ticks`` = the tick structs after the last step.  ``device=True``: ``ticks`` is a
+        device pointer to ``batch`` tick structs, advanced in place; the rollout is only enqueued (log: the handle's own buffers, read
+        with ``download_rollout``)."""
+        self.generation += 1
+        dt = self.dt_mpc if dt_mpc is None else float(dt_mpc)
+        if device:
+            p = plant if plant is not None else default_plant()
+            _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(int(ticks)), int(batch), int(n_ticks), dt, int(ticks_per_step), int(subtick0),
+                                              C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+            return None
+        import torch
+
+        ticks = np.ascontiguousarray(ticks, dtype=TICK_DTYPE)
+        nb = ticks.shape[0]
+        p, keep = self._stage_plant(plant, nb, instance_mass, ext_wrench)
+        d_t = torch.from_numpy(ticks.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(d_t.data_ptr()), nb, int(n_ticks), dt, int(ticks_per_step), int(subtick0),
+                                          C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+        out = self.download_rollout(nb, int(n_ticks))
+        del keep
+        out["ticks"] = d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy()
+        return out
 
     def time_solve(self, reps: int, stream: int = 0) -> float:
         ms = C.c_float(0)

@@ -346,6 +346,7 @@ struct hmpc_tick_inputs {
   int flags;              /* HMPC_TICK_* bits (was padding: 0 keeps the previous meaning) */
 };
 #define HMPC_TICK_LEG_Q_MOTOR 1 /* leg_q holds raw motor angles: apply LegController.cpp:111-113's offset first */
+#define HMPC_TICK_FALLEN 2      /* set by the plant step (hmpc_plant_step_device) once the body has tipped over; the builder tests bit 0 only */
 /* f1+f2: builds the packed records of `batch` ticks on the device into the handle's own record buffer (which becomes
  * the current batch) and returns the clamped world_position_desired (ConvexMPCLocomotion.cpp:336-346) per instance.
  * host_ticks / wpd_out are host pointers (wpd_out may be NULL); the _device form takes device pointers and a stream. */
@@ -988,6 +989,122 @@ struct hmpc_command {
 int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks, const struct hmpc_command *device_commands,
                            int group_size, double dtMPC, const double *device_penalty, double *device_wpd_out, double *device_f_ff,
                            double *device_tau, void *stream);
+/* ---- closed loop on the device: plant step, foot placement, tick log (csrc/hmpc_plant.h) ----
+ * hmpc_tick_solve_device takes tick structs in HBM to forces in HBM; hmpc_plant_step_device takes (tick structs, step-0 forces) to the
+ * tick structs of the NEXT tick, in place, and hmpc_rollout_device chains n ticks of both on one stream.  The plant is the single rigid
+ * body the MPC predicts with (SolverMPC.cpp:312-331), integrated semi-implicitly with a quaternion attitude.  Its constants are the
+ * PLANT'S OWN (struct hmpc_plant, binary64), independent of the handle's hmpc_params: the plant may be heavier than the MPC believes,
+ * per instance (device_mass), and may be pushed (device_ext_wrench).  The plant has no legs: leg_q is never changed -- the joint angles
+ * enter the QP only through the foot rotations -- and a stance foot keeps its pFoot bit for bit.
+ *
+ * One launch, one thread per instance, 256 threads per workgroup, nothing synchronised.  ALL arithmetic is binary64, every operation a
+ * correctly rounded IEEE operation (+ - * / sqrt; no contraction), in exactly the order written here; a * b + c * d + e * f below always
+ * means ((a * b) + (c * d)) + (e * f), x cross y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0), vectors are handled component by
+ * component.  Per instance i, tick struct tk:
+ *   If tk.flags & HMPC_TICK_FALLEN: nothing of tk and nothing of its summary row changes.  Otherwise:
+ *   m = device_mass ? device_mass[i] : mass;  (F_ext, tau_ext) = device_ext_wrench ? its row i (force, then torque about the centre of mass,
+ *   world frame) : six times +0.0 (added all the same);  I = inertia, g = gravity.
+ *   u0[0..11] = forces[i * force_stride + 0..11] widened from float: F_L = u0[0..2], F_R = u0[3..5], M_L = u0[6..8], M_R = u0[9..11], world
+ *   frame, applied as they stand whatever the status word (the rule of hmpc_predict_states).
+ *   p = position, v = vWorld, w = omegaWorld, q = orientation (body -> world, scalar first), R = rBody (row-major, world -> body).
+ *   R0 = R as read;  vdw0[a] = R0[a] * v_des_robot[0] + R0[3 + a] * v_des_robot[1] + R0[6 + a] * 0.0,  a = 0, 1   (the builder's expression)
+ *   d = dt_tick / (double)substeps;  hd = 0.5 * d.        Then `substeps` times:
+ *     1.  r_L = pFoot[0..2] - p;  r_R = pFoot[3..5] - p
+ *     2.  tau = ((r_L cross F_L + M_L) + (r_R cross F_R + M_R)) + tau_ext
+ *     3.  F = (F_L + F_R) + F_ext
+ *     4.  tb[k] = R[3k] * tau[0] + R[3k + 1] * tau[1] + R[3k + 2] * tau[2]
+ *     5.  with HMPC_PLANT_GYRO:  wb[k] = R[3k] * w[0] + R[3k + 1] * w[1] + R[3k + 2] * w[2];  Iw[k] = I[k] * wb[k];  tb = tb - (wb cross Iw)
+ *     6.  ab[k] = tb[k] / I[k];  alpha[k] = R[k] * ab[0] + R[3 + k] * ab[1] + R[6 + k] * ab[2]
+ *     7.  a[k] = F[k] / m + (k == 2 ? -g : 0.0)
+ *     8.  w = w + d * alpha
+ *     9.  v = v + d * a
+ *     10. p = p + d * v
+ *     11. with (q0, q1, q2, q3) = q and the NEW w:   e0 = -(w0 * q1 + w1 * q2 + w2 * q3),   e1 = (w0 * q0 + w1 * q3) - w2 * q2,
+ *         e2 = (w1 * q0 + w2 * q1) - w0 * q3,   e3 = (w2 * q0 + w0 * q2) - w1 * q1     ((0, w) (x) q, Hamilton product)
+ *         q[k] = q[k] + hd * e[k];   n = sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);   q[k] = q[k] / n
+ *     12. R = transpose of M(q), the polynomial of orientation_tools.h:182-200:
+ *         M = [ 1 - 2 (q2 q2 + q3 q3),  2 (q1 q2 - q0 q3),      2 (q1 q3 + q0 q2)     ]
+ *             [ 2 (q1 q2 + q0 q3),      1 - 2 (q1 q1 + q3 q3),  2 (q2 q3 - q0 q1)     ]
+ *             [ 2 (q1 q3 - q0 q2),      2 (q2 q3 + q0 q1),      1 - 2 (q1 q1 + q2 q2) ]
+ *   Once per tick, after the sub-steps:
+ *     rpy[0] = det_atan2(2 (q0 q1 + q2 q3), 1 - 2 (q1 q1 + q2 q2));   s = 2 (q0 q2 - q1 q3), s = 0.99999 unless s < 0.99999, rpy[1] = det_asin(s);
+ *     rpy[2] = det_atan2(2 (q0 q3 + q1 q2), 1 - 2 (q2 q2 + q3 q3))     -- the formulas of the solve kernel's quat_to_rpy (SolverMPC.cpp:338-341,
+ *     clamp included) over csrc/hmpc_math.h's deterministic routines.  (rpy is the one output a libm restatement matches to a few ulp only.)
+ *     world_position_desired[a] = base[a] + dt_tick * vdw0[a], base = device_wpd ? device_wpd[2 i + a] (the builder's clamped value,
+ *     ConvexMPCLocomotion.cpp:336-346) : the tick's own -- ConvexMPCLocomotion.cpp:50-54 on the rBody BEFORE the step.
+ *     If advance_gait: gait_iteration = (gait_iteration + 1) % horizon of the handle.
+ *     With HMPC_PLANT_PLACE_FEET, for each leg j that is in swing at step 0 of the NEW gait phase (progress = gait_iteration % horizon -
+ *     gait_offsets[j], + horizon if negative; swing <=> not progress < gait_durations[j] -- GaitGenerator.cpp:85-103), with the NEW p, v, R:
+ *       vdw[a] = R[a] * v_des_robot[0] + R[3 + a] * v_des_robot[1] + R[6 + a] * 0.0;   rh[k] = R[k] * hip[j][0] + R[3 + k] * hip[j][1] + R[6 + k] * hip[j][2]
+ *       Pf[k] = (p[k] + rh[k]) + v[k] * 0.0                                              (swingTimeRemaining = 0)
+ *       rel[a] = ((v[a] * 0.5) * (double)gait_durations[0]) * dtMPC + 0.02 * (v[a] - vdw[a]);   rel[a] = (double)fminf(fmaxf((float)rel[a], (float)-0.4), (float)0.4)
+ *       pFoot[j] = (Pf[0] + rel[0], Pf[1] + rel[1], +0.0)        -- ConvexMPCLocomotion.cpp:148-164, the float narrowing of its clamp kept.
+ *     A leg in stance keeps its pFoot: a foot freezes where it was placed on the tick it touches down.
+ *     If the new R[8] < fall_cos: flags |= HMPC_TICK_FALLEN  (FSM.cpp:78-87).
+ *     Summary row (int32[4], ACCUMULATED, never initialised by the step: start it at {0, -1, 0, 0}):  if the flag was set just now and
+ *     row[1] < 0: row[1] = row[0];  row[0] += 1;  row[2] += 1 when HMPC_STATUS_CODE(status[i]) is neither HMPC_S_OK nor HMPC_S_OK_RELAXED;
+ *     row[3] = max(row[3], HMPC_STATUS_ITERS(status[i])).  So: ticks stepped, first fall tick or -1, ticks not solved, largest iteration count.
+ *
+ * hmpc_plant_step_device: device_ticks = hmpc_tick_inputs[batch] in HBM, advanced in place.  device_forces NULL = the handle's force buffer
+ * with force_stride = 12 * horizon (the argument is ignored then); else force_stride >= 12 floats between instances.  device_status NULL =
+ * the handle's.  device_wpd NULL = the tick's own world_position_desired.  device_summary [batch][4] may be NULL.  Passing forces and
+ * status explicitly makes the step usable without a solve.  HMPC_E_ARG, nothing enqueued: NULL handle, ticks or plant, batch < 0,
+ * substeps < 1, force_stride < 12 with explicit forces, batch > max_batch when the handle's own forces or status are read, a three-contact
+ * handle.  It does not replace the handle's batch. */
+#define HMPC_PLANT_GYRO 1       /* step 5: the gyroscopic term */
+#define HMPC_PLANT_PLACE_FEET 2 /* foot placement for the legs in swing */
+struct hmpc_plant {
+  double dt_tick;      /* 0.005: seconds per tick */
+  double dtMPC;        /* 0.04: seconds per horizon step, read by the foot placement only; hmpc_rollout_device puts its own argument here */
+  int substeps;        /* 1: integrator sub-steps per tick, >= 1 */
+  int advance_gait;    /* 0 or 1: this tick ends a horizon step (hmpc_rollout_device sets it per tick) */
+  int flags;           /* 0: HMPC_PLANT_* bits */
+  int reserved;        /* 0 */
+  double mass;         /* 9 */
+  double inertia[3];   /* (0.5413, 0.5200, 0.0691) */
+  double gravity;      /* 9.81 */
+  double hip[2][3];    /* Biped.h getHipYawLocation: (-0.005, -0.057, -0.126) for leg 0, y negated for leg 1; body frame */
+  double fall_cos;     /* 0.5 */
+  const double *device_mass;        /* NULL, or double[batch] in HBM: overrides `mass` per instance */
+  const double *device_ext_wrench;  /* NULL, or double[batch][6] in HBM: world-frame force, then torque about the centre of mass */
+};
+void hmpc_default_plant(struct hmpc_plant *p);
+int hmpc_plant_step_device(hmpc_handle *h, void *device_ticks, int batch, const struct hmpc_plant *plant, const float *device_forces,
+                           int force_stride, const uint32_t *device_status, const double *device_wpd, int32_t *device_summary,
+                           void *stream);
+/* The log of a rollout: device pointers, each may be NULL (= not logged).  Row (i, k) = instance i, tick k:
+ *   state   [batch][n_ticks][12] double: rpy, position, omegaWorld, vWorld AFTER tick k's plant step
+ *   wrench  [batch][n_ticks][12] float:  the step-0 forces of tick k as the plant read them
+ *   status  [batch][n_ticks]     uint32: the status word of tick k
+ *   tau     [batch][n_ticks][10] double: the joint torques of tick k
+ *   summary [batch][4]           int32:  as in the plant step; initialised to {0, -1, 0, 0} on the stream at the start of the rollout
+ * An instance that has fallen keeps being solved and logged, with its frozen state. */
+struct hmpc_rollout_log {
+  double *state;
+  float *wrench;
+  uint32_t *status;
+  double *tau;
+  int32_t *summary;
+};
+/* n_ticks closed-loop ticks on ONE stream: for k = 0 .. n_ticks - 1 what hmpc_tick_solve_device enqueues, then the plant step (which also
+ * writes row k of the log) with advance_gait = ((subtick0 + k + 1) % ticks_per_step == 0); plant->advance_gait and plant->dtMPC are not
+ * read.  No host synchronisation, no hipGraph, and no hipMalloc after the first call (the clamped world_position_desired and the torques
+ * of a tick go through two small buffers of the handle).  With hmpc_set_tick_warm_start on, the tick after an advance is solved with
+ * horizon_shift = 1 and every other one with 0 -- tick 0 with 0; the handle is left with the shift of the last tick.  With
+ * hmpc_set_device_repair on the plant reads repaired forces.  log == NULL: the handle's own log buffers (hmpc_get_device_rollout, allocated
+ * here on first need); else the caller's, rows as above.  The current batch becomes device_ticks' last tick, as after hmpc_tick_solve_device.
+ * Two-contact handles only.  HMPC_E_ARG, nothing enqueued: n_ticks < 1, ticks_per_step < 1, subtick0 < 0, plant->substeps < 1, a
+ * three-contact handle, batch > max_batch or < 0, a NULL handle, ticks or plant (plant == NULL is NOT the default plant).
+ * hmpc_get_device_rollout: the handle's own log buffers, (re)allocated for max_batch x n_ticks when they hold fewer ticks -- outside the
+ * solve; the pointers stay valid until a call with a larger n_ticks.  hmpc_set_device_rollout: caller-owned buffers for the rollouts that
+ * pass log == NULL (NULL member = the handle's own; log == NULL = all the handle's own).  hmpc_download_rollout waits for the stream of
+ * the last rollout, then copies its log (any pointer may be NULL; a member that was not logged: HMPC_E_ARG); HMPC_E_ARG before the first.
+ * Device groups: per member, through hmpc_group_member. */
+int hmpc_rollout_device(hmpc_handle *h, void *device_ticks, int batch, int n_ticks, double dtMPC, int ticks_per_step, int subtick0,
+                        const struct hmpc_plant *plant, const struct hmpc_rollout_log *log, void *stream);
+int hmpc_set_device_rollout(hmpc_handle *h, const struct hmpc_rollout_log *log);
+int hmpc_get_device_rollout(hmpc_handle *h, int n_ticks, struct hmpc_rollout_log *log);
+int hmpc_download_rollout(hmpc_handle *h, double *state, float *wrench, uint32_t *status, double *tau, int32_t *summary);
 /* copies the current batch's packed records device -> host (parity hook for f1/f2) */
 int hmpc_download_records(hmpc_handle *h, void *host_records);
 
