@@ -130,6 +130,7 @@ __device__ inline bool plant_step_instance(hmpc_tick_inputs &tk, const hmpc_plan
   tk.rpy[0] = det_atan2(2 * (q[0] * q[1] + q[2] * q[3]), 1 - 2 * (q[1] * q[1] + q[2] * q[2]));
   double sp = 2 * (q[0] * q[2] - q[1] * q[3]);
   if (!(sp < 0.99999)) sp = 0.99999;
+  if (sp < -0.99999) sp = -0.99999;  // (two-sided, unlike the solve kernel's quat_to_rpy: rounding takes |sp| past 1 at pitch -90 degrees too)
   tk.rpy[1] = det_asin(sp);
   tk.rpy[2] = det_atan2(2 * (q[0] * q[3] + q[1] * q[2]), 1 - 2 * (q[2] * q[2] + q[3] * q[3]));
 #pragma unroll

@@ -1027,9 +1027,12 @@ int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks
  *             [ 2 (q1 q2 + q0 q3),      1 - 2 (q1 q1 + q3 q3),  2 (q2 q3 - q0 q1)     ]
  *             [ 2 (q1 q3 - q0 q2),      2 (q2 q3 + q0 q1),      1 - 2 (q1 q1 + q2 q2) ]
  *   Once per tick, after the sub-steps:
- *     rpy[0] = det_atan2(2 (q0 q1 + q2 q3), 1 - 2 (q1 q1 + q2 q2));   s = 2 (q0 q2 - q1 q3), s = 0.99999 unless s < 0.99999, rpy[1] = det_asin(s);
- *     rpy[2] = det_atan2(2 (q0 q3 + q1 q2), 1 - 2 (q2 q2 + q3 q3))     -- the formulas of the solve kernel's quat_to_rpy (SolverMPC.cpp:338-341,
- *     clamp included) over csrc/hmpc_math.h's deterministic routines.  (rpy is the one output a libm restatement matches to a few ulp only.)
+ *     rpy[0] = det_atan2(2 (q0 q1 + q2 q3), 1 - 2 (q1 q1 + q2 q2));   s = 2 (q0 q2 - q1 q3), s = 0.99999 unless s < 0.99999,
+ *     then s = -0.99999 if s < -0.99999, rpy[1] = det_asin(s);
+ *     rpy[2] = det_atan2(2 (q0 q3 + q1 q2), 1 - 2 (q2 q2 + q3 q3))     -- the formulas of the solve kernel's quat_to_rpy (SolverMPC.cpp:338-341)
+ *     over csrc/hmpc_math.h's deterministic routines, with the clamp of s made TWO-SIDED: the reference (and the solve kernel, which keeps
+ *     its clamp bit for bit) limits s from above only, and at pitch -90 degrees rounding takes s below -1, where asin is NaN -- a plant that
+ *     is pushed over must not hand NaN to the next solve.  (rpy is the one output a libm restatement matches to a few ulp only.)
  *     world_position_desired[a] = base[a] + dt_tick * vdw0[a], base = device_wpd ? device_wpd[2 i + a] (the builder's clamped value,
  *     ConvexMPCLocomotion.cpp:336-346) : the tick's own -- ConvexMPCLocomotion.cpp:50-54 on the rBody BEFORE the step.
  *     If advance_gait: gait_iteration = (gait_iteration + 1) % horizon of the handle.

@@ -9,6 +9,7 @@ Used by tests/ (and tests/golden/make_caller_golden.py) only.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import tempfile
@@ -19,6 +20,7 @@ from . import ref_py
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_ref", "libcaller_ref.so")
+REFERENCE = os.environ.get("REF", "/root/reference")  # (oracle/Makefile's REF)
 KMAX = ref_py.K_MAX_GAIT_SEGMENTS
 DT_CONTROL, ITERATIONS_BETWEEN_MPC = 0.001, 40  # FSMState_Walking.cpp:5  Cmpc(0.001, 40)
 
@@ -36,8 +38,35 @@ def available() -> bool:
     return os.path.exists(LIB_PATH)
 
 
+STAMP_PATH = LIB_PATH + ".srchash"
+SHIM_PATH = os.path.join(HERE, "caller_ref_shim.cpp")
+
+
+def _shim_hash() -> str:
+    with open(SHIM_PATH, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
+
+
+def _stamp() -> str | None:
+    try:
+        with open(STAMP_PATH) as f:
+            return f.read().strip()
+    except OSError:
+        return None
+
+
 def build() -> None:
-    subprocess.check_call(["make", "-C", HERE, "-s", LIB_PATH])
+    """Builds the library through oracle/Makefile.  A library left by an earlier build is judged by the CONTENT of the shim it was built
+    from (a stamp beside it), not by file times -- a fresh checkout beside an older oracle/_ref gives every source an arbitrary time, and a
+    library without the shim's newest accessor would be kept.  Where the reference's sources are absent the prebuilt file is kept as it is."""
+    want = _shim_hash()
+    if os.path.exists(LIB_PATH) and _stamp() == want:
+        return
+    can_rebuild = os.path.isdir(REFERENCE)
+    subprocess.check_call(["make", "-C", HERE, "-s"] + (["-B"] if can_rebuild and os.path.exists(LIB_PATH) else []) + [LIB_PATH])
+    if can_rebuild:
+        with open(STAMP_PATH, "w") as f:
+            f.write(want + "\n")
 
 
 _lib = None
@@ -46,8 +75,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            build()
+        build()
         L = C.CDLL(LIB_PATH)
         vp = C.c_void_p
         L.refc_create.restype = vp
@@ -65,6 +93,8 @@ def lib():
         L.refc_get_members.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
         L.refc_update_mpc.argtypes = [vp]
         L.refc_run.argtypes = [vp, C.c_int]
+        if hasattr(L, "refc_get_swing_final"):  # (a prebuilt library from before this accessor, kept where the reference is absent)
+            L.refc_get_swing_final.argtypes = [vp, C.c_int, vp, vp]
         L.refc_get_capture.argtypes = [C.POINTER(Capture)]
         L.refc_update_command.argtypes = [vp, vp, vp]
         L.refc_leg_tau_f64.argtypes = [vp, vp, vp]
@@ -171,6 +201,12 @@ class Caller:
     def run(self, gait_number: int):
         with ref_py.quiet():
             lib().refc_run(self.h, int(gait_number))
+
+    def swing_final(self, leg: int):
+        """(the final position run() gave footSwingTrajectories[leg], the swingTimeRemaining[leg] it used)"""
+        pf, rem = np.zeros(3), np.zeros(1)
+        lib().refc_get_swing_final(self.h, int(leg), _p(pf), _p(rem))
+        return pf, float(rem[0])
 
     @staticmethod
     def capture() -> dict:

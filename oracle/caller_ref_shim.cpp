@@ -213,6 +213,13 @@ void refc_run(RefCaller *c, int gaitNumber) {
   c->mpc->run(c->fsm);
 }
 
+// the final position run() handed to footSwingTrajectories[leg] (ConvexMPCLocomotion.cpp:148-166: the foot-placement heuristic's Pf),
+// and the swing time it extrapolated the hip over (swingTimeRemaining[leg])
+void refc_get_swing_final(RefCaller *c, int leg, double *pf3, double *swing_time_remaining) {
+  for (int i = 0; i < 3; ++i) pf3[i] = c->mpc->footSwingTrajectories[leg]._pf[i];
+  if (swing_time_remaining) *swing_time_remaining = c->mpc->swingTimeRemaining[leg];
+}
+
 struct refc_capture {
   int n_setup, n_update, horizon, pad;
   double dt, mu, f_max;

@@ -86,6 +86,7 @@ def plant_step(ticks, plant, horizon, forces, status=None, wpd=None, summary=Non
     q0, q1, q2, q3 = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
     s = 2 * (q0 * q2 - q1 * q3)
     s = np.where(s < 0.99999, s, 0.99999)
+    s = np.where(s < -0.99999, -0.99999, s)
     rpy = np.stack([np.arctan2(2 * (q0 * q1 + q2 * q3), 1 - 2 * (q1 * q1 + q2 * q2)), np.arcsin(s),
                     np.arctan2(2 * (q0 * q3 + q1 * q2), 1 - 2 * (q2 * q2 + q3 * q3))], -1)
     base = t["world_position_desired"] if wpd is None else np.asarray(wpd, dtype=np.float64).reshape(nb, 2)

@@ -80,6 +80,7 @@ static void plain_step(hmpc_tick_inputs &tk, const PlantArgs &a, int i) {
   for (int k = 0; k < 9; ++k) tk.rBody[k] = R[k];
   double sp = 2 * (q0 * q2 - q1 * q3);
   if (!(sp < 0.99999)) sp = 0.99999;
+  if (sp < -0.99999) sp = -0.99999;
   tk.rpy[0] = hmpc::det_atan2(2 * (q0 * q1 + q2 * q3), 1 - 2 * (q1 * q1 + q2 * q2));
   tk.rpy[1] = hmpc::det_asin(sp);
   tk.rpy[2] = hmpc::det_atan2(2 * (q0 * q3 + q1 * q2), 1 - 2 * (q2 * q2 + q3 * q3));
