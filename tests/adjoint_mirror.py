@@ -22,11 +22,16 @@ DENSE_FD = 2 * DENSE_E_MEASURED
 # largest, the factor covering the seed-to-seed spread of the binary32 assembly noise of two independently assembled records (FD_FORCE).
 ADJ_FD_E_MEASURED = 1.10e-5  # (per shape 1.2e-6, 8.2e-8, 1.0e-6, 7.0e-7, 2.8e-8, 3.6e-6, 4.3e-6, 1.1e-5)
 ADJ_FD = 2 * ADJ_FD_E_MEASURED
+# (the irregular gait tables of tests/derived_irregular.py, batches 1, 3, 4: measured by tests/test_derived_irregular_mirror.py, the same factor)
+ADJ_FD_E_MEASURED_IRREGULAR = 8.31e-7  # (per batch 6.3e-7, 3.7e-7, 8.3e-7; left out 1 of 15, none, none)
+ADJ_FD_IRREGULAR = 2 * ADJ_FD_E_MEASURED_IRREGULAR
 # The same for weights and Alpha_K, every entry multiplied by 1 + uniform(-s, s), s = FD_W_STEP halved until at most FD_LEFT_OUT_CAP of
 # the shape is left out: ADJ_FD_W = 2 x the largest E measured; pooled over all kept instances sum|pred - act| / sum|act| < FD_W_POOLED.
 FD_W_STEP = 1e-2
 ADJ_FD_W_E_MEASURED = 7.75e-5  # (per shape 7.0e-6, 4.9e-7, 4.3e-6, 2.4e-6, 1.5e-6, 1.3e-5, 2.7e-5, 7.7e-5; pooled ratio 0.055)
 ADJ_FD_W = 2 * ADJ_FD_W_E_MEASURED
+ADJ_FD_W_E_MEASURED_IRREGULAR = 2.29e-5  # (the irregular gait tables, as above: per batch 5.8e-6, 2.3e-5, 1.9e-5 at s = 1e-2; none left out)
+ADJ_FD_W_IRREGULAR = 2 * ADJ_FD_W_E_MEASURED_IRREGULAR
 FD_W_POOLED = 0.5
 KEYS = ("grad_x0", "grad_traj", "grad_weights", "grad_alpha", "dir", "summary")
 

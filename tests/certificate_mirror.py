@@ -279,6 +279,22 @@ def row_bounds(H32, g32, u, h, nc):
     return (H @ uf + g).reshape(h, 6 * nc), (G_FACTOR * 2.0 ** -24 * mag).reshape(h, 6 * nc), (D_FACTOR * mag).reshape(h, 6 * nc)
 
 
+def g_magnitude(o, weights, traj, h, nc):
+    """M_g[h, U] >= |g|: the magnitude sum of g's own terms, g_k = 2 sum_{i >= k} Phi_{i-k}' S (Apow_{i+1} x0 - traj_i) with every product
+    and difference replaced by the sum of absolute values, from the oracle's binary32 Phi, Apow and x0 widened.  G_FACTOR 2^-24 (sum_j
+    |H_rj||u_j| + M_g_r) bounds the rounding of H32 u + g32 on rows where |H||u| does not carry it: the rows of eliminated variables of a
+    gait table with few stance leg-steps, whose u is 0 at an optimum and whose g is what x - traj leaves after cancelling (D_bound's
+    argument, applied to the binary32 side).  The kappa against it is that of G_bound on regular shapes (<= 3.7 measured)."""
+    Phi, Apow, x0 = (np.asarray(o[key], dtype=np.float64) for key in ("Phi", "Apow", "x0"))
+    w = np.concatenate([np.asarray(weights, dtype=np.float64), [0.0]])
+    tr = np.concatenate([np.abs(np.asarray(traj, dtype=np.float64)).reshape(h, 12), np.zeros((h, 1))], axis=1)
+    mag = np.zeros((h, 6 * nc))
+    for k in range(h):
+        for i in range(k, h):
+            mag[k] += 2.0 * np.abs(Phi[i - k]).T @ (w * (np.abs(Apow[i + 1]) @ np.abs(x0) + tr[i]))
+    return mag
+
+
 def qpoases_primal_dual(oracle, rec_row, h, nc):
     """qpOASES on the reference's reduced QP of one record: (u[h, 6 nc] float64 scattered, y_one_sided[h, nc, 10] >= 0).  qpOASES' y of a
     constraint row is > 0 at its lower side and < 0 at its upper side; the ten one-sided constraints take them by their sigma."""

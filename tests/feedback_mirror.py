@@ -18,6 +18,10 @@ MIRROR_TOL = 1e-9
 FD_STEP = 1e-3
 FD_E_MEASURED = 1.69e-4
 FD_FORCE = 2 * FD_E_MEASURED
+# The same E over the irregular gait tables (tests/derived_irregular.py, batches 1, 2, 4), measured on the CPU against the reference's qpOASES
+# (tests/test_derived_irregular_mirror.py prints it); the same factor.
+FD_E_MEASURED_IRREGULAR = 6.51e-4  # (batch 2, h = 20, 2 of 8 left out; batch 1: 2.5e-5, 1 of 15 left out; batch 4: 4.7e-5, none left out)
+FD_FORCE_IRREGULAR = 2 * FD_E_MEASURED_IRREGULAR
 FD_LEFT_OUT_CAP = 0.25
 
 

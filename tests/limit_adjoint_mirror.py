@@ -35,6 +35,10 @@ DENSE_L_E_MEASURED = 3.74e-5  # (hard_3x, lh; per entry 6.5e-6, 3.1e-7, 8.0e-7, 
 #                               the round-off of the dense KKT solve divided by it is what is seen there)
 DENSE_FC = 2 * DENSE_FC_E_MEASURED
 DENSE_L = 2 * DENSE_L_E_MEASURED
+# The irregular gait tables of tests/derived_irregular.py under random dFc, dbeta: at h = 20 with a flight step the central difference's
+# round-off (which grows as the step falls, see pose_adjoint_mirror) exceeds DENSE_FC at FD_DENSE_STEP by 1 %.  The reference is stepped
+# coarser; the bound stays.
+FD_DENSE_STEP_IRREGULAR = 1e-5
 
 
 def all_cases(cases):
@@ -227,6 +231,12 @@ COVERS = dict(standing="mu lt lh", walking="lt lh", mixed="mu lt lh", single_h20
               hard_3x="mu lt lh", hard_6x="mu lt lh cap")
 
 
+def cover(name, groups):
+    """A batch from outside COVERS (tests/derived_irregular.py) and the groups counted for it, as a string of COVERS' kind."""
+    assert COVERS.setdefault(name, groups) == groups
+    return tuple(groups.split())
+
+
 def groups_of(name, f_max):
     """The groups a batch must cover before anything is compared on it: all four at f_max = 40, COVERS at the default."""
     return GROUPS if f_max == LOW_CAP else tuple(COVERS[name].split())
@@ -333,6 +343,11 @@ FD_L_STEP = 1e-2
 # At most 4 of 16 instances of a batch were left out (standing_cap40 under a moved cap); no batch had to be dropped.
 LADJ_FD_E_MEASURED = dict(mu=1.03e-5, lt=6.90e-7, lh=5.90e-7, cap=9.67e-8)
 LADJ_FD = {g: 2 * e for g, e in LADJ_FD_E_MEASURED.items()}
+# (the irregular gait tables of tests/derived_irregular.py, batches 1, 3, 4: measured by tests/test_derived_irregular_mirror.py, the same factor)
+# mu: batch 1 8.8e-7, batch 4 3.8e-6 (batch 3 has no admitted friction row); lt: 3.7e-7, 7.2e-7, 3.3e-7; lh: 1.2e-7, 1.2e-7, 6.7e-8; cap: batch 1
+# 1.3e-13, batch 4 1.7e-11 (one and three admitted cap rows); none left out anywhere
+LADJ_FD_E_MEASURED_IRREGULAR = dict(mu=3.76e-6, lt=7.19e-7, lh=1.22e-7, cap=1.71e-11)
+LADJ_FD_IRREGULAR = {g: 2 * e for g, e in LADJ_FD_E_MEASURED_IRREGULAR.items()}
 FD_POOLED = am.FD_W_POOLED
 _fdl = {}
 

@@ -22,6 +22,10 @@ DENSE_P_E_MEASURED = 9.38e-7  # (hard_6x, inertia; r: 5.4e-7, 1.9e-7, 1.4e-7, 2.
 #                               it holds the binary32 rounding of the assembled dt Iinv that the chain rules read, ~6e-8 of an entry)
 DENSE_AB = 2 * DENSE_AB_E_MEASURED
 DENSE_P = 2 * DENSE_P_E_MEASURED
+# The irregular gait tables of tests/derived_irregular.py under random dA, dB: l.u* is more strongly curved there and the central
+# difference's truncation, which falls with the square of the step, exceeds DENSE_AB at FD_DENSE_STEP (full_stance_except_one_leg_step at
+# h = 10: 4.2e-5, 4.2e-7, 5.0e-8 at steps of 1e-5, 1e-6, 1e-7).  The reference is stepped finer; the bound stays.
+FD_DENSE_STEP_IRREGULAR = 1e-7
 
 
 def quat_to_R32(q):
@@ -146,6 +150,11 @@ MADJ_FD_R_E_MEASURED = 9.95e-5  # (per shape 7.1e-6, 8.5e-7, 5.6e-6, 2.8e-6, 1.4
 MADJ_FD_P_E_MEASURED = 7.29e-5  # (per shape 9.4e-6, 3.7e-7, 3.8e-6, 1.4e-6, 6.0e-7, 1.5e-5, 1.5e-5, 7.3e-5 at s = 1e-2; pooled ratio 0.074)
 MADJ_FD_R = 2 * MADJ_FD_R_E_MEASURED
 MADJ_FD_P = 2 * MADJ_FD_P_E_MEASURED
+# (the irregular gait tables of tests/derived_irregular.py, batches 1, 3, 4: measured by tests/test_derived_irregular_mirror.py, the same factor)
+MADJ_FD_R_E_MEASURED_IRREGULAR = 1.08e-5  # (per batch 4.9e-6, 4.3e-6, 1.1e-5; left out none, 1 of 4, none)
+MADJ_FD_P_E_MEASURED_IRREGULAR = 1.83e-5  # (per batch 3.6e-6, 1.8e-5, 1.4e-5; none left out)
+MADJ_FD_R_IRREGULAR = 2 * MADJ_FD_R_E_MEASURED_IRREGULAR
+MADJ_FD_P_IRREGULAR = 2 * MADJ_FD_P_E_MEASURED_IRREGULAR
 FD_POOLED = am.FD_W_POOLED
 _fdm = {}
 

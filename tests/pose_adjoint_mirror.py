@@ -366,6 +366,10 @@ DENSE_ROUTE_E_MEASURED = 2.57e-6  # (hard_6x; 2.0e-7, 3.1e-8, 2.1e-7, 2.6e-7, 2.
 DENSE_JA_E_MEASURED = 3.59e-6  # (hard_6x; 3.9e-7, 6.8e-8, 2.4e-7, 4.7e-7, 8.2e-9, 8.2e-7, 3.5e-6, 3.58e-6; cap40: 3.2e-7, 7.7e-8, 6.0e-7)
 DENSE_FRAMES_E_MEASURED = 4.03e-6  # (hard_6x; 1.0e-6, 1.0e-7, 3.9e-7, 7.1e-7, 4.9e-8, 1.3e-6, 1.7e-6, 4.02e-6; cap40: 7.7e-7, 7.7e-8, 8.8e-7)
 DENSE_Q, DENSE_ROUTE, DENSE_JA, DENSE_FRAMES = (2 * v for v in (DENSE_Q_E_MEASURED, DENSE_ROUTE_E_MEASURED, DENSE_JA_E_MEASURED, DENSE_FRAMES_E_MEASURED))
+# The irregular gait tables of tests/derived_irregular.py under q and the joint angles: the central difference's round-off grows as the
+# step falls (q on flight_in_the_middle at h = 20: 3.6e-6, 3.5e-5, 1.8e-4 at steps of 1e-5, 1e-6, 1e-7) and exceeds DENSE_Q and DENSE_ROUTE
+# at FD_DENSE_STEP.  The reference is stepped coarser; the bounds stay.
+FD_DENSE_STEP_IRREGULAR = 1e-5
 
 # What each batch must hold before anything is compared on it: admitted active rows among j' = 4 .. 7 (rows 4 .. 6 of a leg-step: the
 # only rows the foot frames enter) and a non-zero grad_B[6:9]; a batch that holds neither would pass on zeros.  Counted on the CPU at
@@ -405,6 +409,9 @@ def assert_pose_covered(rows_list, grad_B, what=""):
 FD_POSE_STEP = dict(q=1e-2, ja=1e-3)
 PADJ_FD_E_MEASURED = dict(q=7.62e-5, ja=4.33e-7)
 PADJ_FD = {g: 2 * e for g, e in PADJ_FD_E_MEASURED.items()}
+# (the irregular gait tables of tests/derived_irregular.py, batches 1, 3, 4: measured by tests/test_derived_irregular_mirror.py, the same factor)
+PADJ_FD_E_MEASURED_IRREGULAR = dict(q=1.22e-5, ja=8.91e-8)  # (per batch q 3.4e-6, 9.2e-6, 1.2e-5; ja 1.0e-8, 7.8e-8, 8.9e-8; none left out)
+PADJ_FD_IRREGULAR = {g: 2 * e for g, e in PADJ_FD_E_MEASURED_IRREGULAR.items()}
 FD_POOLED = am.FD_W_POOLED
 FD_GROUPS = ("q", "ja")
 _fdp = {}

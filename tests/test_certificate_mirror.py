@@ -36,6 +36,16 @@ def reference_case(oracle, case):
     return _cache[name]
 
 
+def enter_case(name, build, left_out_cap=0.0):
+    """A case from outside CASES (tests/derived_irregular.py): build() gives its reference_case dict, once; the multiplier check's cap for
+    it is left_out_cap.  From then on reference_case -- and every helper built on it -- takes the case's tuple."""
+    assert name not in CASE_IDS
+    LEFT_OUT_CAP.setdefault(name, left_out_cap)
+    if name not in _cache:
+        _cache[name] = build()
+    return _cache[name]
+
+
 def leg_step_bound(G_bound, i, c, nc):
     return float(G_bound[i, cm.cols(c, nc)].max())
 

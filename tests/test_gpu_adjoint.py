@@ -23,7 +23,8 @@ from test_margins_mirror import PARAM_SET_0
 pytestmark = pytest.mark.gpu
 E_ARG = -1
 GRADS = ("grad_x0", "grad_traj", "grad_weights", "grad_alpha", "dir")
-# the gains' three small shapes, beside those of CASES (which hold h = 20 single support, three contacts at h = 10 and a walking gait)
+# the gains' three small shapes, beside those of CASES (which hold h = 20 single support, three contacts at h = 10 and a walking gait);
+# what the gait TABLE indexes (flight steps, swinging first contacts, a swinging hand, n = 0, the wide shape): tests/test_gpu_derived_irregular.py
 SMALL = [("h1", "standing", 1, 8, 2, 201), ("h3", "walking", 3, 8, 2, 202), ("h11", "walking", 11, 8, 2, 203)]
 
 _cache = {}

@@ -46,9 +46,10 @@ def dense_limits(oracle, d, un, k, h, nc):
 
 
 @pytest.mark.parametrize("entry", ALL_CASES, ids=ALL_IDS)
-def test_grad_Fc_and_grad_bound_are_the_dense_models_derivatives(oracle, entry):
+def test_grad_Fc_and_grad_bound_are_the_dense_models_derivatives(oracle, entry, step=lam.FD_DENSE_STEP):
     """Central differences of l.u* under random dFc (inside each row's cols(c)) and random dbeta against <grad_Fc, dFc> + <grad_bound,
-    dbeta>, within DENSE_FC of max(1, |value|); dFc alone and dbeta alone as well, so that neither hides behind the other."""
+    dbeta>, within DENSE_FC of max(1, |value|); dFc alone and dbeta alone as well, so that neither hides behind the other.  (step: the central difference's; the irregular gait tables of
+    tests/derived_irregular.py need a larger one, see limit_adjoint_mirror.FD_DENSE_STEP_IRREGULAR.)"""
     name, case, f_max = entry
     h, nb, nc = case[2], case[3], case[4]
     d = limit_case(oracle, entry)
@@ -61,7 +62,7 @@ def test_grad_Fc_and_grad_bound_are_the_dense_models_derivatives(oracle, entry):
         dl = dense_limits(oracle, d, un, k, h, nc)
         dFc, dbeta = lam.random_dFc(rng, nc), rng.uniform(-1.0, 1.0, (h, nc, 10))
         for a, b in ((dFc, dbeta), (dFc, None), (None, dbeta)):
-            want = dl.central(d["ell"][k], a, b)
+            want = dl.central(d["ell"][k], a, b, step=step)
             got = (0.0 if a is None else (g["grad_Fc"][k] * a).sum()) + (0.0 if b is None else (g["grad_bound"][k] * b).sum())
             worst = max(worst, abs(got - want) / max(1.0, abs(want)))
     print(name, "directional derivatives in Fc, beta against central differences / max(1, |value|)", worst, "DENSE_FC", lam.DENSE_FC)

@@ -30,9 +30,10 @@ def moved_model(base, un, k):
 
 
 @pytest.mark.parametrize("case", [c[1] for c in CASES], ids=CASE_IDS)
-def test_grad_A_and_grad_B_are_the_dense_models_derivatives(oracle, case):
+def test_grad_A_and_grad_B_are_the_dense_models_derivatives(oracle, case, step=mam.FD_DENSE_STEP):
     """Central differences of l.u* under random dA, dB against <G_A, dA> + <G_B, dB>, within DENSE_AB of max(1, |value|); dA alone and dB
-    alone as well, so that neither hides behind the other."""
+    alone as well, so that neither hides behind the other.  (step: the central difference's; the irregular gait tables of
+    tests/derived_irregular.py need a smaller one, see model_adjoint_mirror.FD_DENSE_STEP_IRREGULAR.)"""
     name, h, nb, nc = case[0], case[2], case[3], case[4]
     base, d, g = mirror_case(oracle, case), adjoint_case(oracle, case), model_case(oracle, case)
     un = records.unpack_records(base["rec"], h, nc)
@@ -45,7 +46,7 @@ def test_grad_A_and_grad_B_are_the_dense_models_derivatives(oracle, case):
         #  of 1e-4 was measured there, which falls with the square of the step)
         dA, dB = rng.uniform(-1.0, 1.0, (13, 13)), rng.uniform(-1.0, 1.0, (13, 6 * nc)) * float(base["m"]["Bcd"][k][9, 0])
         for a, b in ((dA, dB), (dA, None), (None, dB)):
-            want = mm.central(d["ell"][k], a, b)
+            want = mm.central(d["ell"][k], a, b, step=step)
             got = (0.0 if a is None else (g["grad_A"][k] * a).sum()) + (0.0 if b is None else (g["grad_B"][k] * b).sum())
             worst = max(worst, abs(got - want) / max(1.0, abs(want)))
     print(name, "directional derivatives in Acd, Bcd against central differences / max(1, |value|)", worst, "DENSE_AB", mam.DENSE_AB)

@@ -58,9 +58,11 @@ def route_mirror(p, oracle, un, k, h, nc, keep):
 
 
 @pytest.mark.parametrize("entry", ALL_CASES, ids=ALL_IDS)
-def test_q_and_joint_angles_are_the_dense_models_derivatives(oracle, entry):
+def test_q_and_joint_angles_are_the_dense_models_derivatives(oracle, entry, step=pm.FD_DENSE_STEP):
     """Central differences of l.u* under q (each component, a random direction; the routes x0, Acd, Bcd + Fc each alone under that
-    direction) and under every joint angle, pushed through stage_a64, against grad_record's q and joint-angle slices."""
+    direction) and under every joint angle, pushed through stage_a64, against grad_record's q and joint-angle slices.
+    (step: the central difference's; the irregular gait tables of tests/derived_irregular.py need a larger one, see
+    pose_adjoint_mirror.FD_DENSE_STEP_IRREGULAR.)"""
     name, case, f_max = entry
     h, nb, nc = case[2], case[3], case[4]
     p = pose_case(oracle, entry)
@@ -79,13 +81,13 @@ def test_q_and_joint_angles_are_the_dense_models_derivatives(oracle, entry):
         dirs = [np.eye(4)[i] for i in range(4)] + [rng.uniform(-1.0, 1.0, 4)]
         sq = max(1.0, np.abs(gq).max())
         for dq in dirs:
-            eq = max(eq, abs(gq @ dq - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dq=dq)) / sq)
+            eq = max(eq, abs(gq @ dq - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dq=dq, step=step)) / sq)
         for routes, keep in (("x0", ("grad_x0",)), ("A", ("grad_A",)), ("B Fc", ("grad_B", "grad_Fc"))):
             gr = route_mirror(p, oracle, un, k, h, nc, keep)["grad_record"][sl["q"]]
-            er = max(er, abs(gr @ dirs[4] - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dq=dirs[4], routes=routes)) / sq)
+            er = max(er, abs(gr @ dirs[4] - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dq=dirs[4], routes=routes, step=step)) / sq)
         sj = max(1.0, np.abs(gj).max())
         for i in range(10):
-            ej = max(ej, abs(gj[i] - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dja=np.eye(10)[i], routes="Fc")) / sj)
+            ej = max(ej, abs(gj[i] - central(dp, d["ell"][k], base64, q, ja, Rh, r, nc, dja=np.eye(10)[i], routes="Fc", step=step)) / sj)
     print(name, "q", eq, "routes of q alone", er, "joint angles", ej, "bounds", pm.DENSE_Q, pm.DENSE_ROUTE, pm.DENSE_JA,
           "max|grad q|", float(np.abs(g["grad_record"][:, sl["q"]]).max()), "max|grad ja|", float(np.abs(g["grad_record"][:, sl["joint_angles"]]).max()))
     assert eq <= pm.DENSE_Q and er <= pm.DENSE_ROUTE and ej <= pm.DENSE_JA, (eq, er, ej)
