@@ -45,6 +45,8 @@ EXPORTS = [
     "hmpc_adjoint_chain_multi", "hmpc_set_device_adjoint_chain_multi", "hmpc_get_device_adjoint_chain_multi", "hmpc_download_adjoint_chain_multi",
     "hmpc_default_plant", "hmpc_plant_step_device", "hmpc_rollout_device", "hmpc_set_device_rollout", "hmpc_get_device_rollout",
     "hmpc_download_rollout",
+    "hmpc_default_rollout_cost", "hmpc_rollout_score_device", "hmpc_rollout_select_device", "hmpc_rollout_sweep_device",
+    "hmpc_get_device_rollout_sweep",
 ]
 
 
@@ -90,6 +92,20 @@ ROLLOUT_LOG = ("state", "wrench", "status", "tau", "summary")
 class RolloutLog(C.Structure):
     """include/hector_mpc.h struct hmpc_rollout_log (device pointers of a rollout's log; each may be NULL)."""
     _fields_ = [(k, C.c_void_p) for k in ROLLOUT_LOG]
+
+
+class RolloutCost(C.Structure):
+    """include/hector_mpc.h struct hmpc_rollout_cost (the weights of hmpc_rollout_score_device; hmpc_default_rollout_cost fills the defaults)."""
+    _fields_ = [("w_state", C.c_double * 12), ("w_terminal", C.c_double * 12), ("w_wrench", C.c_double * 12), ("w_tau", C.c_double * 10),
+                ("height", C.c_double), ("dt_tick", C.c_double), ("fall_penalty", C.c_double), ("unsolved_penalty", C.c_double)]
+
+
+ROLLOUT_CHOICE = ("index", "score", "wrench", "tau", "summary")
+
+
+class RolloutChoice(C.Structure):
+    """include/hector_mpc.h struct hmpc_rollout_choice (device pointers of a rollout selection's outputs; each may be NULL)."""
+    _fields_ = [(k, C.c_void_p) for k in ROLLOUT_CHOICE]
 
 
 class Command(C.Structure):
@@ -292,6 +308,13 @@ def load():
     L.hmpc_set_device_rollout.argtypes = [vp, C.POINTER(RolloutLog)]
     L.hmpc_get_device_rollout.argtypes = [vp, ci, C.POINTER(RolloutLog)]
     L.hmpc_download_rollout.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hmpc_default_rollout_cost.argtypes = [C.POINTER(RolloutCost)]
+    L.hmpc_default_rollout_cost.restype = None
+    L.hmpc_rollout_score_device.argtypes = [vp, vp, ci, ci, C.POINTER(RolloutCost), C.POINTER(RolloutLog), vp, vp, vp]
+    L.hmpc_rollout_select_device.argtypes = [vp, vp, vp, ci, ci, C.POINTER(RolloutLog), C.POINTER(RolloutChoice), vp]
+    L.hmpc_rollout_sweep_device.argtypes = [vp, vp, ci, vp, ci, ci, cd, ci, ci, C.POINTER(Plant), C.POINTER(RolloutCost), vp,
+                                            C.POINTER(RolloutChoice), vp]
+    L.hmpc_get_device_rollout_sweep.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

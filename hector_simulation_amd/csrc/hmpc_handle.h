@@ -169,6 +169,13 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   int roll_own_ticks = 0;
   hmpc_rollout_log roll_caller{}, roll_last{};
   int roll_last_batch = 0, roll_last_ticks = 0;
+  // closed-loop command sweeps (hmpc_rollout_sweep_device, hmpc_rollout_score.hip): the expanded ticks the rollout advances and their copy
+  // from before it (each hmpc_tick_inputs[max_batch]: not the shared scratch, they outlive n solves), cost [max_batch][4] and score
+  // [max_batch]; allocated by the first sweep.  rsw_batch = the instances of the last sweep (0: none yet).  rscore_batch, rscore_ticks =
+  // the shape of the log hmpc_rollout_score_device scored last (what hmpc_rollout_select_device takes a caller's log to have)
+  DeviceBuffer<unsigned char> d_rsw_ticks, d_rsw_ticks0;
+  DeviceBuffer<double> d_rsw_cost, d_rsw_score;
+  int rsw_batch = 0, rscore_batch = 0, rscore_ticks = 0;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 

@@ -42,6 +42,19 @@ def default_plant(**fields):
     return p
 
 
+def default_rollout_cost(**fields):
+    """``struct hmpc_rollout_cost`` with the defaults of ``hmpc_default_rollout_cost``; keyword arguments overwrite the scalar fields (height,
+    dt_tick, fall_penalty, unsolved_penalty) and the weight vectors ``w_state``, ``w_terminal``, ``w_wrench`` (12 values each), ``w_tau`` (10)."""
+    c = _lib.RolloutCost()
+    _lib.load().hmpc_default_rollout_cost(C.byref(c))
+    for k, v in fields.items():
+        if k.startswith("w_"):
+            getattr(c, k)[:] = [float(x) for x in v]
+        else:
+            setattr(c, k, float(v))
+    return c
+
+
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "too_large", 4: "kkt", 5: "working_set_full", 6: "ok_relaxed", 7: "sweep_mismatch", 8: "hessian_not_positive_definite", 9: "regularisation_step"}
 
 
@@ -830,6 +843,171 @@ class BatchedMPC:
         out = self.download_rollout(nb, int(n_ticks))
         del keep
         out["ticks"] = d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy()
+        return out
+
+    # ---- closed-loop command sweeps (include/hector_mpc.h hmpc_rollout_score_device / _select_device / _sweep_device)
+    def _stage_log(self, log: dict, batch: int, n_ticks: int):
+        """``struct hmpc_rollout_log`` over HBM copies of the host arrays of ``log`` (a missing or ``None`` member stays NULL); + the copies."""
+        import torch
+
+        lg, keep = _lib.RolloutLog(), {}
+        shapes = dict(state=(np.float64, (batch, n_ticks, 12)), wrench=(np.float32, (batch, n_ticks, 12)), status=(np.int32, (batch, n_ticks)),
+                      tau=(np.float64, (batch, n_ticks, 10)), summary=(np.int32, (batch, 4)))
+        for k, (dt, shape) in shapes.items():
+            a = log.get(k)
+            if a is None:
+                continue
+            if k == "status":
+                a = np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
+            keep[k] = torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape).copy()).cuda(self.device)
+            setattr(lg, k, keep[k].data_ptr())
+        return lg, keep
+
+    def rollout_score(self, ticks0, log=None, cost=None, device: bool = False, batch: int = 0, n_ticks: int = 0, cost_ptr: int = 0,
+                      score_ptr: int = 0, stream: int = 0):
+        """The cost of every instance's rollout log (include/hector_mpc.h hmpc_rollout_score_device).  ``ticks0``: the tick structs AS THEY
+        WERE BEFORE the rollout; ``cost``: a ``default_rollout_cost()`` (``None``: the defaults).  ``device=False``: ``ticks0`` is a
+        ``TICK_DTYPE`` array and ``log`` a dict of host arrays -- ``state`` float64[batch, n_ticks, 12], and optionally ``wrench``, ``tau``,
+        ``summary`` as ``download_rollout`` returns them (a missing member is not scored) -- or ``None`` for the log of the handle's last
+        rollout (pass its ``n_ticks``); everything is staged through HBM and the call waits: returns ``dict(cost=float64[batch, 4] (tracking,
+        effort, terminal, penalty), score=float64[batch])``.  ``device=True``: ``ticks0``, ``cost_ptr``, ``score_ptr`` are device pointers,
+        ``log`` a ``_lib.RolloutLog`` or ``None``, ``batch`` and ``n_ticks`` as in C; the launch is only enqueued."""
+        c = cost if cost is not None else default_rollout_cost()
+        if device:
+            _check(self.L.hmpc_rollout_score_device(self.h, C.c_void_p(int(ticks0)), int(batch), int(n_ticks), C.byref(c),
+                                                    C.byref(log) if log is not None else None, C.c_void_p(int(cost_ptr or 0)),
+                                                    C.c_void_p(int(score_ptr or 0)), C.c_void_p(stream)), "hmpc_rollout_score_device")
+            return None
+        import torch
+
+        ticks0 = np.ascontiguousarray(ticks0, dtype=TICK_DTYPE)
+        nb = ticks0.shape[0]
+        keep = None
+        if log is not None:
+            n_ticks = int(np.asarray(log["state"]).shape[1])
+            lg, keep = self._stage_log(log, nb, n_ticks)
+        d_t = torch.from_numpy(ticks0.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
+        d_c = torch.zeros((nb, 4), dtype=torch.float64, device=d_t.device)
+        d_s = torch.zeros((nb,), dtype=torch.float64, device=d_t.device)
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_rollout_score_device(self.h, C.c_void_p(d_t.data_ptr()), nb, int(n_ticks), C.byref(c),
+                                                C.byref(lg) if log is not None else None, C.c_void_p(d_c.data_ptr()),
+                                                C.c_void_p(d_s.data_ptr()), C.c_void_p(stream)), "hmpc_rollout_score_device")
+        torch.cuda.synchronize(self.device)
+        del keep
+        return dict(cost=d_c.cpu().numpy(), score=d_s.cpu().numpy())
+
+    def _choice_buffers(self, groups: int, members):
+        """``struct hmpc_rollout_choice`` over fresh HBM buffers for the ``members`` asked for; + the buffers."""
+        import torch
+
+        shapes = dict(index=(torch.int32, (groups,)), score=(torch.float64, (groups,)), wrench=(torch.float32, (groups, 12)),
+                      tau=(torch.float64, (groups, 10)), summary=(torch.int32, (groups, 4)))
+        ch, bufs = _lib.RolloutChoice(), {}
+        for k in members:
+            bufs[k] = torch.zeros(shapes[k][1], dtype=shapes[k][0], device=f"cuda:{self.device}")
+            setattr(ch, k, bufs[k].data_ptr())
+        return ch, bufs
+
+    def rollout_select(self, score, group_size: int, penalty=None, log=None, device: bool = False, batch: int = 0, choice=None,
+                       stream: int = 0):
+        """The cheapest instance of every group of ``group_size`` consecutive instances (include/hector_mpc.h hmpc_rollout_select_device):
+        ``score + penalty`` where finite, ties to the lowest index.  ``device=False``: ``score`` float64[batch], ``penalty`` float64[batch] or
+        ``None``, ``log`` a dict of host arrays as for ``rollout_score`` -- it must be the log the last ``rollout_score`` scored -- or
+        ``None`` for the log of the handle's last rollout; the call waits and returns ``dict(index=int32[groups] (-1: no winner),
+        score=float64[groups])`` plus, for every member the log has, the winner's ``wrench`` float32[groups, 12] and ``tau``
+        float64[groups, 10] of tick 0 and its ``summary`` int32[groups, 4].  ``device=True``: ``score``, ``penalty`` device pointers, ``log``
+        a ``_lib.RolloutLog`` or ``None``, ``choice`` a ``_lib.RolloutChoice`` of device pointers; the launch is only enqueued."""
+        if device:
+            _check(self.L.hmpc_rollout_select_device(self.h, C.c_void_p(int(score)), C.c_void_p(int(penalty or 0)), int(batch), int(group_size),
+                                                     C.byref(log) if log is not None else None, C.byref(choice), C.c_void_p(stream)),
+                   "hmpc_rollout_select_device")
+            return None
+        import torch
+
+        score = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        nb = score.shape[0]
+        if group_size < 1 or nb % group_size:
+            raise ValueError("group_size must divide the batch")
+        keep, members = None, list(_lib.ROLLOUT_CHOICE)
+        if log is not None:
+            lg, keep = self._stage_log(log, nb, int(np.asarray(log["state"]).shape[1]))
+            members = ["index", "score"] + [k for k in ("wrench", "tau", "summary") if k in keep]
+        ch, bufs = self._choice_buffers(nb // group_size, members)
+        d_s = torch.from_numpy(score.copy()).cuda(self.device)
+        d_p = None if penalty is None else torch.from_numpy(np.ascontiguousarray(penalty, dtype=np.float64).reshape(nb).copy()).cuda(self.device)
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_rollout_select_device(self.h, C.c_void_p(d_s.data_ptr()), C.c_void_p(0 if d_p is None else d_p.data_ptr()), nb,
+                                                 int(group_size), C.byref(lg) if log is not None else None, C.byref(ch), C.c_void_p(stream)),
+               "hmpc_rollout_select_device")
+        torch.cuda.synchronize(self.device)
+        del keep
+        return {k: v.cpu().numpy() for k, v in bufs.items()}
+
+    def _device_bytes(self, ptr: int, nbytes: int) -> np.ndarray:
+        """``nbytes`` bytes of HBM at ``ptr`` (a buffer of the handle's) as a host array: torch views the pointer and copies it down."""
+        import torch
+
+        class _View:
+            __cuda_array_interface__ = dict(shape=(int(nbytes),), typestr="|u1", data=(int(ptr), False), strides=None, version=2)
+
+        return torch.as_tensor(_View(), device=f"cuda:{self.device}").cpu().numpy()
+
+    def get_device_rollout_sweep(self) -> dict:
+        """Device pointers of the handle's buffers of the last ``rollout_sweep``: ``ticks`` (the expanded tick structs after the rollout),
+        ``cost`` [instances, 4], ``score`` [instances]."""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(self.L.hmpc_get_device_rollout_sweep(self.h, *[C.byref(x) for x in p]), "hmpc_get_device_rollout_sweep")
+        return dict(zip(("ticks", "cost", "score"), [x.value for x in p]))
+
+    def rollout_sweep(self, ticks, commands, n_ticks: int, ticks_per_step: int = 8, subtick0: int = 0, plant=None, cost=None, penalty=None,
+                      device: bool = False, n_states: int = 0, group_size: int = 0, choice=None, dt_mpc: float | None = None,
+                      stream: int = 0, instance_mass=None, ext_wrench=None):
+        """Every robot state rolled out in closed loop under each of its candidate commands, scored and the best picked, nothing leaving
+        the device in between (include/hector_mpc.h hmpc_rollout_sweep_device).  ``device=False``: ``ticks`` is a ``TICK_DTYPE`` array
+        [n_states], ``commands`` a ``COMMAND_DTYPE`` array [n_states, K], ``penalty`` float64[n_states * K] or ``None``, ``instance_mass`` /
+        ``ext_wrench`` per EXPANDED instance; the call waits and returns the dict of ``rollout_select`` (``index``, ``score``, ``wrench``,
+        ``tau``, ``summary`` per state) plus ``cost`` float64[n_states * K, 4], ``all_scores`` float64[n_states * K], ``ticks`` (the expanded
+        tick structs after the rollout), ``log`` (``download_rollout``) and ``ticks_in`` (the robot states read back from the device: the
+        sweep does not modify them).  ``device=True``: ``ticks``, ``commands``, ``penalty`` are
+        device pointers, ``n_states`` and ``group_size`` as in C, ``choice`` a ``_lib.RolloutChoice``; the chain is only enqueued."""
+        self.generation += 1
+        dt = self.dt_mpc if dt_mpc is None else float(dt_mpc)
+        c = cost if cost is not None else default_rollout_cost()
+        if device:
+            p = plant if plant is not None else default_plant()
+            _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(int(ticks)), int(n_states), C.c_void_p(int(commands)), int(group_size),
+                                                    int(n_ticks), dt, int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
+                                                    C.c_void_p(int(penalty or 0)), C.byref(choice), C.c_void_p(stream)),
+                   "hmpc_rollout_sweep_device")
+            return None
+        import torch
+
+        ticks = np.ascontiguousarray(ticks, dtype=TICK_DTYPE)
+        ns = ticks.shape[0]
+        commands = np.ascontiguousarray(commands, dtype=COMMAND_DTYPE).reshape(ns, -1)
+        K = commands.shape[1]
+        nb = ns * K
+        p, keep = self._stage_plant(plant, nb, instance_mass, ext_wrench)
+        d_t = torch.from_numpy(ticks.view(np.uint8).reshape(ns, -1).copy()).cuda(self.device)
+        d_c = torch.from_numpy(commands.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
+        d_p = None if penalty is None else torch.from_numpy(np.ascontiguousarray(penalty, dtype=np.float64).reshape(nb).copy()).cuda(self.device)
+        ch, bufs = self._choice_buffers(ns, _lib.ROLLOUT_CHOICE)
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(d_t.data_ptr()), ns, C.c_void_p(d_c.data_ptr()), K, int(n_ticks), dt,
+                                                int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
+                                                C.c_void_p(0 if d_p is None else d_p.data_ptr()), C.byref(ch), C.c_void_p(stream)),
+               "hmpc_rollout_sweep_device")
+        log = self.download_rollout(nb, int(n_ticks))  # (waits for the stream)
+        torch.cuda.synchronize(self.device)
+        del keep
+        out = {k: v.cpu().numpy() for k, v in bufs.items()}
+        own = self.get_device_rollout_sweep()
+        out["ticks"] = self._device_bytes(own["ticks"], nb * TICK_DTYPE.itemsize).view(TICK_DTYPE).copy()
+        out["cost"] = self._device_bytes(own["cost"], nb * 32).view(np.float64).reshape(nb, 4).copy()
+        out["all_scores"] = self._device_bytes(own["score"], nb * 8).view(np.float64).copy()
+        out["log"] = log
+        out["ticks_in"] = d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy()
         return out
 
     def time_solve(self, reps: int, stream: int = 0) -> float:

@@ -1108,6 +1108,96 @@ int hmpc_rollout_device(hmpc_handle *h, void *device_ticks, int batch, int n_tic
 int hmpc_set_device_rollout(hmpc_handle *h, const struct hmpc_rollout_log *log);
 int hmpc_get_device_rollout(hmpc_handle *h, int n_ticks, struct hmpc_rollout_log *log);
 int hmpc_download_rollout(hmpc_handle *h, double *state, float *wrench, uint32_t *status, double *tau, int32_t *summary);
+/* ---- closed-loop command sweeps: score rollouts, pick the best on the device (csrc/hmpc_rollout_score.h) ----
+ * hmpc_rollout_device leaves a log; hmpc_rollout_score_device turns the log of every instance into a cost, hmpc_rollout_select_device picks
+ * the cheapest instance of every group of consecutive instances, and hmpc_rollout_sweep_device chains expansion (robot states x candidate
+ * commands), rollout, score and selection on one stream: "which command keeps it up over the next second" without the log leaving the device.
+ *
+ * THE SCORE.  One launch, one wave of 64 lanes per instance, four waves per workgroup, nothing synchronised, nothing allocated.  ALL
+ * arithmetic is binary64, every operation a correctly rounded IEEE operation (+ - * / and rint, ties to even; no contraction), in exactly the
+ * order written here; a * b + c * d + e * f means ((a * b) + (c * d)) + (e * f).  W = 64 is a constant of this definition (not of the
+ * hardware), TWO_PI = 6.283185307179586.  Per instance i, with tk = ticks0[i] -- the tick struct AS IT WAS BEFORE THE ROLLOUT (the rollout
+ * advances its ticks in place: score against a copy) --, c = the hmpc_rollout_cost, n = n_ticks, and the log's rows (i, k):
+ *   R0 = tk.rBody;   vdw[a] = R0[a] * tk.v_des_robot[0] + R0[3 + a] * tk.v_des_robot[1] + R0[6 + a] * 0.0,  a = 0, 1   (the builder's expression)
+ *   Row k, k = 0 .. n - 1:
+ *     t = (double)(k + 1) * c.dt_tick
+ *     ref = (tk.roll_des, tk.pitch_des, tk.rpy[2] + t * tk.yaw_rate_des, tk.position[0] + t * vdw[0], tk.position[1] + t * vdw[1], c.height,
+ *            0.0, 0.0, tk.yaw_rate_des, vdw[0], vdw[1], 0.0)          (the columns of the log's state row: rpy, position, omegaWorld, vWorld)
+ *     e[s] = state[i][k][s] - ref[s],  s = 0 .. 11;   then for s = 2 only:  e[2] = e[2] - TWO_PI * rint(e[2] / TWO_PI)
+ *     trk_k = +0.0, then for s = 0 .. 11 in this order:  trk_k = trk_k + (c.w_state[s] * e[s]) * e[s]
+ *     eff_k = +0.0, then, when log.wrench is not NULL, for j = 0 .. 11:  u = (double)wrench[i][k][j];  eff_k = eff_k + (c.w_wrench[j] * u) * u
+ *             then, when log.tau is not NULL, for j = 0 .. 9:  u = tau[i][k][j];  eff_k = eff_k + (c.w_tau[j] * u) * u
+ *   Sums over the ticks, the same for trk (giving cost[0], tracking) and eff (giving cost[1], effort):
+ *     P[l] = +0.0 for l = 0 .. W - 1;   for k = 0 .. n - 1 in ascending order:  P[k % W] = P[k % W] + trk_k      (a lane without a tick keeps +0.0)
+ *     for off = 32, 16, 8, 4, 2, 1:   P'[l] = P[l] + P[l ^ off] for every l at once, then P = P'
+ *     cost = P[0]      (IEEE addition is commutative, so every P[l] ends with the same bits)
+ *   cost[2] = +0.0, then for s = 0 .. 11:  cost[2] = cost[2] + (c.w_terminal[s] * e[s]) * e[s]  with the e of row n - 1     (terminal)
+ *   cost[3] = (summary[i][1] >= 0 ? c.fall_penalty : 0.0) + (summary[i][2] > 0 ? (double)summary[i][2] * c.unsolved_penalty : 0.0), or +0.0
+ *             when log.summary is NULL.  (The comparisons keep 0 * inf from occurring: an infinite penalty masks exactly the instances it is for.)
+ *   score = ((cost[0] + cost[1]) + cost[2]) + cost[3]
+ * A NaN anywhere in a row that carries weight gives a NaN score; with the default fall_penalty a fallen instance scores +inf.  Either masks
+ * the instance in the selection below.
+ *
+ * hmpc_rollout_score_device: device_ticks0 = hmpc_tick_inputs[batch], log = the rows to score (log == NULL: where the handle's last
+ * hmpc_rollout_device logged, and batch and n_ticks must be that rollout's), device_cost [batch][4] and device_score [batch] binary64,
+ * caller-owned, either may be NULL (= not written).  HMPC_E_ARG, nothing enqueued: a NULL handle, ticks0 or cost, batch < 0, n_ticks < 1,
+ * log.state NULL, or log == NULL with no rollout yet or another batch or n_ticks than the last rollout's.  It does not replace the handle's batch.
+ *
+ * THE SELECTION.  One launch, one workgroup per group g = instances g K .. g K + K - 1 (K = group_size):
+ *   s_i      = score[i] + penalty[i]        one binary64 addition; with device_penalty NULL no addition is made
+ *   eligible <=> s_i is finite
+ *   winner   = the eligible instance of smallest s_i; equal values (==, so -0 equals +0) are broken by the lowest index
+ * a lexicographic (s, index) minimum over the eligible instances -- ineligible ones never enter a comparison --, so the result does not
+ * depend on the workgroup size or on the order of the reduction; any group_size (each thread strides over its group).  Outputs: the
+ * members of struct hmpc_rollout_choice, caller-owned device pointers, each may be NULL (= not written); per group
+ *   index [groups]        int32:   the winner's position in its group, or -1 when the group has no winner
+ *   score [groups]        double:  the winner's s_i, or +inf
+ *   wrench[groups][12]    float:   a bit copy of the winner's row of tick 0 of log.wrench, or +0
+ *   tau   [groups][10]    double:  a bit copy of the winner's row of tick 0 of log.tau -- the torques to apply NOW --, or +0
+ *   summary[groups][4]    int32:   a bit copy of the winner's row of log.summary, or {0, -1, 0, 0}
+ * hmpc_rollout_select_device: log == NULL = where the handle's last hmpc_rollout_device logged, with its n_ticks as the row count per
+ * instance, and batch must be that rollout's; log != NULL = the caller's, rows per instance = the n_ticks of the handle's last
+ * hmpc_rollout_score_device, whose batch it must share.  HMPC_E_ARG, nothing enqueued: a NULL handle, score or choice, batch < 0,
+ * group_size < 1, batch % group_size != 0, no such rollout / score call or another batch, or choice->wrench, ->tau or ->summary asked
+ * for with the log member behind it NULL.
+ *
+ * THE CHAIN.  hmpc_rollout_sweep_device, on the one stream and without host synchronisation: (1) device_ticks [n_states] x
+ * device_commands [n_states][K] are expanded as hmpc_tick_sweep_device expands them -- instance g K + k = ticks[g] with its five command
+ * fields replaced by commands[g][k] --, twice, into two buffers of the handle's own (NOT its shared scratch: they must outlive n solves;
+ * allocated for max_batch instances by the first sweep, never inside hmpc_solve); (2) hmpc_rollout_device over the first copy with
+ * log == NULL and the arguments given here; (3) the score with ticks0 = the second copy, into the handle's own cost and score; (4) the
+ * selection with device_penalty [n_states * K] (or NULL) into `choice`.  device_ticks is not modified.  plant->device_mass and
+ * plant->device_ext_wrench are indexed by EXPANDED instance.  hmpc_get_device_rollout_sweep: the handle's buffers of the last sweep -- the
+ * expanded ticks after the rollout, cost [n_states K][4], score [n_states K] -- (any pointer may be NULL; HMPC_E_ARG before the first
+ * sweep); the log is hmpc_download_rollout's.  Two-contact handles only.  HMPC_E_BATCH when n_states * K > max_batch.  HMPC_E_ARG, nothing
+ * enqueued: a NULL handle, ticks, commands, plant, cost or choice, n_states < 1, K < 1, and every argument error of hmpc_rollout_device. */
+struct hmpc_rollout_cost {
+  double w_state[12];      /* the reference's Q (100, 100, 250, 200, 200, 300, 1, 1, 1, 1, 1, 1): weight per column of the log's state row */
+  double w_terminal[12];   /* 0: extra weight on the last tick */
+  double w_wrench[12];     /* the reference's Alpha (1e-4, 1e-4, 5e-4, 1e-4, 1e-4, 5e-4, six times 1e-2): weight on the logged step-0 wrench */
+  double w_tau[10];        /* 0: weight on the logged joint torques */
+  double height;           /* 0.55: reference z */
+  double dt_tick;          /* 0.005: seconds per tick */
+  double fall_penalty;     /* +inf: a fallen instance is masked */
+  double unsolved_penalty; /* 0: per unsolved tick */
+};
+struct hmpc_rollout_choice {
+  int32_t *index;
+  double *score;
+  float *wrench;
+  double *tau;
+  int32_t *summary;
+};
+void hmpc_default_rollout_cost(struct hmpc_rollout_cost *c);
+int hmpc_rollout_score_device(hmpc_handle *h, const void *device_ticks0, int batch, int n_ticks, const struct hmpc_rollout_cost *cost,
+                              const struct hmpc_rollout_log *log, double *device_cost, double *device_score, void *stream);
+int hmpc_rollout_select_device(hmpc_handle *h, const double *device_score, const double *device_penalty, int batch, int group_size,
+                               const struct hmpc_rollout_log *log, const struct hmpc_rollout_choice *choice, void *stream);
+int hmpc_rollout_sweep_device(hmpc_handle *h, const void *device_ticks, int n_states, const struct hmpc_command *device_commands, int K,
+                              int n_ticks, double dtMPC, int ticks_per_step, int subtick0, const struct hmpc_plant *plant,
+                              const struct hmpc_rollout_cost *cost, const double *device_penalty, const struct hmpc_rollout_choice *choice,
+                              void *stream);
+int hmpc_get_device_rollout_sweep(hmpc_handle *h, void **ticks_final, double **cost, double **score);
 /* copies the current batch's packed records device -> host (parity hook for f1/f2) */
 int hmpc_download_records(hmpc_handle *h, void *host_records);
 
