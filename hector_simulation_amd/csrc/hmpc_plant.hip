@@ -45,10 +45,21 @@ static int plant_args(hmpc_handle *h, int batch, const hmpc_plant *plant, const 
   return (a->force_stride < 12) ? HMPC_E_ARG : HMPC_OK;
 }
 
-// the handle's own log buffers, for max_batch x n_ticks (kept when they already hold as many ticks)
+// whether any member of `lg` is one of the handle's own log buffers
+static bool logs_into_own_buffers(const hmpc_handle *h, const hmpc_rollout_log &lg) {
+  return (lg.state && lg.state == h->d_roll_state.get()) || (lg.wrench && lg.wrench == h->d_roll_wrench.get()) ||
+         (lg.status && lg.status == h->d_roll_status.get()) || (lg.tau && lg.tau == h->d_roll_taulog.get()) ||
+         (lg.summary && lg.summary == h->d_roll_summary.get());
+}
+
+// the handle's own log buffers, for max_batch x n_ticks (kept when they already hold as many ticks).  A growth frees the old buffers, so
+// a last rollout that logged into any of them is forgotten first -- whatever happens after: hmpc_download_rollout and the score and
+// selection with log == NULL answer as before the first rollout instead of reading freed memory.  One that logged wholly into the
+// caller's buffers stays.
 static int own_rollout_buffers(hmpc_handle *h, int n_ticks) {
   const size_t rows = (size_t)h->max_batch * (size_t)n_ticks;
   if (n_ticks > h->roll_own_ticks) {
+    if (logs_into_own_buffers(h, h->roll_last)) h->roll_last = {}, h->roll_last_ticks = 0, h->roll_last_batch = 0;
     HIP_TRY(h->d_roll_state.reserve(rows * 12 * sizeof(double), h->last_stream, /*whole_device=*/false));
     HIP_TRY(h->d_roll_wrench.reserve(rows * 12 * sizeof(float), h->last_stream, false));
     HIP_TRY(h->d_roll_status.reserve(rows * sizeof(uint32_t), h->last_stream, false));

@@ -89,8 +89,9 @@ int hmpc_rollout_sweep_device(hmpc_handle *h, const void *device_ticks, int n_st
   hmpc_tick_inputs *now = (hmpc_tick_inputs *)h->d_rsw_ticks.get(), *before = (hmpc_tick_inputs *)h->d_rsw_ticks0.get();
   HIP_TRY(hmpc::launch_expand_ticks((const hmpc_tick_inputs *)device_ticks, n_states, device_commands, K, now, nullptr, s));
   HIP_TRY(hmpc::launch_expand_ticks((const hmpc_tick_inputs *)device_ticks, n_states, device_commands, K, before, nullptr, s));
-  h->last_stream = s;
+  // (last_stream is still the stream of the handle's previous work here: a log that has to grow waits for THAT stream before it frees)
   int rc = hmpc_rollout_device(h, now, batch, n_ticks, dtMPC, ticks_per_step, subtick0, plant, /*log=*/nullptr, stream);
+  h->last_stream = s;
   if (rc != HMPC_OK) return rc;
   h->rsw_batch = batch;
   rc = hmpc_rollout_score_device(h, before, batch, n_ticks, cost, nullptr, h->d_rsw_cost.get(), h->d_rsw_score.get(), stream);

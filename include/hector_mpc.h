@@ -1099,7 +1099,10 @@ struct hmpc_rollout_log {
  * Two-contact handles only.  HMPC_E_ARG, nothing enqueued: n_ticks < 1, ticks_per_step < 1, subtick0 < 0, plant->substeps < 1, a
  * three-contact handle, batch > max_batch or < 0, a NULL handle, ticks or plant (plant == NULL is NOT the default plant).
  * hmpc_get_device_rollout: the handle's own log buffers, (re)allocated for max_batch x n_ticks when they hold fewer ticks -- outside the
- * solve; the pointers stay valid until a call with a larger n_ticks.  hmpc_set_device_rollout: caller-owned buffers for the rollouts that
+ * solve; the pointers stay valid until a call with a larger n_ticks, here or in a rollout or sweep with log == NULL.  Such a growth frees
+ * the old buffers, so the handle forgets a last rollout that logged into any of them (one logged wholly into the caller's buffers stays):
+ * until the next rollout, hmpc_download_rollout and the score and selection with log == NULL return HMPC_E_ARG, as before the first
+ * rollout; the old contents are not copied over.  hmpc_set_device_rollout: caller-owned buffers for the rollouts that
  * pass log == NULL (NULL member = the handle's own; log == NULL = all the handle's own).  hmpc_download_rollout waits for the stream of
  * the last rollout, then copies its log (any pointer may be NULL; a member that was not logged: HMPC_E_ARG); HMPC_E_ARG before the first.
  * Device groups: per member, through hmpc_group_member. */
