@@ -87,8 +87,8 @@ int hmpc_create_ex(hmpc_handle **out, const struct problem_setup *setup, int max
   hmpc_default_params(&h->params);
   const size_t mb = (size_t)max_batch, nf = mb * 6 * n_contacts * setup->horizon;
   const bool ok = h->d_record_store.alloc(mb * h->stride) == hipSuccess && h->d_forces.ensure(nf) == hipSuccess &&
-                  h->d_status.ensure(mb) == hipSuccess && h->d_flagged.alloc_filled(1, 0) == hipSuccess &&
-                  (n_contacts != 2 || h->d_cls.alloc_filled(mb, 0) == hipSuccess) &&
+                  h->d_status.ensure(mb) == hipSuccess && alloc_filled_done(h->d_flagged, 1, 0) == hipSuccess &&
+                  (n_contacts != 2 || alloc_filled_done(h->d_cls, mb, 0) == hipSuccess) &&
                   (max_batch <= DISPATCH_ORDER_MIN_BATCH || (h->d_order.alloc(mb) == hipSuccess && h->d_keys.alloc(mb) == hipSuccess));
   if (!ok) {
     hip_error_text() = "hipMalloc failed in hmpc_create";
@@ -103,6 +103,7 @@ int hmpc_create_ex(hmpc_handle **out, const struct problem_setup *setup, int max
 int hmpc_destroy(hmpc_handle *h) {
   if (!h) return HMPC_E_ARG;
   hipSetDevice(h->device);
+  (void)settle(h);  // the stream rule: the handle's memory is freed next (an error here must not keep the handle alive)
   delete h;  // (every device buffer of the handle frees itself)
   return HMPC_OK;
 }
@@ -124,6 +125,8 @@ static int upload_common(hmpc_handle *h, const void *host_records, int batch, bo
   if (pitch == 0) pitch = h->stride;
   if (pitch < h->stride || pitch % 4 != 0) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
+  // the copy replaces the records a pending solve may have yet to read: behind the handle's stream, or once the handle has settled
+  RC_TRY(async ? enter_stream(h, stream) : settle(h));
   if (pitch != h->stride) {
     if (batch > 0)
       HIP_TRY(hipMemcpy2DAsync(h->d_record_store.get(), h->stride, host_records, pitch, h->stride, (size_t)batch, hipMemcpyHostToDevice, stream));
@@ -158,6 +161,7 @@ int hmpc_upload_records_strided_async(hmpc_handle *h, const void *host_records, 
 int hmpc_download_async(hmpc_handle *h, float *forces, uint32_t *status, void *stream) {
   if (!h) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   const size_t nf = (size_t)h->batch * 6 * h->nc * h->setup.horizon;
   if (forces && nf)
     HIP_TRY(hipMemcpyAsync(forces, h->d_forces.get(), nf * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -251,7 +255,7 @@ int hmpc_set_warm_start(hmpc_handle *h, int on) {
 int hmpc_set_tick_warm_start(hmpc_handle *h, int on, int horizon_shift) {
   if (!h || horizon_shift < 0) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  if (on && !h->d_wset.get()) HIP_TRY(h->d_wset.alloc_filled((size_t)h->max_batch * 8 * h->nc * h->setup.horizon, 0));
+  if (on && !h->d_wset.get()) HIP_TRY(alloc_filled_done(h->d_wset, (size_t)h->max_batch * 8 * h->nc * h->setup.horizon, 0));
   h->tick_warm = on ? 1 : 0;
   h->tick_shift = horizon_shift;
   return HMPC_OK;
@@ -261,8 +265,9 @@ int hmpc_reset_tick_warm_start(hmpc_handle *h) {
   if (!h) return HMPC_E_ARG;
   if (!h->d_wset.get()) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
-  HIP_TRY(hipMemset(h->d_wset.get(), 0, (size_t)h->max_batch * 8 * h->nc * h->setup.horizon));
+  // on the handle's stream, not the null stream: behind the solve that may still be writing the sets and ahead of the next one on that
+  // stream, with no wait on the host (a solve on another stream settles the handle first, like any call that changes streams)
+  HIP_TRY(hipMemsetAsync(h->d_wset.get(), 0, (size_t)h->max_batch * 8 * h->nc * h->setup.horizon, h->last_stream));
   return HMPC_OK;
 }
 
@@ -276,7 +281,7 @@ int hmpc_solve(hmpc_handle *h, void *stream) {
   if (!h) return HMPC_E_ARG;
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   return enqueue_solve(h, (hipStream_t)stream, /*carry_wset=*/true);
 }
 
@@ -287,7 +292,7 @@ int hmpc_solve_command_sweep(hmpc_handle *h, int group_size, void *stream) {
   if (h->batch % group_size != 0) return HMPC_E_ARG;
   if (group_size == 1) return hmpc_solve(h, stream);
   HIP_TRY(hipSetDevice(h->device));
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   return enqueue_command_sweep(h, (hipStream_t)stream, group_size);
 }
 
@@ -306,7 +311,7 @@ int hmpc_set_device_repair(hmpc_handle *h, int on) {
     // both buffers or neither: they are committed to the handle only once both exist and are cleared
     DeviceBuffer<int> list;
     DeviceBuffer<unsigned int> count;
-    if (list.alloc_filled((size_t)(flag_list_cap(h->max_batch) + REG_LIST_CAP), 0) != hipSuccess || count.alloc_filled(2, 0) != hipSuccess) {
+    if (alloc_filled_done(list, (size_t)(flag_list_cap(h->max_batch) + REG_LIST_CAP), 0) != hipSuccess || alloc_filled_done(count, 2, 0) != hipSuccess) {
       hip_error_text() = "hipMalloc failed in hmpc_set_device_repair";
       return HMPC_E_HIP;
     }
@@ -332,7 +337,7 @@ static int resolve_if_flagged(hmpc_handle *h) {
 int hmpc_download(hmpc_handle *h, float *forces, uint32_t *status) {
   if (!h) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   if (h->auto_resolve && h->batch) {
     int rc = resolve_if_flagged(h);
     if (rc != HMPC_OK) return rc;
@@ -363,7 +368,7 @@ int hmpc_time_solve(hmpc_handle *h, void *stream, int reps, float *ms_per_launch
   HIP_TRY(hipEventCreate(&ev.e0));
   HIP_TRY(hipEventCreate(&ev.e1));
   hipStream_t s = (hipStream_t)stream;
-  h->last_stream = s;
+  RC_TRY(enter_stream(h, s));
   HIP_TRY(hipEventRecord(ev.e0, s));
   for (int i = 0; i < reps; ++i) {
     // a single timed launch is a genuine solve of the current batch (it consumes and leaves the tick-to-tick working sets);
@@ -385,6 +390,7 @@ int hmpc_debug_assemble(hmpc_handle *h, int index, int *n, int *m, int *var_ind,
   HIP_TRY(hipSetDevice(h->device));
   const int vi = pick_variant(h);
   const Variant &v = variants()[vi];
+  RC_TRY(enter_stream(h, nullptr));
   if (!h->d_dbg_f.get()) HIP_TRY(h->d_dbg_f.alloc((size_t)DBG_FLOATS_MAX));
   if (!h->d_dbg_i.get()) HIP_TRY(h->d_dbg_i.alloc(2 + MAX_VARS_ANY));
   HIP_TRY(hipMemset(h->d_dbg_i.get(), 0, sizeof(int) * (2 + MAX_VARS_ANY)));
@@ -428,7 +434,7 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
     if (ld < need) return HMPC_E_ARG;
   }
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   const size_t nb = (size_t)h->batch, nfc = (size_t)8 * h->nc * 6 * h->nc;
   DeviceBuffer<float> ext;  // (freed on every return path)
   HIP_TRY(ext.alloc(nb * ((size_t)ld * ld + ld + nfc)));
@@ -440,19 +446,17 @@ int hmpc_debug_solve_external_qp(hmpc_handle *h, const float *H, const float *g,
   LaunchOpt xo;
   xo.carry_wset = false;
   const int rc = enqueue_fast(h, h->last_stream, pick_variant(h), /*classes=*/false, xo);
-  hipError_t e = hipStreamSynchronize(h->last_stream);
+  const int src = settle(h);  // (ext is freed on return)
   h->d_ext_H = h->d_ext_g = h->d_ext_Fc = nullptr;
   h->ext_ld = 0;
-  if (rc != HMPC_OK) return rc;
-  HIP_TRY(e);
-  return HMPC_OK;
+  return rc != HMPC_OK ? rc : src;
 }
 
 int hmpc_debug_handover_slots(hmpc_handle *h, int *slots) {
   if (!h || !slots) return HMPC_E_ARG;
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   if (!h->d_spill_slot.get()) {  // (no saving variant has run on this handle: nothing was ever handed over)
     for (int i = 0; i < h->batch; ++i) slots[i] = -1;
     return HMPC_OK;
@@ -476,7 +480,7 @@ int hmpc_debug_phase_cycles(hmpc_handle *h, long long *cycles /*[batch][NPROF = 
   // (with the device-side repair on, the whole chain: an instance's slot then holds the numbers of the LAST variant that ran it)
   int rc = h->device_repair ? enqueue_solve(h, h->last_stream, false) : launch(h, h->last_stream, pick_variant(h), LaunchOpt());
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   HIP_TRY(hipMemcpy(cycles, h->d_prof.get(), (size_t)h->batch * hmpc::NPROF * sizeof(long long), hipMemcpyDeviceToHost));
   h->d_prof.reset();
   return HMPC_OK;
@@ -490,11 +494,11 @@ int hmpc_build_records_device(hmpc_handle *h, const void *device_ticks, int batc
   if (!h || !device_ticks || batch < 0) return HMPC_E_ARG;
   if (batch > h->max_batch) return HMPC_E_BATCH;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));  // (the builder writes the record store and the size classes)
   HIP_TRY(hmpc::launch_build_records((const hmpc_tick_inputs *)device_ticks, batch, h->setup.horizon, dtMPC, h->d_record_store.get(),
                                      (int)h->stride, device_wpd_out, h->setup.f_max, h->d_cls.get(), (hipStream_t)stream));
   // (the builder left every instance's size class on the device: hmpc_solve routes by it)
   replace_batch(h, h->d_record_store.get(), batch, /*max_stance=*/-1, /*cls_valid=*/1);
-  h->last_stream = (hipStream_t)stream;
   return HMPC_OK;
 }
 
@@ -502,6 +506,7 @@ int hmpc_build_records(hmpc_handle *h, const struct hmpc_tick_inputs *host_ticks
   if (!h || !host_ticks || batch < 0) return HMPC_E_ARG;
   if (batch > h->max_batch) return HMPC_E_BATCH;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(settle(h));  // the shared scratch may hold a pending sweep's expanded ticks, the record store a pending solve's records
   const size_t nb = (size_t)(batch > 0 ? batch : 1);
   const size_t off_w = (sizeof(hmpc_tick_inputs) * nb + 255) & ~(size_t)255;
   void *sp = nullptr;
@@ -512,7 +517,7 @@ int hmpc_build_records(hmpc_handle *h, const struct hmpc_tick_inputs *host_ticks
   HIP_TRY(hipMemcpy(d_t, host_ticks, sizeof(hmpc_tick_inputs) * (size_t)batch, hipMemcpyHostToDevice));
   rc = hmpc_build_records_device(h, d_t, batch, dtMPC, d_w, nullptr);
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
+  RC_TRY(settle(h));
   if (wpd_out && batch) HIP_TRY(hipMemcpy(wpd_out, d_w, sizeof(double) * 2 * (size_t)batch, hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
@@ -521,6 +526,7 @@ int hmpc_body_wrench_device(hmpc_handle *h, const double *device_rBody, double *
   if (h && h->nc != 2) return HMPC_E_ARG;  // rows f1-f3 restate the reference's two-foot controller code
   if (!h || !device_rBody || !device_f_ff) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_body_wrench(h->d_forces.get(), h->batch, h->setup.horizon, device_rBody, device_f_ff, (hipStream_t)stream));
   return HMPC_OK;
 }
@@ -530,15 +536,15 @@ int hmpc_body_wrench(hmpc_handle *h, const double *host_rBody, double *host_f_ff
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   const size_t b = (size_t)h->batch;
+  RC_TRY(settle(h));  // before the copies: the shared scratch may hold a pending sweep's expanded ticks
   void *sp = nullptr;
   int rc = scratch(h, sizeof(double) * (9 + 12) * b, &sp);
   if (rc != HMPC_OK) return rc;
   double *d_r = (double *)sp, *d_f = d_r + 9 * b;
   HIP_TRY(hipMemcpy(d_r, host_rBody, sizeof(double) * 9 * b, hipMemcpyHostToDevice));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
   rc = hmpc_body_wrench_device(h, d_r, d_f, nullptr);
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
+  RC_TRY(settle(h));
   HIP_TRY(hipMemcpy(host_f_ff, d_f, sizeof(double) * 12 * b, hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
@@ -548,6 +554,7 @@ int hmpc_leg_torques_device(hmpc_handle *h, const double *device_rBody, const do
   if (h && h->nc != 2) return HMPC_E_ARG;  // rows f1-f3 restate the reference's two-foot controller code
   if (!h || !device_rBody || !device_leg_q || !device_tau) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_leg_torques(h->d_forces.get(), h->batch, h->setup.horizon, device_rBody, device_leg_q, device_f_ff, device_tau,
                                    /*ticks=*/nullptr, (hipStream_t)stream));
   return HMPC_OK;
@@ -558,16 +565,16 @@ int hmpc_leg_torques(hmpc_handle *h, const double *host_rBody, const double *hos
   if (h->batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nb = (size_t)h->batch;
+  RC_TRY(settle(h));  // before the copies: the shared scratch may hold a pending sweep's expanded ticks
   void *sp = nullptr;
   int rc = scratch(h, sizeof(double) * (9 + 10 + 12 + 10) * nb, &sp);
   if (rc != HMPC_OK) return rc;
   double *d_r = (double *)sp, *d_q = d_r + 9 * nb, *d_f = d_q + 10 * nb, *d_t = d_f + 12 * nb;
   HIP_TRY(hipMemcpy(d_r, host_rBody, sizeof(double) * 9 * nb, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_q, host_leg_q, sizeof(double) * 10 * nb, hipMemcpyHostToDevice));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
   rc = hmpc_leg_torques_device(h, d_r, d_q, d_f, d_t, nullptr);
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(nullptr));
+  RC_TRY(settle(h));
   if (host_f_ff) HIP_TRY(hipMemcpy(host_f_ff, d_f, sizeof(double) * 12 * nb, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(host_tau, d_t, sizeof(double) * 10 * nb, hipMemcpyDeviceToHost));
   return HMPC_OK;
@@ -594,7 +601,7 @@ int hmpc_tick_solve_device(hmpc_handle *h, const void *device_ticks, int batch, 
 int hmpc_download_records(hmpc_handle *h, void *host_records) {
   if (!h || !host_records) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   if (h->batch) HIP_TRY(hipMemcpy(host_records, h->d_records, (size_t)h->batch * h->stride, hipMemcpyDeviceToHost));
   return HMPC_OK;
 }
@@ -626,7 +633,7 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj) {
     rc = enqueue_solve(h, h->last_stream, /*carry_wset=*/false);
     if (rc != HMPC_OK) return rc;
   }
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   if (h->auto_resolve) {
     const int rc = resolve_if_flagged(h);
     if (rc != HMPC_OK) return rc;
@@ -679,7 +686,7 @@ int hmpc_predict_states(hmpc_handle *h, void *stream) {
   memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it)
   set_problem_args(h, a);
   a.mu_inst = nullptr;  // (friction shapes the constraint block only; the model does not depend on it)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_predict(h->nc, a, s, c, (hipStream_t)stream));
   h->results.on_predict();
   return HMPC_OK;
@@ -690,7 +697,7 @@ int hmpc_download_prediction(hmpc_handle *h, float *states, double *cost) {
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_prediction()) return HMPC_E_ARG;  // nothing predicted from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   float *s = nullptr;
   double *c = nullptr;
   const int rc = prediction_buffers(h, &s, &c);
@@ -747,7 +754,7 @@ int hmpc_constraint_margins(hmpc_handle *h, void *stream) {
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_margins(h->nc, a, b.slack, b.summary, b.where, (hipStream_t)stream));
   h->results.on_margins();
   return HMPC_OK;
@@ -758,7 +765,7 @@ int hmpc_download_margins(hmpc_handle *h, double *slack, double *summary, int32_
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_margins()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   MarginBuffers b;
   const int rc = margin_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -777,7 +784,7 @@ int hmpc_margin_penalty(hmpc_handle *h, const double floor[6], const double *dev
   MarginBuffers b;
   const int rc = margin_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_margin_penalty(b.summary, floor, device_penalty_in, device_penalty_out, h->batch, (hipStream_t)stream));
   return HMPC_OK;
 }
@@ -844,7 +851,7 @@ int hmpc_kkt_certificate(hmpc_handle *h, void *stream) {
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_certificate(h->nc, a, h->cert_act_tol, b, (hipStream_t)stream));
   h->results.on_certificate();
   return HMPC_OK;
@@ -855,7 +862,7 @@ int hmpc_download_certificate(hmpc_handle *h, double *grad, double *lambda, doub
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_certificate()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::CertificateOut b;
   const int rc = certificate_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -876,7 +883,7 @@ int hmpc_certificate_penalty(hmpc_handle *h, const double ceil[3], const double 
   hmpc::CertificateOut b;
   const int rc = certificate_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_certificate_penalty(b.summary, ceil, device_penalty_in, device_penalty_out, h->batch, (hipStream_t)stream));
   return HMPC_OK;
 }
@@ -946,7 +953,7 @@ int hmpc_feedback_gains(hmpc_handle *h, void *stream) {
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_feedback(h->nc, a, h->cert_act_tol, b, (hipStream_t)stream));
   h->results.on_gains();
   return HMPC_OK;
@@ -957,7 +964,7 @@ int hmpc_download_gains(hmpc_handle *h, double *gain, double *ref_gain, double *
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_gains()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::FeedbackOut b;
   const int rc = gain_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -989,7 +996,7 @@ int hmpc_first_order_wrench(hmpc_handle *h, const void *device_records_new, void
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));
   set_problem_args(h, a);
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_first_order(h->nc, a, (const unsigned char *)device_records_new, g, b.wrench, b.worst, (hipStream_t)stream));
   h->results.on_first_order();
   return HMPC_OK;
@@ -1000,7 +1007,7 @@ int hmpc_download_first_order(hmpc_handle *h, float *wrench, double *worst_slack
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_first_order()) return HMPC_E_ARG;  // nothing computed from the gains of the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   FirstOrderBuffers b;
   const int rc = first_order_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1061,7 +1068,7 @@ int hmpc_solve_adjoint(hmpc_handle *h, const double *device_seed, void *stream) 
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (no index list, no external QP data, relax 0: stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: friction shapes the constraint block)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_adjoint(h->nc, a, h->cert_act_tol, device_seed, b, (hipStream_t)stream));
   h->results.on_adjoint();
   return HMPC_OK;
@@ -1140,7 +1147,7 @@ int hmpc_solve_adjoint_multi(hmpc_handle *h, const double *device_seeds, int n_s
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (as hmpc_solve_adjoint)
   set_problem_args(h, a);
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_adjoint_multi(h->nc, a, h->cert_act_tol, device_seeds, n_seeds, adjoint_multi_base(h), (hipStream_t)stream));
   h->results.on_adjoint_multi(n_seeds);
   return HMPC_OK;
@@ -1158,7 +1165,7 @@ int hmpc_download_adjoint_multi(hmpc_handle *h, double *grad_x0, double *grad_tr
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_adjoint_multi()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   const hmpc::AdjointOut b = adjoint_multi_base(h);
   size_t n[6];
   adjoint_row_sizes(h, n);
@@ -1178,7 +1185,7 @@ int hmpc_download_adjoint(hmpc_handle *h, double *grad_x0, double *grad_traj, do
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_adjoint()) return HMPC_E_ARG;  // nothing computed from the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::AdjointOut b;
   const int rc = current_adjoint(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1245,7 +1252,7 @@ int hmpc_adjoint_model(hmpc_handle *h, void *stream) {
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_model_adjoint(h->nc, a, (double)h->params.mass, adj.dir, b, (hipStream_t)stream));
   h->results.on_model_adjoint();
   return HMPC_OK;
@@ -1256,7 +1263,7 @@ int hmpc_download_adjoint_model(hmpc_handle *h, double *grad_A, double *grad_B, 
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_model_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint of the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::ModelAdjointOut b;
   const int rc = model_adjoint_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1324,7 +1331,7 @@ int hmpc_adjoint_limits(hmpc_handle *h, const double *device_seed, void *stream)
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_limit_adjoint(h->nc, a, h->cert_act_tol, adj.dir, device_seed, b, (hipStream_t)stream));
   h->results.on_limit_adjoint();
   return HMPC_OK;
@@ -1336,7 +1343,7 @@ int hmpc_download_adjoint_limits(hmpc_handle *h, double *grad_limits, double *gr
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_limit_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint of the last solve of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::LimitAdjointOut b;
   const int rc = limit_adjoint_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1405,7 +1412,7 @@ int hmpc_adjoint_record(hmpc_handle *h, void *stream) {
   memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
   const hmpc::PoseAdjointIn in = {adj.grad_x0, adj.grad_traj, adj.grad_weights, adj.grad_alpha, mo.grad_A, mo.grad_B, mo.grad_r, lo.grad_limits, lo.grad_Fc};
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_pose_adjoint(h->nc, a, in, b, (hipStream_t)stream));
   h->results.on_record_adjoint();
   return HMPC_OK;
@@ -1416,7 +1423,7 @@ int hmpc_download_adjoint_record(hmpc_handle *h, double *grad_record, double *gr
   if (h->batch == 0) return HMPC_OK;
   if (!h->results.has_record_adjoint()) return HMPC_E_ARG;  // nothing computed from the last adjoint, model and limit gradients of this batch
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   hmpc::PoseAdjointOut b;
   const int rc = record_adjoint_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1500,7 +1507,7 @@ int hmpc_adjoint_chain_multi(hmpc_handle *h, const double *device_seeds, void *s
   hmpc::KernelArgs a;
   memset(&a, 0, sizeof(a));  // (stage A as an ordinary solve runs it -- the handle's own assembly)
   set_problem_args(h, a);    // (mu_inst stays: the assembly is the solve's)
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_adjoint_chain(h->nc, a, h->cert_act_tol, (double)h->params.mass, in, n_seeds, out, (hipStream_t)stream));
   for (int k = 0; k < CHAIN_ARRAYS; ++k) h->chain_written[k] = p[k] != nullptr;
   h->results.on_adjoint_chain();
@@ -1516,7 +1523,7 @@ int hmpc_download_adjoint_chain_multi(hmpc_handle *h, const struct hmpc_adjoint_
   for (int k = 0; k < CHAIN_ARRAYS; ++k)
     if (dst[k] && !h->chain_written[k]) return HMPC_E_ARG;  // a detail array that was not written
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   double *src[CHAIN_ARRAYS];
   chain_base(h, src);
   size_t n[CHAIN_ARRAYS];
@@ -1591,7 +1598,7 @@ int hmpc_sweep_select(hmpc_handle *h, int group_size, const double *device_penal
   a.groups = h->batch / group_size, a.group_size = group_size;
   a.force_words = 6 * h->nc * h->setup.horizon, a.state_words = 13 * h->setup.horizon;
   a.index = b.index, a.score = b.score, a.out_forces = b.forces, a.out_status = b.status, a.out_states = b.states;
-  h->last_stream = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_select(a, (hipStream_t)stream));
   h->results.on_select(a.groups);
   return HMPC_OK;
@@ -1600,7 +1607,7 @@ int hmpc_sweep_select(hmpc_handle *h, int group_size, const double *device_penal
 int hmpc_download_selection(hmpc_handle *h, int32_t *index, double *score, float *forces, uint32_t *status, float *states) {
   if (!h || !h->results.has_selection()) return HMPC_E_ARG;  // nothing selected from the last prediction
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   SelectionBuffers b;
   const int rc = selection_buffers(h, &b);
   if (rc != HMPC_OK) return rc;
@@ -1625,6 +1632,7 @@ int hmpc_tick_sweep_device(hmpc_handle *h, const void *device_ticks, int n_ticks
   const int batch = n_ticks * group_size;
   if (batch == 0) return hmpc_build_records_device(h, device_ticks, 0, dtMPC, nullptr, stream);
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));  // (the expansion writes the shared scratch)
   void *sp = nullptr;
   int rc = scratch(h, sizeof(hmpc_tick_inputs) * (size_t)batch, &sp);
   if (rc != HMPC_OK) return rc;

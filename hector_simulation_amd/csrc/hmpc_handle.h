@@ -32,6 +32,12 @@ std::string &hip_error_text();  // what hmpc_last_hip_error reports: per thread 
     }                                                                                                    \
   } while (0)
 
+#define RC_TRY(expr)                       \
+  do {                                     \
+    const int _rc = (expr);                \
+    if (_rc != HMPC_OK) return _rc;        \
+  } while (0)
+
 struct hmpc_handle {  // (opaque to callers: its constructor and destructor are not exported)
   problem_setup setup{};
   int nc = 2;  // contacts per horizon step: 2 (reference) or 3 (hand-contact extension)
@@ -50,7 +56,7 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   int tick_warm = 0, tick_shift = 0;
   int auto_resolve = 1;  // hmpc_download re-solves flagged instances with the safe variant (default on)
   int max_stance = -1;  // max reduced variables of the current batch (known only for host-uploaded records; else -1)
-  hipStream_t last_stream = nullptr;
+  hipStream_t last_stream = nullptr;  // the stream of the last enqueued call: moved by enter_stream, waited for by settle, by nothing else
   bool attrs_set[N_VARIANTS] = {};
   // persistent device scratch for the host-pointer convenience entry points (grown on demand): no allocation per call and nothing to
   // leak on an early error return
@@ -202,7 +208,39 @@ struct LaunchOpt {
 
 // ---- hmpc_launch.hip
 const Variant *variants();  // [N_VARIANTS], in the order of HMPC_VARIANT_TABLE
-// returns a device buffer of at least `bytes` owned by the handle (contents undefined); its earlier users may be on any stream
+// THE STREAM RULE (include/hector_mpc.h, "Streams"), kept by settle and enter_stream and by nothing else: no
+// other line of the library decides to wait for h->last_stream, and none assigns it.
+//  * settle: the host is about to write, read, free or reallocate device memory of the handle: waits until everything enqueued for the
+//    handle has finished.
+//  * enter_stream: the call enqueues on `stream`.  The same stream as the last call's: nothing (no wait, no launch -- stream order does
+//    it).  Another one: settle first, since what is enqueued next writes the handle's memory from the new stream.  Then `stream` is the
+//    handle's stream.  A call enters its stream BEFORE it grows a buffer or launches.
+int settle(hmpc_handle *h);
+int enter_stream(hmpc_handle *h, hipStream_t stream);
+//  * grow: a buffer whose users are the handle's own calls grows to at least `bytes` (contents undefined).  The old allocation is freed,
+//    so the handle is settled first; a buffer that is large enough costs nothing.
+template <class T>
+int grow(hmpc_handle *h, DeviceBuffer<T> &b, size_t bytes) {
+  if (b.get() && bytes <= b.bytes()) return HMPC_OK;
+  if (b.get()) RC_TRY(settle(h));
+  HIP_TRY(b.alloc((bytes + sizeof(T) - 1) / sizeof(T)));  // (frees the old allocation, which nothing uses any more)
+  return HMPC_OK;
+}
+// A new buffer with every byte set (DeviceBuffer::alloc_filled) whose first reader is a kernel on a stream that is not known yet and is, as
+// a rule, NON-BLOCKING: the null stream, on which hipMemset fills, does not order such a stream.  Whether a device memset has finished
+// when hipMemset returns is promised nowhere: hip_runtime_api.h documents the call without a word on completion, and the CUDA runtime API
+// it mirrors says the opposite outright (its "API synchronization behavior" notes: memsets of device memory may be asynchronous with
+// respect to the host).  The fill cannot be put on the reader's stream -- hmpc_create, hmpc_set_tick_warm_start and hmpc_set_device_repair
+// take none -- so the null stream is synchronised behind it.  Once per buffer; a call that finds its buffers allocated never gets here.
+// (A call that HAS a stream fills on it instead: the hand-over slot table in launch(), hmpc_reset_tick_warm_start.)
+template <class T>
+hipError_t alloc_filled_done(DeviceBuffer<T> &b, size_t count, int byte) {
+  hipError_t e = b.alloc_filled(count, byte);
+  if (e == hipSuccess && (e = hipStreamSynchronize(nullptr)) != hipSuccess) b.reset();
+  return e;
+}
+// returns a device buffer of at least `bytes` owned by the handle (contents undefined).  Its earlier users are the handle's own calls: the
+// caller has settled the handle or entered its stream before it writes the buffer
 int scratch(hmpc_handle *h, size_t bytes, void **out);
 // What stage A of a kernel reads of the handle: the batch, the problem shape and the robot / contact constants.  One place, so that the
 // prediction and margins kernels assemble from the very values the solve kernels do.

@@ -23,6 +23,18 @@ const Variant *variants() {
   return v;
 }
 
+int settle(hmpc_handle *h) {
+  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  return HMPC_OK;
+}
+
+int enter_stream(hmpc_handle *h, hipStream_t stream) {
+  if (stream == h->last_stream) return HMPC_OK;
+  const int rc = settle(h);
+  if (rc == HMPC_OK) h->last_stream = stream;
+  return rc;
+}
+
 int scratch(hmpc_handle *h, size_t bytes, void **out) {
   HIP_TRY(h->d_scratch.reserve((bytes + 4095) & ~(size_t)4095, nullptr, /*whole_device=*/true));
   *out = h->d_scratch.get();
@@ -54,7 +66,7 @@ int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
   // keeps the chunks apart).  The device-driven pass (d_list_count) is one launch, capped by its caller.
   const int chunk = (v.e_global && o.d_index_list && !o.d_list_count && grid_all > EGLOBAL_CHUNK) ? EGLOBAL_CHUNK : grid_all;
   if (v.e_global)  // one slice of packed triangle per workgroup of this launch
-    HIP_TRY(h->d_escratch.reserve((size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double), stream, /*whole_device=*/false));
+    RC_TRY(grow(h, h->d_escratch, (size_t)chunk * ((size_t)v.nmax * (v.nmax + 1) / 2) * sizeof(double)));
   // hand-over slots: allocated on the first launch of a variant that saves its state (one slot per instance of the handle).
   // The per-instance slot table is written by EVERY ordinary launch of such a variant (-1 where nothing was saved), also when
   // saving itself is off for the launch, so that a later safe pass never meets an entry of an earlier batch.
@@ -62,7 +74,13 @@ int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
   if ((v.role == Role::SWEEP) != (o.sweep_k > 0)) return HMPC_E_ARG;
   const bool can_save = v.spill_stride > 0 && !o.assemble_only && !o.d_index_list;
   const bool saves = can_save && h->handover && !h->d_ext_H;
-  if (can_save && !h->d_spill_slot.get()) HIP_TRY(h->d_spill_slot.alloc_filled((size_t)h->max_batch, 0xff));
+  if (can_save && !h->d_spill_slot.get()) {
+    // filled on the launch's own stream, which is the stream that reads it next: no fill on the null stream, no wait on the host
+    HIP_TRY(h->d_spill_slot.alloc((size_t)h->max_batch));
+    const hipError_t e = hipMemsetAsync(h->d_spill_slot.get(), 0xff, (size_t)h->max_batch * sizeof(int), stream);
+    if (e != hipSuccess) h->d_spill_slot.reset();  // (never a table that exists but was not filled)
+    HIP_TRY(e);
+  }
   if (saves && (!h->d_spill.get() || h->spill_stride < v.spill_stride)) {
     const int cap = h->max_batch < SPILL_SLOT_CAP ? h->max_batch : SPILL_SLOT_CAP;
     HIP_TRY(h->d_spill.reserve((size_t)cap * v.spill_stride, stream, /*whole_device=*/true));
@@ -302,7 +320,7 @@ int enqueue_command_sweep(hmpc_handle *h, hipStream_t stream, int group_size) {
   const bool small = h->max_stance >= 0 && h->max_stance <= 60;
   const int vi = fast_variant(/*long_h=*/false, small ? 0 : 1, /*sweep=*/true);
   const size_t need = (size_t)(h->batch / group_size) * 36 * (size_t)variants()[vi].nt * sizeof(double);  // (V2_SWEEP_120 has the wider workgroups)
-  HIP_TRY(h->d_sweep_m.reserve(need, stream, /*whole_device=*/false));
+  RC_TRY(grow(h, h->d_sweep_m, need));
   LaunchOpt o;
   o.sweep_k = group_size;  // (natural order inside a sweep)
   // whatever a sweep flags is repaired as an independent instance (its record is complete).  Sweeps save nothing: no continuation; their
@@ -313,7 +331,8 @@ int enqueue_command_sweep(hmpc_handle *h, hipStream_t stream, int group_size) {
 // The host-driven repair: the status words come to the host, what needs_repair (hmpc_plan.h) is re-solved over an uploaded list with the
 // same steps as the device-side chain's, then the steps only the host drives.  It repairs the solve in place: no result is invalidated.
 int resolve_failed(hmpc_handle *h, int *n_resolved) {
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  int src = settle(h);
+  if (src != HMPC_OK) return src;
   std::vector<uint32_t> st(h->batch);
   HIP_TRY(hipMemcpy(st.data(), h->d_status.get(), (size_t)h->batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<int> idx;
@@ -344,7 +363,7 @@ int resolve_failed(hmpc_handle *h, int *n_resolved) {
   rc = safe_pass(h, h->last_stream, so);
   so.skip_ok = 0;
   if (rc != HMPC_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  if ((src = settle(h)) != HMPC_OK) return src;
   if (n_resolved) *n_resolved = (int)idx.size();
   // each later pass: copy the status words back, keep the members of idx whose code `keep` accepts, upload them, run `pass` over
   // them (a copy of `so` with that list), synchronise; *ran = whether anything was kept
@@ -359,9 +378,7 @@ int resolve_failed(hmpc_handle *h, int *n_resolved) {
     LaunchOpt o = so;
     o.n_list = (int)sub.size();
     const int prc = pass(o);
-    if (prc != HMPC_OK) return prc;
-    HIP_TRY(hipStreamSynchronize(h->last_stream));
-    return HMPC_OK;
+    return prc != HMPC_OK ? prc : settle(h);
   };
   bool ran = false;
   // A Hessian that is not positive definite (found by the safe variants' sweeps: HMPC_S_INDEFINITE; the fast variants diverge on it

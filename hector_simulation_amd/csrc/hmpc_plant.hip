@@ -60,10 +60,10 @@ static int own_rollout_buffers(hmpc_handle *h, int n_ticks) {
   const size_t rows = (size_t)h->max_batch * (size_t)n_ticks;
   if (n_ticks > h->roll_own_ticks) {
     if (logs_into_own_buffers(h, h->roll_last)) h->roll_last = {}, h->roll_last_ticks = 0, h->roll_last_batch = 0;
-    HIP_TRY(h->d_roll_state.reserve(rows * 12 * sizeof(double), h->last_stream, /*whole_device=*/false));
-    HIP_TRY(h->d_roll_wrench.reserve(rows * 12 * sizeof(float), h->last_stream, false));
-    HIP_TRY(h->d_roll_status.reserve(rows * sizeof(uint32_t), h->last_stream, false));
-    HIP_TRY(h->d_roll_taulog.reserve(rows * 10 * sizeof(double), h->last_stream, false));
+    RC_TRY(grow(h, h->d_roll_state, rows * 12 * sizeof(double)));
+    RC_TRY(grow(h, h->d_roll_wrench, rows * 12 * sizeof(float)));
+    RC_TRY(grow(h, h->d_roll_status, rows * sizeof(uint32_t)));
+    RC_TRY(grow(h, h->d_roll_taulog, rows * 10 * sizeof(double)));
     h->roll_own_ticks = n_ticks;
   }
   if (!h->d_roll_summary.get()) HIP_TRY(h->d_roll_summary.alloc((size_t)h->max_batch * 4));
@@ -106,8 +106,8 @@ int hmpc_plant_step_device(hmpc_handle *h, void *device_ticks, int batch, const 
   if (rc != HMPC_OK) return rc;
   if (batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_plant_step((hmpc_tick_inputs *)device_ticks, a, (hipStream_t)stream));
-  h->last_stream = (hipStream_t)stream;
   return HMPC_OK;
 }
 
@@ -132,6 +132,7 @@ int hmpc_rollout_device(hmpc_handle *h, void *device_ticks, int batch, int n_tic
   if (!h || !device_ticks || !plant) return HMPC_E_ARG;
   if (n_ticks < 1 || ticks_per_step < 1 || subtick0 < 0 || plant->substeps < 1 || h->nc != 2 || batch < 0 || batch > h->max_batch) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));  // (first: a log that has to grow then waits for this stream alone)
   hmpc_rollout_log lg;
   if (log) lg = *log;
   else {
@@ -160,7 +161,6 @@ int hmpc_rollout_device(hmpc_handle *h, void *device_ticks, int batch, int n_tic
     HIP_TRY(hmpc::launch_plant_step((hmpc_tick_inputs *)device_ticks, a, s));
     shift = pl.advance_gait;
   }
-  h->last_stream = s;
   return HMPC_OK;
 }
 
@@ -169,7 +169,7 @@ int hmpc_download_rollout(hmpc_handle *h, double *state, float *wrench, uint32_t
   const hmpc_rollout_log &lg = h->roll_last;
   if ((state && !lg.state) || (wrench && !lg.wrench) || (status && !lg.status) || (tau && !lg.tau) || (summary && !lg.summary)) return HMPC_E_ARG;
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->last_stream));
+  RC_TRY(settle(h));
   const size_t rows = (size_t)h->roll_last_batch * (size_t)h->roll_last_ticks;
   if (rows == 0) return HMPC_OK;
   if (state) HIP_TRY(hipMemcpy(state, lg.state, rows * 12 * sizeof(double), hipMemcpyDeviceToHost));

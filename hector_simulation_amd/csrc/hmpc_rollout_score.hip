@@ -47,8 +47,8 @@ int hmpc_rollout_score_device(hmpc_handle *h, const void *device_ticks0, int bat
   h->rscore_batch = batch, h->rscore_ticks = n_ticks;
   if (batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_rollout_score(a, (hipStream_t)stream));
-  h->last_stream = (hipStream_t)stream;
   return HMPC_OK;
 }
 
@@ -67,8 +67,8 @@ int hmpc_rollout_select_device(hmpc_handle *h, const double *device_score, const
   a.groups = batch / group_size, a.group_size = group_size;
   if (batch == 0) return HMPC_OK;
   HIP_TRY(hipSetDevice(h->device));
+  RC_TRY(enter_stream(h, (hipStream_t)stream));
   HIP_TRY(hmpc::launch_rollout_select(a, (hipStream_t)stream));
-  h->last_stream = (hipStream_t)stream;
   return HMPC_OK;
 }
 
@@ -86,12 +86,11 @@ int hmpc_rollout_sweep_device(hmpc_handle *h, const void *device_ticks, int n_st
   if (!h->d_rsw_cost.get()) HIP_TRY(h->d_rsw_cost.alloc((size_t)h->max_batch * 4));
   if (!h->d_rsw_score.get()) HIP_TRY(h->d_rsw_score.alloc((size_t)h->max_batch));
   const hipStream_t s = (hipStream_t)stream;
+  RC_TRY(enter_stream(h, s));  // (before the expansions: they write the handle's tick buffers, which the previous sweep's rollout may still read)
   hmpc_tick_inputs *now = (hmpc_tick_inputs *)h->d_rsw_ticks.get(), *before = (hmpc_tick_inputs *)h->d_rsw_ticks0.get();
   HIP_TRY(hmpc::launch_expand_ticks((const hmpc_tick_inputs *)device_ticks, n_states, device_commands, K, now, nullptr, s));
   HIP_TRY(hmpc::launch_expand_ticks((const hmpc_tick_inputs *)device_ticks, n_states, device_commands, K, before, nullptr, s));
-  // (last_stream is still the stream of the handle's previous work here: a log that has to grow waits for THAT stream before it frees)
   int rc = hmpc_rollout_device(h, now, batch, n_ticks, dtMPC, ticks_per_step, subtick0, plant, /*log=*/nullptr, stream);
-  h->last_stream = s;
   if (rc != HMPC_OK) return rc;
   h->rsw_batch = batch;
   rc = hmpc_rollout_score_device(h, before, batch, n_ticks, cost, nullptr, h->d_rsw_cost.get(), h->d_rsw_score.get(), stream);

@@ -172,7 +172,7 @@ int hmpc_pack_record_ex(void *record, int horizon, int n_contacts, const double 
                         const double *state_trajectory, const double *Alpha_K, const int *gait, const double *Rhand,
                         double f_max_hand);
 int hmpc_destroy(hmpc_handle *h);
-/* host records -> device (synchronous copy on the handle's stream) */
+/* host records -> device: waits for whatever is enqueued for the handle (STREAMS below), then copies; the copy has finished on return */
 int hmpc_upload_records(hmpc_handle *h, const void *host_records, int batch);
 /* use records that already live in HBM (no copy; pointer must stay valid until the solve finishes) */
 int hmpc_set_device_records(hmpc_handle *h, const void *device_records, int batch);
@@ -303,6 +303,23 @@ int hmpc_set_handover(hmpc_handle *h, int on);
 int hmpc_set_device_repair(hmpc_handle *h, int on);
 /* NOTE (device repair): the list of flagged instances and its counter belong to the handle -- keep the solves of ONE handle
  * on one stream at a time (use one handle per stream to overlap launches, as bench.py does). */
+/* STREAMS.  A handle remembers the stream of its last enqueued call -- every entry point that takes a `stream`, hmpc_download_async and
+ * the upload variants included; the blocking host-pointer entries (hmpc_build_records, hmpc_body_wrench, hmpc_leg_torques,
+ * hmpc_debug_assemble) enqueue on the null stream.  A call waits on the host for that stream FIRST
+ *   - if it frees or reallocates device memory the handle owns (a buffer that has to grow: the groups' H^-1 of a command sweep, the safe
+ *     variants' scratch, the handle's own rollout log; hmpc_destroy);
+ *   - if it writes device memory the handle owns from the host (hmpc_upload_records, hmpc_build_records, hmpc_body_wrench,
+ *     hmpc_leg_torques, the host-driven repair of hmpc_resolve_failed / hmpc_download) or reads it to the host (every hmpc_download_*);
+ *   - if it enqueues on ANOTHER stream than that one: what it enqueues writes the handle's memory from the new stream.
+ * So a handle may be moved from one stream to the next, and a blocking entry may be called while work is pending, without any
+ * synchronisation by the caller FOR THE HANDLE'S MEMORY.  A call on the SAME stream as the one before waits for nothing and enqueues
+ * nothing extra: stream order does it (one handle per stream, as bench.py runs, never waits).  hmpc_reset_tick_warm_start does not wait
+ * either: it clears the saved sets on the handle's stream, behind the solve that may still write them.  Buffers that are filled when
+ * they are allocated (hmpc_create, the first hmpc_set_tick_warm_start(on) / hmpc_set_device_repair(on)) are complete when the call
+ * returns: a solve on any stream may follow at once.  (The hand-over slot table of a handle's first solve is filled on that solve's stream.)
+ * What stays the caller's business: the caller's OWN buffers (records, outputs, seeds, ticks, logs handed in by pointer -- valid and
+ * ordered until the stream has passed them); two calls of one handle in flight on two streams at once (see the note above: the second
+ * call waits for the first, it does not overlap it); and where a result belongs -- put a result call on the solve's stream. */
 /* Stream-ordered variants for pipelining host batches (two handles on two streams: the copies of one overlap the solve
  * of the other).  The host buffers should be pinned (hipHostMalloc / hipHostRegister) for the copies to be asynchronous
  * and must stay valid until the stream reaches them.  hmpc_download_async does not run the safe pass: check the status
