@@ -237,29 +237,30 @@ def load():
     L.hmpc_group_last_error.restype = C.c_char_p
     L.hmpc_debug_phase_cycles.argtypes = [vp, vp]
     L.hmpc_debug_handover_slots.argtypes = [vp, vp]
+    # the set, get and download entries of every derived result: one pointer per array of its family (interface.RESULTS), behind the handle
+    # and, for the multi-seed adjoint, the seed count; the selection's get reports its groups last; the chain passes its struct
+    from .interface import RESULTS  # (here, not at the top: interface.py imports this module)
+
+    for family, arrays in RESULTS.items():
+        if family == "adjoint_chain_multi":
+            continue
+        count = family == "adjoint_multi"
+        getattr(L, "hmpc_set_device_" + family).argtypes = [vp] + [ci] * count + [vp] * len(arrays)
+        getattr(L, "hmpc_download_" + family).argtypes = [vp] + [vp] * len(arrays)
+        if family != "first_order":  # (the one family without a get)
+            getattr(L, "hmpc_get_device_" + family).argtypes = ([vp] + [C.POINTER(ci)] * count + [C.POINTER(vp)] * len(arrays)
+                                                                + [C.POINTER(ci)] * (family == "selection"))
     L.hmpc_predict_states.argtypes = [vp, vp]
-    L.hmpc_set_device_prediction.argtypes = [vp, vp, vp]
-    L.hmpc_get_device_prediction.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.hmpc_download_prediction.argtypes = [vp, vp, vp]
     L.hmpc_legacy_predicted_state.argtypes = [ci, ci]
     L.hmpc_legacy_predicted_state.restype = cd
     L.hmpc_sweep_select.argtypes = [vp, ci, vp, vp]
-    L.hmpc_set_device_selection.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.hmpc_get_device_selection.argtypes = [vp] + [C.POINTER(vp)] * 5 + [C.POINTER(ci)]
-    L.hmpc_download_selection.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hmpc_tick_sweep_device.argtypes = [vp, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp]
     L.hmpc_constraint_margins.argtypes = [vp, vp]
-    L.hmpc_set_device_margins.argtypes = [vp, vp, vp, vp]
-    L.hmpc_get_device_margins.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.hmpc_download_margins.argtypes = [vp, vp, vp, vp]
     L.hmpc_margin_penalty.argtypes = [vp, vp, vp, vp, vp]
     L.hmpc_set_sweep_margin_floor.argtypes = [vp, vp]
     L.hmpc_legacy_constraint_slack.argtypes = [ci, ci, ci]
     L.hmpc_legacy_constraint_slack.restype = cd
     L.hmpc_kkt_certificate.argtypes = [vp, vp]
-    L.hmpc_set_device_certificate.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.hmpc_get_device_certificate.argtypes = [vp] + [C.POINTER(vp)] * 5
-    L.hmpc_download_certificate.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hmpc_set_certificate_tolerance.argtypes = [vp, cd]
     L.hmpc_certificate_penalty.argtypes = [vp, vp, vp, vp, vp]
     L.hmpc_set_sweep_certificate_ceiling.argtypes = [vp, vp]
@@ -268,35 +269,15 @@ def load():
     L.hmpc_legacy_stationarity.argtypes = []
     L.hmpc_legacy_stationarity.restype = cd
     L.hmpc_feedback_gains.argtypes = [vp, vp]
-    L.hmpc_set_device_gains.argtypes = [vp, vp, vp, vp, vp]
-    L.hmpc_get_device_gains.argtypes = [vp] + [C.POINTER(vp)] * 4
-    L.hmpc_download_gains.argtypes = [vp, vp, vp, vp, vp]
     L.hmpc_first_order_wrench.argtypes = [vp, vp, vp]
-    L.hmpc_set_device_first_order.argtypes = [vp, vp, vp]
-    L.hmpc_download_first_order.argtypes = [vp, vp, vp]
     L.hmpc_legacy_feedback_gain.argtypes = [ci, ci]
     L.hmpc_legacy_feedback_gain.restype = cd
     L.hmpc_solve_adjoint.argtypes = [vp, vp, vp]
-    L.hmpc_set_device_adjoint.argtypes = [vp] + [vp] * 6
-    L.hmpc_get_device_adjoint.argtypes = [vp] + [C.POINTER(vp)] * 6
-    L.hmpc_download_adjoint.argtypes = [vp] + [vp] * 6
     L.hmpc_solve_adjoint_multi.argtypes = [vp, vp, ci, vp]
-    L.hmpc_set_device_adjoint_multi.argtypes = [vp, ci] + [vp] * 6
-    L.hmpc_get_device_adjoint_multi.argtypes = [vp, C.POINTER(ci)] + [C.POINTER(vp)] * 6
-    L.hmpc_download_adjoint_multi.argtypes = [vp] + [vp] * 6
     L.hmpc_select_adjoint_seed.argtypes = [vp, ci]
     L.hmpc_adjoint_model.argtypes = [vp, vp]
-    L.hmpc_set_device_adjoint_model.argtypes = [vp] + [vp] * 5
-    L.hmpc_get_device_adjoint_model.argtypes = [vp] + [C.POINTER(vp)] * 5
-    L.hmpc_download_adjoint_model.argtypes = [vp] + [vp] * 5
     L.hmpc_adjoint_limits.argtypes = [vp, vp, vp]
-    L.hmpc_set_device_adjoint_limits.argtypes = [vp] + [vp] * 6
-    L.hmpc_get_device_adjoint_limits.argtypes = [vp] + [C.POINTER(vp)] * 6
-    L.hmpc_download_adjoint_limits.argtypes = [vp] + [vp] * 6
     L.hmpc_adjoint_record.argtypes = [vp, vp]
-    L.hmpc_set_device_adjoint_record.argtypes = [vp] + [vp] * 3
-    L.hmpc_get_device_adjoint_record.argtypes = [vp] + [C.POINTER(vp)] * 3
-    L.hmpc_download_adjoint_record.argtypes = [vp] + [vp] * 3
     L.hmpc_adjoint_chain_multi.argtypes = [vp, vp, vp]
     L.hmpc_set_device_adjoint_chain_multi.argtypes = [vp, ci, C.POINTER(AdjointChain)]
     L.hmpc_get_device_adjoint_chain_multi.argtypes = [vp, C.POINTER(ci), C.POINTER(AdjointChain)]

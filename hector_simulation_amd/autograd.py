@@ -25,7 +25,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import records
+from . import _lib, records
 
 
 def _buffers(mpc, device):
@@ -34,8 +34,7 @@ def _buffers(mpc, device):
     writes."""
     buf = getattr(mpc, "_autograd_buffers", None)
     if buf is None:
-        b, hz, u = mpc.max_batch, mpc.horizon, 6 * mpc.contacts
-        shapes = dict(grad_x0=(b, 13), grad_traj=(b, hz, 12), grad_weights=(b, 12), grad_alpha=(b, u), dir=(b, hz, u), summary=(b, 2))
+        shapes = mpc.result_shapes("adjoint", (mpc.max_batch,))
         buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
         mpc._autograd_buffers = buf
     if mpc.get_device_adjoint() != {k: buf[k].data_ptr() for k in mpc.ADJOINT_KEYS}:
@@ -47,8 +46,7 @@ def _model_buffers(mpc, device):
     """The same for the model gradients (``set_device_adjoint_model``)."""
     buf = getattr(mpc, "_autograd_model_buffers", None)
     if buf is None:
-        b, nc = mpc.max_batch, mpc.contacts
-        shapes = dict(grad_A=(b, 13, 13), grad_B=(b, 13, 6 * nc), grad_r=(b, 3, nc), grad_params=(b, 4), costate=(b, 2, 13))
+        shapes = mpc.result_shapes("adjoint_model", (mpc.max_batch,))
         buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
         mpc._autograd_model_buffers = buf
     if mpc.get_device_adjoint_model() != {k: buf[k].data_ptr() for k in mpc.MODEL_ADJOINT_KEYS}:
@@ -60,9 +58,7 @@ def _limit_buffers(mpc, device):
     """The same for the limit gradients (``set_device_adjoint_limits``)."""
     buf = getattr(mpc, "_autograd_limit_buffers", None)
     if buf is None:
-        b, nc, hz = mpc.max_batch, mpc.contacts, mpc.horizon
-        shapes = dict(grad_limits=(b, 3 + nc), grad_Fc=(b, 8 * nc, 6 * nc), grad_bound=(b, hz, nc, 10), nu=(b, hz, nc, 10), summary=(b, 3))
-        shapes["lambda"] = (b, hz, nc, 10)
+        shapes = mpc.result_shapes("adjoint_limits", (mpc.max_batch,))
         buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
         mpc._autograd_limit_buffers = buf
     if mpc.get_device_adjoint_limits() != {k: buf[k].data_ptr() for k in mpc.LIMIT_ADJOINT_KEYS}:
@@ -74,9 +70,7 @@ def _record_buffers(mpc, device):
     """The same for the record gradients (``set_device_adjoint_record``)."""
     buf = getattr(mpc, "_autograd_record_buffers", None)
     if buf is None:
-        b, nc = mpc.max_batch, mpc.contacts
-        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
-        shapes = dict(grad_record=(b, nf + 12 * mpc.horizon), grad_frames=(b, 1 + nc, 3, 3), grad_rpy=(b, 3))
+        shapes = mpc.result_shapes("adjoint_record", (mpc.max_batch,))
         buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
         mpc._autograd_record_buffers = buf
     if mpc.get_device_adjoint_record() != {k: buf[k].data_ptr() for k in mpc.RECORD_ADJOINT_KEYS}:
@@ -88,9 +82,8 @@ def _multi_buffers(mpc, device, n_seeds):
     """The same for the multi-seed adjoint (``set_device_adjoint_multi``), with room for ``n_seeds`` slices of max_batch rows."""
     buf = getattr(mpc, "_autograd_multi_buffers", None)
     if buf is None or buf["summary"].shape[0] < n_seeds:
-        b, hz, u = mpc.max_batch, mpc.horizon, 6 * mpc.contacts
-        shapes = dict(grad_x0=(b, 13), grad_traj=(b, hz, 12), grad_weights=(b, 12), grad_alpha=(b, u), dir=(b, hz, u), summary=(b, 2))
-        buf = {k: torch.zeros((n_seeds,) + s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        shapes = mpc.result_shapes("adjoint_multi", (n_seeds, mpc.max_batch))
+        buf = {k: torch.zeros(s, dtype=torch.float64, device=device) for k, s in shapes.items()}
         mpc._autograd_multi_buffers = buf
     now = mpc.get_device_adjoint_multi()
     if {k: now[k] for k in mpc.ADJOINT_KEYS} != {k: buf[k].data_ptr() for k in mpc.ADJOINT_KEYS}:
@@ -102,11 +95,8 @@ def _chain_buffers(mpc, device, n_seeds):
     """The same for the compact arrays of the multi-seed chain (``set_device_adjoint_chain_multi``); no detail array is asked for."""
     buf = getattr(mpc, "_autograd_chain_buffers", None)
     if buf is None or buf["grad_rpy"].shape[0] < n_seeds:
-        b, nc = mpc.max_batch, mpc.contacts
-        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
-        shapes = dict(grad_record=(b, nf + 12 * mpc.horizon), grad_frames=(b, 1 + nc, 3, 3), grad_rpy=(b, 3), grad_params=(b, 4),
-                      grad_limits=(b, 3 + nc), limit_summary=(b, 3))
-        buf = {k: torch.zeros((n_seeds,) + s, dtype=torch.float64, device=device) for k, s in shapes.items()}
+        shapes = mpc.result_shapes("adjoint_chain_multi", (n_seeds, mpc.max_batch))
+        buf = {k: torch.zeros(shapes[k], dtype=torch.float64, device=device) for k in _lib.CHAIN_COMPACT}  # (no detail array)
         mpc._autograd_chain_buffers = buf
     now = mpc.get_device_adjoint_chain_multi()
     want = {k: (buf[k].data_ptr() if k in buf else 0) for k in mpc.CHAIN_KEYS}

@@ -1,5 +1,6 @@
 // hmpc_handle.h -- what the host units of libhector_mpc_hip.so share and nobody outside sees: the handle, the error string, the options
-// of one launch, and what hmpc_launch.hip (what a solve enqueues) offers hmpc_capi.hip (the batched C ABI).  Everything here is hidden.
+// of one launch, and what hmpc_launch.hip (what a solve enqueues) offers hmpc_capi.hip (the batched C ABI) and hmpc_results.hip (the results
+// derived from a solve).  Everything here is hidden.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,7 @@
 #include "hmpc_pose_adjoint.h"
 #include "hmpc_margins.h"
 #include "hmpc_plan.h"
+#include "hmpc_results.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -97,74 +99,33 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   hmpc_params params{};  // robot / contact constants (hmpc_set_params; defaults = the reference's literals)
   const float *d_mu_inst = nullptr;  // hmpc_set_instance_mu: per-instance friction parameter in HBM (caller-owned), nullptr = params.mu for all
   DeviceBuffer<double> d_reg_rho;  // Hessians that are not positive definite: the pivot the safe variant found, then rho of hmpc_resolve_failed's regularisation steps, per instance (allocated with the first list launch)
-  ResultState results;  // which of the results below belong to the current batch and its last solve (hmpc_plan.h)
-  // prediction (hmpc_predict_states): states [max_batch][horizon][13] binary32 and cost [max_batch][2] binary64, to the caller's buffers
-  // (hmpc_set_device_prediction) or the handle's own, allocated by the first call that needs them
-  OutputBuffer<float> d_pred_states;
-  OutputBuffer<double> d_pred_cost;
-  // selection (hmpc_sweep_select): one row per sweep group, to the caller's buffers (hmpc_set_device_selection) or the handle's own,
-  // allocated for max_batch groups by the first call that needs them
-  OutputBuffer<int32_t> d_sel_index;
-  OutputBuffer<double> d_sel_score;
-  OutputBuffer<float> d_sel_forces;
-  OutputBuffer<uint32_t> d_sel_status;
-  OutputBuffer<float> d_sel_states;
-  // constraint margins (hmpc_constraint_margins): slack [max_batch][horizon][nc][10] and summary [max_batch][6] binary64, where
-  // [max_batch][6], to the caller's buffers (hmpc_set_device_margins) or the handle's own, allocated by the first call that needs them
-  OutputBuffer<double> d_mar_slack, d_mar_summary;
-  OutputBuffer<int32_t> d_mar_where;
+  ResultState results;  // which of the derived results belong to the current batch and its last solve (hmpc_plan.h)
+  // The results derived from a solve (hmpc_results.hip).  Their families, arrays and shapes are the table of hmpc_results.h and stated
+  // nowhere else; d_result[family][k] is array k of a family of [0, N_SINGLE): the caller's buffer (hmpc_set_device_<family>) or the
+  // handle's own, allocated for max_batch rows by the first call that needs it.
+  OutputBuffer<unsigned char> d_result[hmpc::N_SINGLE][hmpc::MAX_SINGLE_ARRAYS];
   // hmpc_set_sweep_margin_floor: hmpc_tick_sweep_device masks the commands whose margins miss the floor (penalty: scratch of the handle)
   bool sweep_floor_on = false;
   double sweep_floor[hmpc::MARGIN_CLASSES] = {};
   DeviceBuffer<double> d_sweep_penalty;
-  // KKT certificate (hmpc_kkt_certificate): grad [max_batch][horizon][6 nc], lambda [max_batch][horizon][nc][10], resid
-  // [max_batch][horizon][nc][6] and summary [max_batch][4] binary64, where [max_batch][2], to the caller's buffers
-  // (hmpc_set_device_certificate) or the handle's own, allocated by the first call that needs them
-  OutputBuffer<double> d_cert_grad, d_cert_lambda, d_cert_resid, d_cert_summary;
-  OutputBuffer<int32_t> d_cert_where;
   double cert_act_tol = 1e-3;  // hmpc_set_certificate_tolerance
   // hmpc_set_sweep_certificate_ceiling: hmpc_tick_sweep_device masks the commands whose certificate exceeds the ceiling (same scratch)
   bool sweep_ceil_on = false;
   double sweep_ceil[hmpc::CERT_CEILS] = {};
-  // feedback gains (hmpc_feedback_gains): gain [max_batch][6 nc][13], ref_gain [max_batch][horizon][6 nc][12] and summary [max_batch][2]
-  // binary64, free_dims [max_batch][horizon]; the first-order wrench (hmpc_first_order_wrench): wrench [max_batch][6 nc] binary32,
-  // worst_slack [max_batch] binary64; to the caller's buffers (hmpc_set_device_gains, hmpc_set_device_first_order) or the handle's
-  // own, allocated by the first call that needs them
-  OutputBuffer<double> d_fb_gain, d_fb_ref, d_fb_summary;
-  OutputBuffer<int32_t> d_fb_free;
-  OutputBuffer<float> d_fo_wrench;
-  OutputBuffer<double> d_fo_worst;
-  // adjoint (hmpc_solve_adjoint): grad_x0 [max_batch][13], grad_traj [max_batch][horizon][12], grad_weights [max_batch][12], grad_alpha
-  // [max_batch][6 nc], dir [max_batch][horizon][6 nc] and summary [max_batch][2] binary64; to the caller's buffers
-  // (hmpc_set_device_adjoint) or the handle's own, allocated by the first call that needs them
-  OutputBuffer<double> d_adj_x0, d_adj_traj, d_adj_weights, d_adj_alpha, d_adj_dir, d_adj_summary;
-  // multi-seed adjoint (hmpc_solve_adjoint_multi): the six arrays of the adjoint once per seed, seed-major over the CURRENT batch
-  // ([n_seeds][batch][...]), in the order grad_x0, grad_traj, grad_weights, grad_alpha, dir, summary; to the caller's buffers
-  // (hmpc_set_device_adjoint_multi, room for adjm_caller_seeds slices) or the handle's own, reserved for (n_seeds, max_batch) by the
-  // launch that needs them (adjm_own_seeds = what they hold room for)
-  DeviceBuffer<double> d_adjm_own[6];
-  double *adjm_caller[6] = {};
+  // multi-seed adjoint (hmpc_solve_adjoint_multi): the arrays of the adjoint once per seed, seed-major over the CURRENT batch
+  // ([n_seeds][batch][...]); to the caller's buffers (hmpc_set_device_adjoint_multi, room for adjm_caller_seeds slices) or the handle's
+  // own, reserved for (n_seeds, max_batch) by the launch that needs them (adjm_own_seeds = what they hold room for)
+  DeviceBuffer<double> d_adjm_own[hmpc::ADJOINT_ARRAYS];
+  double *adjm_caller[hmpc::ADJOINT_ARRAYS] = {};
   int adjm_caller_seeds = 0, adjm_own_seeds = 0;
-  // model gradients (hmpc_adjoint_model): grad_A [max_batch][13][13], grad_B [max_batch][13][6 nc], grad_r [max_batch][3][nc], grad_params
-  // [max_batch][4] and costate [max_batch][2][13] binary64; to the caller's buffers (hmpc_set_device_adjoint_model) or the handle's own,
-  // allocated by the first call that needs them
-  OutputBuffer<double> d_madj_A, d_madj_B, d_madj_r, d_madj_params, d_madj_costate;
-  // limit gradients (hmpc_adjoint_limits): grad_limits [max_batch][3 + nc], grad_Fc [max_batch][8 nc][6 nc], grad_bound, lambda and nu
-  // [max_batch][horizon][nc][10] and summary [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_limits) or the
-  // handle's own, allocated by the first call that needs them
-  OutputBuffer<double> d_ladj_limits, d_ladj_Fc, d_ladj_bound, d_ladj_lambda, d_ladj_nu, d_ladj_summary;
-  // record gradients (hmpc_adjoint_record): grad_record [max_batch][NF + 12 horizon], grad_frames [max_batch][1 + nc][9] and grad_rpy
-  // [max_batch][3] binary64; to the caller's buffers (hmpc_set_device_adjoint_record) or the handle's own, allocated by the first call
-  // that needs them
-  OutputBuffer<double> d_padj_record, d_padj_frames, d_padj_rpy;
-  // chain of the multi-seed adjoint (hmpc_adjoint_chain_multi): the fourteen arrays of struct hmpc_adjoint_chain in its member order,
-  // seed-major over the CURRENT batch; the six compact ones to the caller's buffers (hmpc_set_device_adjoint_chain_multi, room for
-  // chain_caller_seeds slices) or the handle's own, reserved for (n_seeds, max_batch) by the launch that needs them (chain_own_seeds =
-  // what they hold room for); the eight detail ones to the caller's buffers only.  chain_written = the arrays the chain that stands wrote.
-  DeviceBuffer<double> d_chain_own[6];
-  double *chain_caller[14] = {};
+  // chain of the multi-seed adjoint (hmpc_adjoint_chain_multi): the arrays of struct hmpc_adjoint_chain in its member order, seed-major
+  // over the CURRENT batch; the compact ones to the caller's buffers (hmpc_set_device_adjoint_chain_multi, room for chain_caller_seeds
+  // slices) or the handle's own, reserved for (n_seeds, max_batch) by the launch that needs them (chain_own_seeds = what they hold room
+  // for); the detail ones to the caller's buffers only.  chain_written = the arrays the chain that stands wrote.
+  DeviceBuffer<double> d_chain_own[hmpc::CHAIN_COMPACT];
+  double *chain_caller[hmpc::CHAIN_ARRAYS] = {};
   int chain_caller_seeds = 0, chain_own_seeds = 0;
-  bool chain_written[14] = {};
+  bool chain_written[hmpc::CHAIN_ARRAYS] = {};
   // closed loop (hmpc_rollout_device, hmpc_plant.hip): a tick's clamped world_position_desired [max_batch][2] and torques [max_batch][10]
   // between its solve and its plant step; the handle's own log buffers, for max_batch x roll_own_ticks rows (hmpc_get_device_rollout);
   // the caller's (hmpc_set_device_rollout); and where the last rollout logged, which is what hmpc_download_rollout copies

@@ -140,73 +140,125 @@ inline bool params_ok(const hmpc_params &p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- what is still valid
-// Which results on the device belong to the CURRENT batch and its LAST solve.  The graph: batch -> solve -> prediction -> selection,
-// solve -> margins, solve -> certificate, solve -> gains -> first-order wrench, solve -> adjoint -> model gradients, adjoint -> limit gradients, solve -> multi-seed adjoint -> (a selected slice as the adjoint), multi-seed adjoint -> chain (the model, limit and record gradients of every seed), (adjoint, model gradients, limit gradients) -> record gradients; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the facts.
-// (hmpc_resolve_failed repairs the solve in place and invalidates nothing; a bare launch that is no solve -- hmpc_debug_phase_cycles
-//  without device repair -- does not count as one.)
+// Which results on the device belong to the CURRENT batch and its LAST solve.  Every result is a node of one graph, stated once as the
+// table of each node's parents below; whatever replaces a node makes everything behind it stale.  Nothing outside this struct writes the
+// facts.  (hmpc_resolve_failed repairs the solve in place and invalidates nothing; a bare launch that is no solve --
+// hmpc_debug_phase_cycles without device repair -- does not count as one.)
+enum class ResultNode : int { SOLVE, PREDICTION, SELECTION, MARGINS, CERTIFICATE, GAINS, FIRST_ORDER, ADJOINT, MODEL_ADJOINT, LIMIT_ADJOINT, RECORD_ADJOINT, ADJOINT_MULTI, ADJOINT_CHAIN, N };
+constexpr int RESULT_NODES = (int)ResultNode::N, RESULT_MAX_PARENTS = 3;
+// the parents of every node, in the order of ResultNode (N = none; the solve's parent is the batch itself: on_batch).  The record
+// gradients read the adjoint, the model gradients and the limit gradients; the chain reads the multi-seed adjoint alone.
+inline constexpr ResultNode RESULT_PARENTS[RESULT_NODES][RESULT_MAX_PARENTS] = {
+    /* SOLVE */ {ResultNode::N, ResultNode::N, ResultNode::N},
+    /* PREDICTION */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* SELECTION */ {ResultNode::PREDICTION, ResultNode::N, ResultNode::N},
+    /* MARGINS */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* CERTIFICATE */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* GAINS */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* FIRST_ORDER */ {ResultNode::GAINS, ResultNode::N, ResultNode::N},
+    /* ADJOINT */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* MODEL_ADJOINT */ {ResultNode::ADJOINT, ResultNode::N, ResultNode::N},
+    /* LIMIT_ADJOINT */ {ResultNode::ADJOINT, ResultNode::N, ResultNode::N},
+    /* RECORD_ADJOINT */ {ResultNode::ADJOINT, ResultNode::MODEL_ADJOINT, ResultNode::LIMIT_ADJOINT},
+    /* ADJOINT_MULTI */ {ResultNode::SOLVE, ResultNode::N, ResultNode::N},
+    /* ADJOINT_CHAIN */ {ResultNode::ADJOINT_MULTI, ResultNode::N, ResultNode::N},
+};
+constexpr uint32_t result_bit(ResultNode n) { return 1u << (int)n; }
+constexpr bool result_behind(ResultNode d, ResultNode a) {  // d is a descendant of a (parents precede their children in ResultNode)
+  for (int k = 0; k < RESULT_MAX_PARENTS; ++k) {
+    const ResultNode p = RESULT_PARENTS[(int)d][k];
+    if (p != ResultNode::N && (p == a || result_behind(p, a))) return true;
+  }
+  return false;
+}
+struct ResultDescendants {
+  uint32_t of[RESULT_NODES];  // result_bit of every node behind node n
+};
+constexpr ResultDescendants result_descendants() {
+  ResultDescendants t{};
+  for (int a = 0; a < RESULT_NODES; ++a)
+    for (int d = 0; d < RESULT_NODES; ++d)
+      if (result_behind((ResultNode)d, (ResultNode)a)) t.of[a] |= 1u << d;
+  return t;
+}
+inline constexpr ResultDescendants RESULT_BEHIND = result_descendants();  // (worked out by the compiler: a solve pays one AND for it)
+
 class ResultState {
  public:
-  void on_batch() { solve_enqueued = predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = adjoint_chain_enqueued = false, adjoint_selected = -1; }          // the handle holds another batch
-  void on_solve() { solve_enqueued = true, predict_enqueued = select_enqueued = margins_enqueued = certificate_enqueued = gains_enqueued = first_order_enqueued = adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = adjoint_multi_enqueued = adjoint_chain_enqueued = false, adjoint_selected = -1; }    // every solve of a batch: its forces are newer than anything derived
-  void on_predict() { predict_enqueued = true, select_enqueued = false; }                      // (a selection made before this prediction read an older one)
-  void on_select(int groups) { select_enqueued = true, select_groups = groups; }
-  void on_margins() { margins_enqueued = true; }
-  void on_certificate() { certificate_enqueued = true; }
-  void on_gains() { gains_enqueued = true, first_order_enqueued = false; }  // (a wrench made before these gains read older ones)
-  void on_first_order() { first_order_enqueued = true; }
-  void on_adjoint() { adjoint_enqueued = true, adjoint_selected = -1, model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }  // (independent of the gains and the wrench; model and limit gradients made before this adjoint read an older dir)
-  void on_model_adjoint() { model_adjoint_enqueued = true, record_adjoint_enqueued = false; }  // (record gradients made before these read older ones)
-  void on_limit_adjoint() { limit_adjoint_enqueued = true, record_adjoint_enqueued = false; }  // (independent of the model gradients)
-  void on_record_adjoint() { record_adjoint_enqueued = true; }  // (the C entry point asks can_record_adjoint first)
+  // the three generic moves (hmpc_results.hip calls them with the node its family table names)
+  bool has(ResultNode n) const { return (valid & result_bit(n)) != 0; }
+  void set(ResultNode n) {  // n has been enqueued anew: it stands, whatever was made from the one before is stale
+    invalidate(RESULT_BEHIND.of[(int)n]);
+    valid |= result_bit(n);
+    if (n == ResultNode::ADJOINT) adjoint_selected = -1;  // (a single launch; on_select_adjoint names its slice afterwards)
+  }
+  void retarget(ResultNode n) { invalidate(result_bit(n) | RESULT_BEHIND.of[(int)n]); }  // the caller moved n's buffers: whatever was computed went elsewhere
+
+  void on_batch() { retarget(ResultNode::SOLVE); }  // the handle holds another batch
+  void on_solve() { set(ResultNode::SOLVE); }       // every solve of a batch: its forces are newer than anything derived
+  void on_predict() { set(ResultNode::PREDICTION); }
+  void on_select(int groups) { set(ResultNode::SELECTION), select_groups = groups; }
+  void on_margins() { set(ResultNode::MARGINS); }
+  void on_certificate() { set(ResultNode::CERTIFICATE); }
+  void on_gains() { set(ResultNode::GAINS); }
+  void on_first_order() { set(ResultNode::FIRST_ORDER); }
+  void on_adjoint() { set(ResultNode::ADJOINT); }  // (independent of the gains and the wrench)
+  void on_model_adjoint() { set(ResultNode::MODEL_ADJOINT); }
+  void on_limit_adjoint() { set(ResultNode::LIMIT_ADJOINT); }    // (independent of the model gradients)
+  void on_record_adjoint() { set(ResultNode::RECORD_ADJOINT); }  // (the C entry point asks can_record_adjoint first)
   // A multi-seed adjoint is a node of its own behind the solve, in buffers of its own.  The CURRENT adjoint -- the parent of the model, limit
   // and record gradients -- is whichever came last of a single launch (on_adjoint) and a selected slice of the multi-seed one
   // (on_select_adjoint; the C entry point asks has_adjoint_multi and the range of s first).  A new multi-seed launch or new buffers for it
   // overwrite or move a selected slice, so a current adjoint that is a selection falls with them; one from a single launch does not.
-  void on_adjoint_multi(int seeds) { adjoint_multi_enqueued = true, adjoint_multi_seeds = seeds, adjoint_chain_enqueued = false, drop_selection(); }
-  void on_select_adjoint(int s) { adjoint_enqueued = true, adjoint_selected = s, model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false; }
+  void on_adjoint_multi(int seeds) { set(ResultNode::ADJOINT_MULTI), adjoint_multi_seeds = seeds, drop_selection(); }
+  void on_select_adjoint(int s) { set(ResultNode::ADJOINT), adjoint_selected = s; }
   // The chain of the multi-seed adjoint (hmpc_adjoint_chain_multi) is a node behind it alone, in buffers of its own: it reads the multi-seed
   // adjoint's slices where they stand and touches neither the current adjoint, a selection, nor the single-seed model, limit and record
   // nodes; none of those touches it.  (The C entry point asks has_adjoint_multi first.)
-  void on_adjoint_chain() { adjoint_chain_enqueued = true; }
-  // the caller moved a result's buffers: whatever was computed went elsewhere
-  void retarget_prediction() { predict_enqueued = select_enqueued = false; }
-  void retarget_selection() { select_enqueued = false; }
-  void retarget_margins() { margins_enqueued = false; }
-  void retarget_certificate() { certificate_enqueued = false; }
-  void retarget_gains() { gains_enqueued = first_order_enqueued = false; }
-  void retarget_first_order() { first_order_enqueued = false; }
-  void retarget_adjoint() { adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false, adjoint_selected = -1; }  // (a selection goes too: the current adjoint is gone either way)
-  void retarget_adjoint_multi() { adjoint_multi_enqueued = adjoint_chain_enqueued = false, drop_selection(); }
-  void retarget_adjoint_chain() { adjoint_chain_enqueued = false; }
-  void retarget_model_adjoint() { model_adjoint_enqueued = record_adjoint_enqueued = false; }
-  void retarget_limit_adjoint() { limit_adjoint_enqueued = record_adjoint_enqueued = false; }
-  void retarget_record_adjoint() { record_adjoint_enqueued = false; }
+  void on_adjoint_chain() { set(ResultNode::ADJOINT_CHAIN); }
+  void retarget_prediction() { retarget(ResultNode::PREDICTION); }
+  void retarget_selection() { retarget(ResultNode::SELECTION); }
+  void retarget_margins() { retarget(ResultNode::MARGINS); }
+  void retarget_certificate() { retarget(ResultNode::CERTIFICATE); }
+  void retarget_gains() { retarget(ResultNode::GAINS); }
+  void retarget_first_order() { retarget(ResultNode::FIRST_ORDER); }
+  void retarget_adjoint() { retarget(ResultNode::ADJOINT); }  // (a selection goes too: the current adjoint is gone either way)
+  void retarget_adjoint_multi() { retarget(ResultNode::ADJOINT_MULTI), drop_selection(); }
+  void retarget_adjoint_chain() { retarget(ResultNode::ADJOINT_CHAIN); }
+  void retarget_model_adjoint() { retarget(ResultNode::MODEL_ADJOINT); }
+  void retarget_limit_adjoint() { retarget(ResultNode::LIMIT_ADJOINT); }
+  void retarget_record_adjoint() { retarget(ResultNode::RECORD_ADJOINT); }
 
-  bool has_solve() const { return solve_enqueued; }            // a solve of the current batch has been enqueued
-  bool has_prediction() const { return predict_enqueued; }     // ... and a prediction behind it
-  bool has_selection() const { return select_enqueued; }       // ... and a selection behind that prediction
-  bool has_margins() const { return margins_enqueued; }        // margins of the last solve of the current batch have been enqueued
-  bool has_certificate() const { return certificate_enqueued; }  // a certificate of the last solve of the current batch has been enqueued
-  bool has_gains() const { return gains_enqueued; }              // feedback gains of the last solve of the current batch have been enqueued
-  bool has_first_order() const { return first_order_enqueued; }  // ... and a first-order wrench behind those gains
-  bool has_adjoint() const { return adjoint_enqueued; }          // an adjoint of the last solve of the current batch has been enqueued
-  bool has_model_adjoint() const { return model_adjoint_enqueued; }  // ... and model gradients behind that adjoint
-  bool has_limit_adjoint() const { return limit_adjoint_enqueued; }  // ... and limit gradients behind that adjoint
-  bool can_record_adjoint() const { return adjoint_enqueued && model_adjoint_enqueued && limit_adjoint_enqueued; }  // all three inputs of the record gradients stand
-  bool has_record_adjoint() const { return record_adjoint_enqueued; }  // ... and record gradients behind all three
-  bool has_adjoint_multi() const { return adjoint_multi_enqueued; }  // a multi-seed adjoint of the last solve of the current batch has been enqueued
-  int adjoint_multi_seeds_enqueued() const { return adjoint_multi_enqueued ? adjoint_multi_seeds : 0; }  // ... and its seeds
-  bool has_adjoint_chain() const { return adjoint_multi_enqueued && adjoint_chain_enqueued; }  // ... and the chain of every seed behind it
-  int selected_adjoint_seed() const { return adjoint_enqueued ? adjoint_selected : -1; }  // the slice the current adjoint is (-1: a single launch's, or none)
-  int selected_groups() const { return select_enqueued ? select_groups : 0; }  // groups of that selection
+  bool has_solve() const { return has(ResultNode::SOLVE); }              // a solve of the current batch has been enqueued
+  bool has_prediction() const { return has(ResultNode::PREDICTION); }    // ... and a prediction behind it
+  bool has_selection() const { return has(ResultNode::SELECTION); }      // ... and a selection behind that prediction
+  bool has_margins() const { return has(ResultNode::MARGINS); }
+  bool has_certificate() const { return has(ResultNode::CERTIFICATE); }
+  bool has_gains() const { return has(ResultNode::GAINS); }
+  bool has_first_order() const { return has(ResultNode::FIRST_ORDER); }  // ... a first-order wrench behind those gains
+  bool has_adjoint() const { return has(ResultNode::ADJOINT); }          // the current adjoint: a single launch's or a selected slice
+  bool has_model_adjoint() const { return has(ResultNode::MODEL_ADJOINT); }
+  bool has_limit_adjoint() const { return has(ResultNode::LIMIT_ADJOINT); }
+  // the record gradients are the one node with three parents: all three inputs must stand
+  bool can_record_adjoint() const { return has(ResultNode::ADJOINT) && has(ResultNode::MODEL_ADJOINT) && has(ResultNode::LIMIT_ADJOINT); }
+  bool has_record_adjoint() const { return has(ResultNode::RECORD_ADJOINT); }
+  bool has_adjoint_multi() const { return has(ResultNode::ADJOINT_MULTI); }
+  int adjoint_multi_seeds_enqueued() const { return has_adjoint_multi() ? adjoint_multi_seeds : 0; }  // ... and its seeds
+  // a chain stands only as long as the multi-seed adjoint it was made from does (on_adjoint_chain does not ask)
+  bool has_adjoint_chain() const { return has(ResultNode::ADJOINT_MULTI) && has(ResultNode::ADJOINT_CHAIN); }
+  int selected_adjoint_seed() const { return has_adjoint() ? adjoint_selected : -1; }  // the slice the current adjoint is (-1: a single launch's, or none)
+  int selected_groups() const { return has_selection() ? select_groups : 0; }  // groups of that selection
 
  private:
-  bool solve_enqueued = false, predict_enqueued = false, select_enqueued = false, margins_enqueued = false, certificate_enqueued = false,
-       gains_enqueued = false, first_order_enqueued = false, adjoint_enqueued = false, model_adjoint_enqueued = false, limit_adjoint_enqueued = false,
-       record_adjoint_enqueued = false, adjoint_multi_enqueued = false, adjoint_chain_enqueued = false;
+  uint32_t valid = 0;  // result_bit(n) of every node that stands
   int select_groups = 0, adjoint_multi_seeds = 0, adjoint_selected = -1;
+  void invalidate(uint32_t nodes) {
+    valid &= ~nodes;
+    if (nodes & result_bit(ResultNode::ADJOINT)) adjoint_selected = -1;
+  }
+  // the selection rule: a current adjoint that is a slice of the multi-seed one goes when that slice is overwritten or moved
   void drop_selection() {
-    if (adjoint_selected >= 0) adjoint_enqueued = model_adjoint_enqueued = limit_adjoint_enqueued = record_adjoint_enqueued = false, adjoint_selected = -1;
+    if (adjoint_selected >= 0) retarget(ResultNode::ADJOINT);
   }
 };
 

@@ -128,6 +128,56 @@ def last_status() -> int:
     return int(_lib.load().hmpc_last_status())
 
 
+# ---------------------------------------------------------------- the results derived from a solve
+# THE shape table of the host side: per family -- named by the suffix of its hmpc_set_device_* / hmpc_get_device_* / hmpc_download_*
+# entries -- its arrays in the argument order of those entries, each with its dtype and the shape of one row (one instance's; one sweep
+# group's for the selection) as a function of (horizon, contacts).  Every host array of a download is allocated from here, and _lib.py
+# counts the entries' arguments here.  The library keeps its own copy (csrc/hmpc_results.h); tests/test_result_layout_on_host.py
+# compares the two line by line.
+def _record_floats(h, c):
+    return ((records.N_FIXED3 if c == 3 else records.N_FIXED) + 12 * h,)
+
+
+_f4, _f8, _i4, _u4 = np.float32, np.float64, np.int32, np.uint32
+RESULTS = {
+    "prediction": (("states", _f4, lambda h, c: (h, 13)), ("cost", _f8, lambda h, c: (2,))),
+    "selection": (("index", _i4, lambda h, c: ()), ("score", _f8, lambda h, c: ()), ("forces", _f4, lambda h, c: (6 * c * h,)),
+                  ("status", _u4, lambda h, c: ()), ("states", _f4, lambda h, c: (h, 13))),
+    "margins": (("slack", _f8, lambda h, c: (h, c, 10)), ("summary", _f8, lambda h, c: (6,)), ("where", _i4, lambda h, c: (6,))),
+    "certificate": (("grad", _f8, lambda h, c: (h, 6 * c)), ("lambda", _f8, lambda h, c: (h, c, 10)), ("resid", _f8, lambda h, c: (h, c, 6)),
+                    ("summary", _f8, lambda h, c: (4,)), ("where", _i4, lambda h, c: (2,))),
+    "gains": (("gain", _f8, lambda h, c: (6 * c, 13)), ("ref_gain", _f8, lambda h, c: (h, 6 * c, 12)), ("summary", _f8, lambda h, c: (2,)),
+              ("free_dims", _i4, lambda h, c: (h,))),
+    "first_order": (("wrench", _f4, lambda h, c: (6 * c,)), ("worst_slack", _f8, lambda h, c: ())),
+    "adjoint": (("grad_x0", _f8, lambda h, c: (13,)), ("grad_traj", _f8, lambda h, c: (h, 12)), ("grad_weights", _f8, lambda h, c: (12,)),
+                ("grad_alpha", _f8, lambda h, c: (6 * c,)), ("dir", _f8, lambda h, c: (h, 6 * c)), ("summary", _f8, lambda h, c: (2,))),
+    "adjoint_model": (("grad_A", _f8, lambda h, c: (13, 13)), ("grad_B", _f8, lambda h, c: (13, 6 * c)), ("grad_r", _f8, lambda h, c: (3, c)),
+                      ("grad_params", _f8, lambda h, c: (4,)), ("costate", _f8, lambda h, c: (2, 13))),
+    "adjoint_limits": (("grad_limits", _f8, lambda h, c: (3 + c,)), ("grad_Fc", _f8, lambda h, c: (8 * c, 6 * c)),
+                       ("grad_bound", _f8, lambda h, c: (h, c, 10)), ("lambda", _f8, lambda h, c: (h, c, 10)), ("nu", _f8, lambda h, c: (h, c, 10)),
+                       ("summary", _f8, lambda h, c: (3,))),
+    "adjoint_record": (("grad_record", _f8, _record_floats), ("grad_frames", _f8, lambda h, c: (1 + c, 3, 3)), ("grad_rpy", _f8, lambda h, c: (3,))),
+}
+RESULTS["adjoint_multi"] = RESULTS["adjoint"]  # (one row per (seed, instance))
+
+
+def _row_of(family, name, as_name=None):
+    return next((as_name or k, dt, shape) for k, dt, shape in RESULTS[family] if k == name)
+
+
+# the chain: struct hmpc_adjoint_chain's members, each the record, model or limit row it is (six compact, eight detail)
+RESULTS["adjoint_chain_multi"] = (
+    tuple(_row_of("adjoint_record", k) for k in ("grad_record", "grad_frames", "grad_rpy")) + (_row_of("adjoint_model", "grad_params"),
+    _row_of("adjoint_limits", "grad_limits"), _row_of("adjoint_limits", "summary", "limit_summary"))
+    + tuple(_row_of("adjoint_model", k) for k in ("grad_A", "grad_B", "grad_r", "costate"))
+    + tuple(_row_of("adjoint_limits", k) for k in ("grad_Fc", "grad_bound", "lambda", "nu")))
+assert tuple(k for k, _, _ in RESULTS["adjoint_chain_multi"]) == _lib.CHAIN_COMPACT + _lib.CHAIN_DETAIL
+
+
+def _result_keys(family):
+    return tuple(k for k, _, _ in RESULTS[family])
+
+
 # ---------------------------------------------------------------- batched handle API
 class BatchedMPC:
     """One handle = one GPU, one (dt, f_max, horizon) problem shape, up to ``max_batch`` independent MPC instances.
@@ -147,6 +197,7 @@ class BatchedMPC:
         self.stride = int(self.L.hmpc_record_stride_ex(self.horizon, self.contacts))
         self._keep = None
         self._keep_out = None
+        self._keepalive = {}  # what the caller's buffers of every derived result keep alive, by family
         self.dt_mpc = float(dt)  # (binary64, as given: what rollout() passes as dtMPC by default)
         self.generation = 0  # counts the calls of this object that replace the batch or its forces (autograd.py compares it)
 
@@ -298,6 +349,40 @@ class BatchedMPC:
         _check(self.L.hmpc_download_f64(self.h, x.ctypes.data, obj.ctypes.data), "hmpc_download_f64")
         return x, obj
 
+    # ---- the results derived from a solve: every public method below is one call of these three helpers over RESULTS
+    def result_shapes(self, family: str, lead) -> dict:
+        """name -> shape of every array of ``family`` (a key of RESULTS) with the leading axes ``lead`` before one row's."""
+        return {k: tuple(lead) + shape(self.horizon, self.contacts) for k, _, shape in RESULTS[family]}
+
+    def _download(self, family: str, lead=None, only=None) -> dict:
+        """Host arrays of ``family`` by RESULTS -- ``lead`` rows each (default: one per instance of the batch), ``only`` = the arrays
+        wanted (default: all) -- filled by its ``hmpc_download_*`` entry."""
+        shapes = self.result_shapes(family, (self.batch,) if lead is None else lead)
+        out = {k: np.zeros(shapes[k], dtype=dt) for k, dt, _ in RESULTS[family] if only is None or k in only}
+        if family == "adjoint_chain_multi":
+            args = [C.byref(_lib.AdjointChain(**{k: v.ctypes.data for k, v in out.items()}))]
+        else:
+            args = [out[k].ctypes.data for k, _, _ in RESULTS[family]]
+        _check(getattr(self.L, "hmpc_download_" + family)(self.h, *args), "hmpc_download_" + family)
+        return out
+
+    def _get_device(self, family: str, count: bool = False) -> dict:
+        """Device pointers of ``family``'s arrays by name, from its ``hmpc_get_device_*`` entry; ``count``: the entry reports a count first
+        (``n_seeds``)."""
+        n, ptrs = C.c_int(0), [C.c_void_p() for _ in RESULTS[family]]
+        _check(getattr(self.L, "hmpc_get_device_" + family)(self.h, *([C.byref(n)] if count else []), *[C.byref(p) for p in ptrs]),
+               "hmpc_get_device_" + family)
+        out = {k: int(p.value or 0) for (k, _, _), p in zip(RESULTS[family], ptrs)}
+        return dict(out, n_seeds=n.value) if count else out
+
+    def _set_device(self, family: str, ptrs, keepalive, *count) -> None:
+        """``family``'s ``hmpc_set_device_*`` entry with the caller's pointers in the order of RESULTS (0 / None = the handle's own), behind
+        ``count`` where the entry takes one (``n_seeds``); ``keepalive`` lives as long as the buffers are set."""
+        self._keepalive[family] = keepalive
+        assert len(ptrs) == len(RESULTS[family])
+        _check(getattr(self.L, "hmpc_set_device_" + family)(self.h, *[int(c) for c in count], *[C.c_void_p(int(p or 0)) for p in ptrs]),
+               "hmpc_set_device_" + family)
+
     def predict_states(self, stream: int = 0) -> None:
         """One launch behind the solve on ``stream``: the model's predicted states and tracking cost under the forces in the force buffer
         (include/hector_mpc.h hmpc_predict_states).  Raises when no solve of the current batch has been enqueued."""
@@ -306,18 +391,13 @@ class BatchedMPC:
     def download_prediction(self):
         """(states[batch, horizon, 13] float32: row i = the state after step i; cost[batch, 2] float64: tracking, force).  Waits; runs no
         safe pass (``download()`` first, then ``predict_states()`` again, for repaired forces)."""
-        b = self.batch
-        states = np.zeros((b, self.horizon, 13), dtype=np.float32)
-        cost = np.zeros((b, 2), dtype=np.float64)
-        _check(self.L.hmpc_download_prediction(self.h, states.ctypes.data, cost.ctypes.data), "hmpc_download_prediction")
-        return states, cost
+        out = self._download("prediction")
+        return out["states"], out["cost"]
 
     def set_device_prediction(self, states_ptr: int, cost_ptr: int, keepalive=None) -> None:
         """Caller-owned device buffers for later predictions (float32[max_batch, horizon, 13], float64[max_batch, 2]; 0 / None = the
         handle's own)."""
-        self._keep_pred = keepalive
-        _check(self.L.hmpc_set_device_prediction(self.h, C.c_void_p(int(states_ptr or 0)), C.c_void_p(int(cost_ptr or 0))),
-               "hmpc_set_device_prediction")
+        self._set_device("prediction", (states_ptr, cost_ptr), keepalive)
 
     def sweep_select(self, group_size: int, penalty_ptr: int = 0, stream: int = 0) -> None:
         """One launch behind the prediction on ``stream``: the eligible instance of smallest (cost[0] + cost[1]) + penalty in every group of
@@ -331,20 +411,13 @@ class BatchedMPC:
         safe pass."""
         g = C.c_int(0)
         _check(self.L.hmpc_get_device_selection(self.h, None, None, None, None, None, C.byref(g)), "hmpc_get_device_selection")
-        n = int(g.value)
-        out = dict(index=np.zeros(n, dtype=np.int32), score=np.zeros(n, dtype=np.float64), forces=np.zeros((n, self.nvar), dtype=np.float32),
-                   status=np.zeros(n, dtype=np.uint32), states=np.zeros((n, self.horizon, 13), dtype=np.float32))
-        _check(self.L.hmpc_download_selection(self.h, *[out[k].ctypes.data for k in ("index", "score", "forces", "status", "states")]),
-               "hmpc_download_selection")
-        return out
+        return self._download("selection", lead=(int(g.value),))
 
     def set_device_selection(self, index_ptr: int = 0, score_ptr: int = 0, forces_ptr: int = 0, status_ptr: int = 0, states_ptr: int = 0,
                              keepalive=None) -> None:
         """Caller-owned device buffers for later selections, one row per group (int32[G], float64[G], float32[G, nvar], uint32[G],
         float32[G, horizon, 13]; 0 / None = the handle's own)."""
-        self._keep_sel = keepalive
-        _check(self.L.hmpc_set_device_selection(self.h, *[C.c_void_p(int(p or 0)) for p in (index_ptr, score_ptr, forces_ptr, status_ptr,
-                                                                                             states_ptr)]), "hmpc_set_device_selection")
+        self._set_device("selection", (index_ptr, score_ptr, forces_ptr, status_ptr, states_ptr), keepalive)
 
     def tick_sweep_device(self, ticks_ptr: int, n_ticks: int, commands_ptr: int, group_size: int, dt_mpc: float, tau_ptr: int,
                           f_ff_ptr: int = 0, wpd_ptr: int = 0, penalty_ptr: int = 0, stream: int = 0) -> None:
@@ -365,18 +438,12 @@ class BatchedMPC:
     def download_margins(self) -> dict:
         """slack float64[batch, horizon, contacts, 10] (+inf for swing leg-steps), summary float64[batch, 6] and where int32[batch, 6]
         (-1 = no candidate).  Waits; runs no safe pass."""
-        b = self.batch
-        out = dict(slack=np.zeros((b, self.horizon, self.contacts, 10), dtype=np.float64), summary=np.zeros((b, 6), dtype=np.float64),
-                   where=np.zeros((b, 6), dtype=np.int32))
-        _check(self.L.hmpc_download_margins(self.h, *[out[k].ctypes.data for k in ("slack", "summary", "where")]), "hmpc_download_margins")
-        return out
+        return self._download("margins")
 
     def set_device_margins(self, slack_ptr: int = 0, summary_ptr: int = 0, where_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later margins (float64[max_batch, horizon, contacts, 10], float64[max_batch, 6],
         int32[max_batch, 6]; 0 / None = the handle's own)."""
-        self._keep_mar = keepalive
-        _check(self.L.hmpc_set_device_margins(self.h, *[C.c_void_p(int(p or 0)) for p in (slack_ptr, summary_ptr, where_ptr)]),
-               "hmpc_set_device_margins")
+        self._set_device("margins", (slack_ptr, summary_ptr, where_ptr), keepalive)
 
     def margin_penalty(self, floor, out_ptr: int, penalty_in_ptr: int = 0, stream: int = 0) -> None:
         """out[i] = +inf where some summary[i, k] >= floor[k] is false (NaN floor entries are not tested), else penalty_in[i] or 0: a
@@ -401,21 +468,13 @@ class BatchedMPC:
     def download_certificate(self) -> dict:
         """grad float64[batch, horizon, 6 contacts], lambda float64[batch, horizon, contacts, 10], resid float64[batch, horizon, contacts, 6],
         summary float64[batch, 4] and where int32[batch, 2] (-1 = no candidate).  Waits; runs no safe pass."""
-        b, hz, nc = self.batch, self.horizon, self.contacts
-        out = {"grad": np.zeros((b, hz, 6 * nc), dtype=np.float64), "lambda": np.zeros((b, hz, nc, 10), dtype=np.float64),
-               "resid": np.zeros((b, hz, nc, 6), dtype=np.float64), "summary": np.zeros((b, 4), dtype=np.float64),
-               "where": np.zeros((b, 2), dtype=np.int32)}
-        _check(self.L.hmpc_download_certificate(self.h, *[out[k].ctypes.data for k in ("grad", "lambda", "resid", "summary", "where")]),
-               "hmpc_download_certificate")
-        return out
+        return self._download("certificate")
 
     def set_device_certificate(self, grad_ptr: int = 0, lambda_ptr: int = 0, resid_ptr: int = 0, summary_ptr: int = 0, where_ptr: int = 0,
                                keepalive=None) -> None:
         """Caller-owned device buffers for later certificates (shapes of ``download_certificate`` with max_batch rows; 0 / None = the
         handle's own)."""
-        self._keep_cert = keepalive
-        _check(self.L.hmpc_set_device_certificate(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_ptr, lambda_ptr, resid_ptr, summary_ptr,
-                                                                                               where_ptr)]), "hmpc_set_device_certificate")
+        self._set_device("certificate", (grad_ptr, lambda_ptr, resid_ptr, summary_ptr, where_ptr), keepalive)
 
     def set_certificate_tolerance(self, act_tol: float) -> None:
         """A slack <= ``act_tol`` makes its limit active for the multipliers (default 1e-3; 0 < act_tol < 0.005)."""
@@ -444,18 +503,11 @@ class BatchedMPC:
     def download_gains(self) -> dict:
         """gain float64[batch, 6 contacts, 13], ref_gain float64[batch, horizon, 6 contacts, 12], summary float64[batch, 2] (smallest
         Cholesky pivot ratio, max |gain|) and free_dims int32[batch, horizon].  Waits; runs no safe pass."""
-        b, hz, u = self.batch, self.horizon, 6 * self.contacts
-        out = dict(gain=np.zeros((b, u, 13), dtype=np.float64), ref_gain=np.zeros((b, hz, u, 12), dtype=np.float64),
-                   summary=np.zeros((b, 2), dtype=np.float64), free_dims=np.zeros((b, hz), dtype=np.int32))
-        _check(self.L.hmpc_download_gains(self.h, *[out[k].ctypes.data for k in ("gain", "ref_gain", "summary", "free_dims")]),
-               "hmpc_download_gains")
-        return out
+        return self._download("gains")
 
     def set_device_gains(self, gain_ptr: int = 0, ref_gain_ptr: int = 0, summary_ptr: int = 0, free_dims_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later gains (shapes of ``download_gains`` with max_batch rows; 0 / None = the handle's own)."""
-        self._keep_gains = keepalive
-        _check(self.L.hmpc_set_device_gains(self.h, *[C.c_void_p(int(p or 0)) for p in (gain_ptr, ref_gain_ptr, summary_ptr, free_dims_ptr)]),
-               "hmpc_set_device_gains")
+        self._set_device("gains", (gain_ptr, ref_gain_ptr, summary_ptr, free_dims_ptr), keepalive)
 
     def first_order_wrench(self, records_ptr: int, stream: int = 0) -> None:
         """One launch: the step-0 wrench of every instance moved to first order to the records at ``records_ptr`` (``batch`` records of
@@ -466,18 +518,14 @@ class BatchedMPC:
     def download_first_order(self) -> dict:
         """wrench float32[batch, 6 contacts] and worst_slack float64[batch] (the least step-0 slack at that wrench; +inf with no stance
         contact).  Waits."""
-        out = dict(wrench=np.zeros((self.batch, 6 * self.contacts), dtype=np.float32), worst_slack=np.zeros(self.batch, dtype=np.float64))
-        _check(self.L.hmpc_download_first_order(self.h, out["wrench"].ctypes.data, out["worst_slack"].ctypes.data), "hmpc_download_first_order")
-        return out
+        return self._download("first_order")
 
     def set_device_first_order(self, wrench_ptr: int = 0, worst_slack_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later first-order wrenches (float32[max_batch, 6 contacts], float64[max_batch]; 0 / None = the
         handle's own)."""
-        self._keep_fo = keepalive
-        _check(self.L.hmpc_set_device_first_order(self.h, C.c_void_p(int(wrench_ptr or 0)), C.c_void_p(int(worst_slack_ptr or 0))),
-               "hmpc_set_device_first_order")
+        self._set_device("first_order", (wrench_ptr, worst_slack_ptr), keepalive)
 
-    ADJOINT_KEYS = ("grad_x0", "grad_traj", "grad_weights", "grad_alpha", "dir", "summary")
+    ADJOINT_KEYS = _result_keys("adjoint")
 
     def solve_adjoint(self, seed_ptr: int, stream: int = 0) -> None:
         """One launch behind the solve on ``stream``: from the seed dL/du (float64[batch, horizon, 6 contacts] in HBM) the gradients of L
@@ -489,26 +537,17 @@ class BatchedMPC:
         """grad_x0 float64[batch, 13], grad_traj float64[batch, horizon, 12], grad_weights float64[batch, 12], grad_alpha
         float64[batch, 6 contacts], dir float64[batch, horizon, 6 contacts] and summary float64[batch, 2] (smallest Cholesky pivot ratio,
         max |dir|).  Waits; runs no safe pass."""
-        b, hz, u = self.batch, self.horizon, 6 * self.contacts
-        out = dict(grad_x0=np.zeros((b, 13)), grad_traj=np.zeros((b, hz, 12)), grad_weights=np.zeros((b, 12)), grad_alpha=np.zeros((b, u)),
-                   dir=np.zeros((b, hz, u)), summary=np.zeros((b, 2)))
-        _check(self.L.hmpc_download_adjoint(self.h, *[out[k].ctypes.data for k in self.ADJOINT_KEYS]), "hmpc_download_adjoint")
-        return out
+        return self._download("adjoint")
 
     def get_device_adjoint(self) -> dict:
         """Device pointers of where the next adjoint goes, by the names of ``download_adjoint`` (the handle's own buffers are allocated
         here if they were not yet)."""
-        ptrs = [C.c_void_p() for _ in self.ADJOINT_KEYS]
-        _check(self.L.hmpc_get_device_adjoint(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint")
-        return {k: int(p.value or 0) for k, p in zip(self.ADJOINT_KEYS, ptrs)}
+        return self._get_device("adjoint")
 
     def set_device_adjoint(self, grad_x0_ptr: int = 0, grad_traj_ptr: int = 0, grad_weights_ptr: int = 0, grad_alpha_ptr: int = 0,
                            dir_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later adjoints (shapes of ``download_adjoint`` with max_batch rows; 0 / None = the handle's own)."""
-        self._keep_adj = keepalive
-        _check(self.L.hmpc_set_device_adjoint(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_x0_ptr, grad_traj_ptr, grad_weights_ptr,
-                                                                                           grad_alpha_ptr, dir_ptr, summary_ptr)]),
-               "hmpc_set_device_adjoint")
+        self._set_device("adjoint", (grad_x0_ptr, grad_traj_ptr, grad_weights_ptr, grad_alpha_ptr, dir_ptr, summary_ptr), keepalive)
 
     def solve_adjoint_multi(self, seeds_ptr: int, n_seeds: int, stream: int = 0) -> None:
         """``solve_adjoint`` under ``n_seeds`` seeds (float64[n_seeds, batch, horizon, 6 contacts] in HBM) behind ONE matrix backward pass:
@@ -521,28 +560,18 @@ class BatchedMPC:
     def download_adjoint_multi(self) -> dict:
         """The arrays of ``download_adjoint`` with a leading axis over the seeds of the last ``solve_adjoint_multi``.  Waits; runs no safe
         pass."""
-        n = C.c_int(0)
-        _check(self.L.hmpc_get_device_adjoint_multi(self.h, C.byref(n), *[None] * 6), "hmpc_get_device_adjoint_multi")
-        s, b, hz, u = n.value, self.batch, self.horizon, 6 * self.contacts
-        out = dict(grad_x0=np.zeros((s, b, 13)), grad_traj=np.zeros((s, b, hz, 12)), grad_weights=np.zeros((s, b, 12)),
-                   grad_alpha=np.zeros((s, b, u)), dir=np.zeros((s, b, hz, u)), summary=np.zeros((s, b, 2)))
-        _check(self.L.hmpc_download_adjoint_multi(self.h, *[out[k].ctypes.data for k in self.ADJOINT_KEYS]), "hmpc_download_adjoint_multi")
-        return out
+        return self._download("adjoint_multi", lead=(self._get_device("adjoint_multi", count=True)["n_seeds"], self.batch))
 
     def get_device_adjoint_multi(self) -> dict:
         """Device pointers of slice 0 of where the multi-seed adjoint is or goes next, by the names of ``download_adjoint`` (0: one of the
         handle's own that no launch has reserved yet), and ``n_seeds``: the seeds of the one that stands (0: none)."""
-        n, ptrs = C.c_int(0), [C.c_void_p() for _ in self.ADJOINT_KEYS]
-        _check(self.L.hmpc_get_device_adjoint_multi(self.h, C.byref(n), *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_multi")
-        return dict({k: int(p.value or 0) for k, p in zip(self.ADJOINT_KEYS, ptrs)}, n_seeds=n.value)
+        return self._get_device("adjoint_multi", count=True)
 
     def set_device_adjoint_multi(self, n_seeds: int = 0, grad_x0_ptr: int = 0, grad_traj_ptr: int = 0, grad_weights_ptr: int = 0,
                                  grad_alpha_ptr: int = 0, dir_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later multi-seed adjoints, with room for ``n_seeds`` slices of the current batch (0 / None = the
         handle's own)."""
-        self._keep_adj_multi = keepalive
-        _check(self.L.hmpc_set_device_adjoint_multi(self.h, int(n_seeds), *[C.c_void_p(int(p or 0)) for p in (
-            grad_x0_ptr, grad_traj_ptr, grad_weights_ptr, grad_alpha_ptr, dir_ptr, summary_ptr)]), "hmpc_set_device_adjoint_multi")
+        self._set_device("adjoint_multi", (grad_x0_ptr, grad_traj_ptr, grad_weights_ptr, grad_alpha_ptr, dir_ptr, summary_ptr), keepalive, n_seeds)
 
     def select_adjoint_seed(self, s: int) -> None:
         """Makes slice ``s`` of the last ``solve_adjoint_multi`` the current adjoint: ``adjoint_model``, ``adjoint_limits`` (hand it the
@@ -550,7 +579,7 @@ class BatchedMPC:
         copy.  Raises when ``s`` is out of range or no multi-seed adjoint of the last solve of the current batch stands."""
         _check(self.L.hmpc_select_adjoint_seed(self.h, int(s)), "hmpc_select_adjoint_seed")
 
-    MODEL_ADJOINT_KEYS = ("grad_A", "grad_B", "grad_r", "grad_params", "costate")
+    MODEL_ADJOINT_KEYS = _result_keys("adjoint_model")
 
     def adjoint_model(self, stream: int = 0) -> None:
         """One launch behind ``solve_adjoint`` on ``stream``: from the ``dir`` that adjoint left, the gradients of the same loss in Acd,
@@ -562,30 +591,20 @@ class BatchedMPC:
         """grad_A float64[batch, 13, 13], grad_B float64[batch, 13, 6 contacts], grad_r float64[batch, 3, contacts] (the record's order:
         axis, then contact), grad_params float64[batch, 4] (mass, inertia 0 .. 2) and costate float64[batch, 2, 13].  Waits; runs no safe
         pass."""
-        b, nc = self.batch, self.contacts
-        out = dict(grad_A=np.zeros((b, 13, 13)), grad_B=np.zeros((b, 13, 6 * nc)), grad_r=np.zeros((b, 3, nc)), grad_params=np.zeros((b, 4)),
-                   costate=np.zeros((b, 2, 13)))
-        _check(self.L.hmpc_download_adjoint_model(self.h, *[out[k].ctypes.data for k in self.MODEL_ADJOINT_KEYS]),
-               "hmpc_download_adjoint_model")
-        return out
+        return self._download("adjoint_model")
 
     def get_device_adjoint_model(self) -> dict:
         """Device pointers of where the next model gradients go, by the names of ``download_adjoint_model`` (the handle's own buffers are
         allocated here if they were not yet)."""
-        ptrs = [C.c_void_p() for _ in self.MODEL_ADJOINT_KEYS]
-        _check(self.L.hmpc_get_device_adjoint_model(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_model")
-        return {k: int(p.value or 0) for k, p in zip(self.MODEL_ADJOINT_KEYS, ptrs)}
+        return self._get_device("adjoint_model")
 
     def set_device_adjoint_model(self, grad_A_ptr: int = 0, grad_B_ptr: int = 0, grad_r_ptr: int = 0, grad_params_ptr: int = 0,
                                  costate_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later model gradients (shapes of ``download_adjoint_model`` with max_batch rows; 0 / None = the
         handle's own)."""
-        self._keep_madj = keepalive
-        _check(self.L.hmpc_set_device_adjoint_model(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_A_ptr, grad_B_ptr, grad_r_ptr,
-                                                                                                 grad_params_ptr, costate_ptr)]),
-               "hmpc_set_device_adjoint_model")
+        self._set_device("adjoint_model", (grad_A_ptr, grad_B_ptr, grad_r_ptr, grad_params_ptr, costate_ptr), keepalive)
 
-    LIMIT_ADJOINT_KEYS = ("grad_limits", "grad_Fc", "grad_bound", "lambda", "nu", "summary")
+    LIMIT_ADJOINT_KEYS = _result_keys("adjoint_limits")
 
     def adjoint_limits(self, seed_ptr: int, stream: int = 0) -> None:
         """One launch behind ``solve_adjoint`` on ``stream``: from the ``dir`` that adjoint left and the seed it was given (``seed_ptr``
@@ -598,31 +617,20 @@ class BatchedMPC:
         """grad_limits float64[batch, 3 + contacts] (mu, lt, lh, the Fz cap of every contact), grad_Fc float64[batch, 8 contacts,
         6 contacts], grad_bound / lambda / nu float64[batch, horizon, contacts, 10] and summary float64[batch, 3].  Waits; runs no safe
         pass."""
-        b, nc, hz = self.batch, self.contacts, self.horizon
-        out = dict(grad_limits=np.zeros((b, 3 + nc)), grad_Fc=np.zeros((b, 8 * nc, 6 * nc)), grad_bound=np.zeros((b, hz, nc, 10)),
-                   nu=np.zeros((b, hz, nc, 10)), summary=np.zeros((b, 3)))
-        out["lambda"] = np.zeros((b, hz, nc, 10))
-        _check(self.L.hmpc_download_adjoint_limits(self.h, *[out[k].ctypes.data for k in self.LIMIT_ADJOINT_KEYS]),
-               "hmpc_download_adjoint_limits")
-        return out
+        return self._download("adjoint_limits")
 
     def get_device_adjoint_limits(self) -> dict:
         """Device pointers of where the next limit gradients go, by the names of ``download_adjoint_limits`` (the handle's own buffers are
         allocated here if they were not yet)."""
-        ptrs = [C.c_void_p() for _ in self.LIMIT_ADJOINT_KEYS]
-        _check(self.L.hmpc_get_device_adjoint_limits(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_limits")
-        return {k: int(p.value or 0) for k, p in zip(self.LIMIT_ADJOINT_KEYS, ptrs)}
+        return self._get_device("adjoint_limits")
 
     def set_device_adjoint_limits(self, grad_limits_ptr: int = 0, grad_Fc_ptr: int = 0, grad_bound_ptr: int = 0, lambda_ptr: int = 0,
                                   nu_ptr: int = 0, summary_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later limit gradients (shapes of ``download_adjoint_limits`` with max_batch rows; 0 / None = the
         handle's own)."""
-        self._keep_ladj = keepalive
-        _check(self.L.hmpc_set_device_adjoint_limits(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_limits_ptr, grad_Fc_ptr, grad_bound_ptr,
-                                                                                                  lambda_ptr, nu_ptr, summary_ptr)]),
-               "hmpc_set_device_adjoint_limits")
+        self._set_device("adjoint_limits", (grad_limits_ptr, grad_Fc_ptr, grad_bound_ptr, lambda_ptr, nu_ptr, summary_ptr), keepalive)
 
-    RECORD_ADJOINT_KEYS = ("grad_record", "grad_frames", "grad_rpy")
+    RECORD_ADJOINT_KEYS = _result_keys("adjoint_record")
 
     def adjoint_record(self, stream: int = 0) -> None:
         """One launch behind ``solve_adjoint``, ``adjoint_model`` and ``adjoint_limits`` on ``stream``: their outputs chained through the
@@ -634,37 +642,22 @@ class BatchedMPC:
         """grad_record float64[batch, fixed floats + 12 horizon] in the float order of the packed record (``records.OFF`` / ``OFF3``),
         grad_frames float64[batch, 1 + contacts, 3, 3] (the body rotation, then every contact frame) and grad_rpy float64[batch, 3].
         Waits; runs no safe pass."""
-        b, nc, hz = self.batch, self.contacts, self.horizon
-        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
-        out = dict(grad_record=np.zeros((b, nf + 12 * hz)), grad_frames=np.zeros((b, 1 + nc, 3, 3)), grad_rpy=np.zeros((b, 3)))
-        _check(self.L.hmpc_download_adjoint_record(self.h, *[out[k].ctypes.data for k in self.RECORD_ADJOINT_KEYS]),
-               "hmpc_download_adjoint_record")
-        return out
+        return self._download("adjoint_record")
 
     def get_device_adjoint_record(self) -> dict:
         """Device pointers of where the next record gradients go, by the names of ``download_adjoint_record`` (the handle's own buffers
         are allocated here if they were not yet)."""
-        ptrs = [C.c_void_p() for _ in self.RECORD_ADJOINT_KEYS]
-        _check(self.L.hmpc_get_device_adjoint_record(self.h, *[C.byref(p) for p in ptrs]), "hmpc_get_device_adjoint_record")
-        return {k: int(p.value or 0) for k, p in zip(self.RECORD_ADJOINT_KEYS, ptrs)}
+        return self._get_device("adjoint_record")
 
     def set_device_adjoint_record(self, grad_record_ptr: int = 0, grad_frames_ptr: int = 0, grad_rpy_ptr: int = 0, keepalive=None) -> None:
         """Caller-owned device buffers for later record gradients (shapes of ``download_adjoint_record`` with max_batch rows; 0 / None =
         the handle's own)."""
-        self._keep_padj = keepalive
-        _check(self.L.hmpc_set_device_adjoint_record(self.h, *[C.c_void_p(int(p or 0)) for p in (grad_record_ptr, grad_frames_ptr, grad_rpy_ptr)]),
-               "hmpc_set_device_adjoint_record")
+        self._set_device("adjoint_record", (grad_record_ptr, grad_frames_ptr, grad_rpy_ptr), keepalive)
 
-    CHAIN_KEYS = _lib.CHAIN_COMPACT + _lib.CHAIN_DETAIL
+    CHAIN_KEYS = _result_keys("adjoint_chain_multi")
 
     def _chain_shapes(self, n_seeds: int) -> dict:
-        s, b, nc, hz = n_seeds, self.batch, self.contacts, self.horizon
-        nf = records.N_FIXED3 if nc == 3 else records.N_FIXED
-        shapes = dict(grad_record=(s, b, nf + 12 * hz), grad_frames=(s, b, 1 + nc, 3, 3), grad_rpy=(s, b, 3), grad_params=(s, b, 4),
-                      grad_limits=(s, b, 3 + nc), limit_summary=(s, b, 3), grad_A=(s, b, 13, 13), grad_B=(s, b, 13, 6 * nc), grad_r=(s, b, 3, nc),
-                      costate=(s, b, 2, 13), grad_Fc=(s, b, 8 * nc, 6 * nc), grad_bound=(s, b, hz, nc, 10), nu=(s, b, hz, nc, 10))
-        shapes["lambda"] = (s, b, hz, nc, 10)
-        return shapes
+        return self.result_shapes("adjoint_chain_multi", (n_seeds, self.batch))
 
     def adjoint_chain_multi(self, seeds_ptr: int, stream: int = 0) -> None:
         """Behind ``solve_adjoint_multi``: for every seed of it the chain ``adjoint_model`` -> ``adjoint_limits`` -> ``adjoint_record``,
@@ -688,11 +681,7 @@ class BatchedMPC:
         no safe pass."""
         n = C.c_int(0)
         _check(self.L.hmpc_get_device_adjoint_chain_multi(self.h, C.byref(n), None), "hmpc_get_device_adjoint_chain_multi")
-        shapes = self._chain_shapes(n.value)
-        out = {k: np.zeros(shapes[k]) for k in (self.CHAIN_KEYS if detail else _lib.CHAIN_COMPACT)}
-        b = _lib.AdjointChain(**{k: v.ctypes.data for k, v in out.items()})
-        _check(self.L.hmpc_download_adjoint_chain_multi(self.h, C.byref(b)), "hmpc_download_adjoint_chain_multi")
-        return out
+        return self._download("adjoint_chain_multi", lead=(n.value, self.batch), only=self.CHAIN_KEYS if detail else _lib.CHAIN_COMPACT)
 
     def set_device_adjoint_chain_multi(self, n_seeds: int = 0, keepalive=None, **ptrs) -> None:
         """Caller-owned device buffers for later chains, with room for ``n_seeds`` slices of the current batch, by ``CHAIN_KEYS`` with
@@ -702,7 +691,7 @@ class BatchedMPC:
         unknown = [k for k in ptrs if k not in names]
         if unknown:
             raise TypeError(f"set_device_adjoint_chain_multi: unknown buffers {unknown}")
-        self._keep_chain = keepalive
+        self._keepalive["adjoint_chain_multi"] = keepalive
         b = _lib.AdjointChain(**{names[k]: int(v or 0) or None for k, v in ptrs.items()})
         _check(self.L.hmpc_set_device_adjoint_chain_multi(self.h, int(n_seeds), C.byref(b)), "hmpc_set_device_adjoint_chain_multi")
 
