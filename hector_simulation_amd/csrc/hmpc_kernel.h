@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #ifndef HMPC_REFINE
 #define HMPC_REFINE 1  // corrections u += E (b_W - N_W x(u)) applied to the multipliers of the final working set
@@ -357,6 +358,15 @@ struct VariantTraits {
   // holds the block-diagonals in two passes, so the register blocks are filled as for the scalar sweeps and turned into tiles in stage S.
   static constexpr bool MFMA_SWEEP3 = !ASM_ONLY && SM::MFS3 && ROLE == Role::FAST;
   static constexpr int MFS3_NTG = (NMAX + 15) / 16;
+  // The block-pivot steps as one unrolled pass per tile row (mfs_steps<.., ROWS = true>: tile row and the step's place in it are compile-time constants) or
+  // as the loop over the steps with both at run time.  Stage S on the 8 x 8 grid of the hand-over shape: row passes (headline kernel 1.152 / 1.155 ->
+  // 1.086 / 1.092 ms, 27 397 -> 43 943 instructions, 159 VGPRs both; profiles/r34).  MFS3_ROW_PASSES, stage S on the 12 x 12 and 15 x 15 grids (20 tiles per
+  // wave, 12 and 15 tile rows): the loop -- with row passes the three-contact variant stays at 256 VGPRs without a spill but its code grows from 64 850 to
+  // 121 677 instructions, which nobody has timed, and the wide variant sits on 256 VGPRs already (next line).  SCHUR_ROW_PASSES, the Schur inversion of the
+  // block start: every grid (3 x 3, 4 x 4, 6 x 6, and variant 7's 5 x 5: 170 -> 176 VGPRs, two waves per SIMD as before) but the wide FAST variant's 5 x 5,
+  // where row passes cost 16 spilled VGPRs and 12 B of scratch (none with the loop).
+  static constexpr bool MFS3_ROW_PASSES = false;
+  static constexpr bool SCHUR_ROW_PASSES = !WIDE_SHAPE;
 
   // ---- stage W, the block start.  Rounds at most: walking ~1.6 iterations per solve, nothing to gain: one; three contacts: three (1.13 -> 1.18 M solves/s
   // over two); everything else two (a third one is worth <1 % on 120 variables and its third copy of the phase tips the register allocation of the 168-VGPR
@@ -635,6 +645,12 @@ __device__ __forceinline__ void mfs_load_parked(MfsAcc<NTG, NWV> &acc, const int
   }
 }
 
+// row(0), row(1), ... over the K tile rows of a grid, each with its index as a compile-time constant, until one returns false
+template <class Row, int... K>
+__device__ __forceinline__ void mfs_for_tile_rows(Row row, std::integer_sequence<int, K...>) {
+  (void)(row(std::integral_constant<int, K>()) && ...);  // (stops at the first row in which the steps end)
+}
+
 // The NTG * 4 block-pivot steps on the tiles in acc (code specialised per wave).  Callers: a barrier between the last read
 // of whatever PN aliases and this call.
 // CHECK = true (the Schur matrix of the block start, n = k0 rows of a 16 NTG grid): a tile (I, J) with 16 J >= n is DEAD -- identity
@@ -645,7 +661,9 @@ __device__ __forceinline__ void mfs_load_parked(MfsAcc<NTG, NWV> &acc, const int
 // updated by anything but products with such zeros), so the update acc -= Q' 0 of a dead tile changes nothing; (c) nothing reads
 // a dead column of the panel -- the B operand of column J goes to tiles (., J) only, the A operand of row I to tiles (I, .), and
 // J live implies I live -- and schur_store never writes a column >= n.  CHECK = false (stage S): every tile is live, compile time.
-template <int NTG, int NWV, int WV, bool CHECK = false>
+// ROWS = true: one unrolled pass per tile row, the step's place in its row known at compile time; false: one loop over the steps with
+// run-time s / 4 and s % 4 (VariantTraits::MFS3_ROW_PASSES, SCHUR_ROW_PASSES say which grids keep it).  The same bits either way.
+template <int NTG, int NWV, int WV, bool CHECK = false, bool ROWS = true>
 __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &acc, const int n) {
   constexpr MfsTiles<NTG, NWV, WV> T;
   constexpr int TPW = MfsGrid<NTG, NWV>::TPW, PST = MfsPanel<NTG>::PST, CNT = mfs_count(NTG, NWV, WV);
@@ -745,15 +763,10 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
       default: publish_ik(std::integral_constant<int, 15>(), s, rr); break;
     }
   };
-  publish(0);
-  __syncthreads();
-  const int nsteps = (n + 3) >> 2;
-#pragma unroll 1
-  for (int s = 0; s < nsteps; ++s) {
-    const int rr = s & 3, Ik = s >> 2;
-    const double(*P)[PST] = PN.P[s & 1];
-    const double x0 = PN.Dinv[s & 1][g][0], x1 = PN.Dinv[s & 1][g][1], x2 = PN.Dinv[s & 1][g][2], x3 = PN.Dinv[s & 1][g][3];
-    // tile(I,J) -= Q_I' P_J, Q = D^-1 P: A operand -Q[g][16 I + c], B operand P[g][16 J + c].
+  // the update of one step from panel buffer par = s % 2: tile(I,J) -= Q_I' P_J, Q = D^-1 P: A operand -Q[g][16 I + c], B operand P[g][16 J + c].
+  auto update = [&](const int par) __attribute__((always_inline)) {
+    const double(*P)[PST] = PN.P[par];
+    const double x0 = PN.Dinv[par][g][0], x1 = PN.Dinv[par][g][1], x2 = PN.Dinv[par][g][2], x3 = PN.Dinv[par][g][3];
     if constexpr (CHECK) {
       // live tiles only, tile by tile behind one scalar branch each (the operand pipeline below, with a test per tile in it, keeps its
       // double buffers alive across the branches: +10 VGPRs on the continuation variant).  The wave's tiles are sorted by (I, J): in a tile
@@ -799,6 +812,80 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
       }
     }
     }
+  };
+  const int nsteps = (n + 3) >> 2;
+  if constexpr (ROWS) {
+    // One pass per tile row Ik, its four steps unrolled: Ik and rr = s % 4 are compile-time constants in the step and in the publish
+    // that follows it.  The pivot rows are then plain accumulator registers (no selects), the buffer parity s % 2 = rr % 2 and the
+    // column offset 4 rr are immediates of the LDS addresses, the diagonal patch is one subtraction on register rr of the pivot
+    // tile (the other three subtracted 0.0: x - 0.0 is x for every x, -0.0 included), and there is no dispatch on Ik at all.
+    // What depends on the lane is formed once per call: the quarter of the tile a lane's column lies in, and its place in it.
+    // Same operations on the same operands in the same order per tile as the loop below; the steps may end inside a tile row.
+    const int cq = c & 3;    // for the lanes with c in [4 rr, 4 rr + 4): c - 4 rr
+    const bool dq = cq == g;  // ... and c == 4 rr + g
+    const bool inq[4] = {(c >> 2) == 0, (c >> 2) == 1, (c >> 2) == 2, (c >> 2) == 3};
+    auto publish_at = [&](auto ikc, auto rrc) __attribute__((always_inline)) {  // the panel of step 4 IK + RR, as publish_ik
+      constexpr int IK = decltype(ikc)::value, RR = decltype(rrc)::value;
+      if constexpr (IK < NTG) {
+        double(*P)[PST] = PN.P[RR & 1];
+#pragma unroll
+        for (int t = 0; t < CNT; ++t) {
+          if (!live(t)) continue;
+          if (T.i[t] == IK) {  // compile time
+            double v = acc[t][RR];
+            if (T.j[t] == IK) {
+              if (inq[RR]) PN.Draw[g][cq] = v;
+              v -= (inq[RR] && dq) ? 1.0 : 0.0;
+            }
+            P[g][16 * T.j[t] + c] = v;
+          } else if (T.j[t] == IK) {
+            if (inq[RR]) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) P[cq][16 * T.i[t] + g + 4 * r] = acc[t][r];
+            }
+          }
+        }
+        {  // (the owner of the pivot block inverts it after all of its panel stores are issued, as in publish_ik)
+          bool owner = false;  // compile time
+#pragma unroll
+          for (int t = 0; t < CNT; ++t) owner = owner || (T.i[t] == IK && T.j[t] == IK);
+          if (owner) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            publish_dinv(RR & 1);
+          }
+        }
+      }
+    };
+    auto step = [&](auto ikc, auto rrc) __attribute__((always_inline)) -> bool {  // false: the steps ended before this one
+      constexpr int IK = decltype(ikc)::value, RR = decltype(rrc)::value, s = 4 * IK + RR;
+      if (s >= nsteps) return false;  // uniform
+      update(RR & 1);
+#pragma unroll
+      for (int t = 0; t < CNT; ++t)
+        if (T.i[t] == IK && T.j[t] == IK) {  // compile time: the pivot block's diagonal
+          asm volatile("");
+          acc[t][RR] -= (inq[RR] && dq) ? 2.0 : 0.0;
+        }
+      if (s + 1 < nsteps) {  // uniform
+        if constexpr (RR < 3) publish_at(ikc, std::integral_constant<int, RR + 1>());
+        else publish_at(std::integral_constant<int, IK + 1>(), std::integral_constant<int, 0>());
+      }
+      __syncthreads();
+      return true;
+    };
+    publish_at(std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+    __syncthreads();
+    mfs_for_tile_rows([&](auto ikc) __attribute__((always_inline)) -> bool {
+      return step(ikc, std::integral_constant<int, 0>()) && step(ikc, std::integral_constant<int, 1>()) && step(ikc, std::integral_constant<int, 2>()) &&
+             step(ikc, std::integral_constant<int, 3>());
+    }, std::make_integer_sequence<int, NTG>());
+  } else {
+  publish(0);
+  __syncthreads();
+#pragma unroll 1
+  for (int s = 0; s < nsteps; ++s) {
+    const int rr = s & 3, Ik = s >> 2;
+    update(s & 1);
 #pragma unroll
     for (int t = 0; t < CNT; ++t)
       if (T.i[t] == T.j[t] && T.i[t] == Ik) {  // (first test compile time, second uniform): the pivot block's diagonal
@@ -809,6 +896,7 @@ __device__ __forceinline__ void mfs_steps(MfsPanel<NTG> &PN, MfsAcc<NTG, NWV> &a
       }
     if (s + 1 < nsteps) publish(s + 1);
     __syncthreads();
+  }
   }
 }
 
@@ -1033,11 +1121,11 @@ __device__ __forceinline__ void schur_store(const MfsAcc<NTG, NWV> &acc, const i
   }
 }
 // the whole inversion, code specialised per wave; returns through SP.pn.bad whether a pivot was not positive
-template <int NTG, int NWV, int WV>
+template <int NTG, int NWV, int WV, bool ROWS>
 __device__ __forceinline__ void schur_invert(SchurPanel<NTG> &SP, const int k0, double *Ep) {
   MfsAcc<NTG, NWV> acc;
   schur_load<NTG, NWV, WV>(acc, k0, Ep, SP.kexp);
-  mfs_steps<NTG, NWV, WV, true>(SP.pn, acc, k0);
+  mfs_steps<NTG, NWV, WV, true, ROWS>(SP.pn, acc, k0);
   schur_store<NTG, NWV, WV>(acc, k0, Ep, SP.kexp);
 }
 
@@ -2098,7 +2186,7 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
   MfsAcc<VT::MFS3_NTG, NW> acc;                                                                \
   mfs_load_parked<VT::MFS3_NTG, NW, W, NMAX>(acc, n, hb, S.kexp);                              \
   __syncthreads(); /* every tile is loaded before the panel (which aliases the parked blocks) is written */ \
-  mfs_steps<VT::MFS3_NTG, NW, W>(PN, acc, n);                                                  \
+  mfs_steps<VT::MFS3_NTG, NW, W, false, VT::MFS3_ROW_PASSES>(PN, acc, n);                         \
   double aw[BPT][GS][GS];                                                                  \
   mfs_relayout<VT::MFS3_NTG, NW, W, NMAX, BPT, NT>(stage, acc, n, S.kexp, e0a, e1a, lva, aw);  \
   mfs_move_blocks<BPT>(a, aw);
@@ -2871,14 +2959,14 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
         SchurPanel<VT::NTGS> &SP = *reinterpret_cast<SchurPanel<VT::NTGS> *>(&Q.ST[0][0]);
         schur_scale_exponents<VT::NTGS>(k0, Ep, SP.kexp);  // (read again at the store, many barriers later; the tile loader takes its own from the diagonal)
         switch (wv) {  // uniform: per-wave specialised code
-          case 0: schur_invert<VT::NTGS, NW, 0>(SP, k0, Ep); break;
-          case 1: schur_invert<VT::NTGS, NW, 1>(SP, k0, Ep); break;
-          case 2: schur_invert<VT::NTGS, NW, (NW > 2 ? 2 : 0)>(SP, k0, Ep); break;  // (cases 2-3: not in the two-wave variants)
-          case 3: schur_invert<VT::NTGS, NW, (NW > 2 ? 3 : 0)>(SP, k0, Ep); break;
-          case 4: schur_invert<VT::NTGS, NW, (NW > 4 ? 4 : 0)>(SP, k0, Ep); break;  // (cases 4-7: eight-wave variants only)
-          case 5: schur_invert<VT::NTGS, NW, (NW > 4 ? 5 : 0)>(SP, k0, Ep); break;
-          case 6: schur_invert<VT::NTGS, NW, (NW > 4 ? 6 : 0)>(SP, k0, Ep); break;
-          default: schur_invert<VT::NTGS, NW, (NW > 4 ? 7 : 0)>(SP, k0, Ep); break;
+          case 0: schur_invert<VT::NTGS, NW, 0, VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
+          case 1: schur_invert<VT::NTGS, NW, 1, VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
+          case 2: schur_invert<VT::NTGS, NW, (NW > 2 ? 2 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;  // (cases 2-3: not in the two-wave variants)
+          case 3: schur_invert<VT::NTGS, NW, (NW > 2 ? 3 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
+          case 4: schur_invert<VT::NTGS, NW, (NW > 4 ? 4 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;  // (cases 4-7: eight-wave variants only)
+          case 5: schur_invert<VT::NTGS, NW, (NW > 4 ? 5 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
+          case 6: schur_invert<VT::NTGS, NW, (NW > 4 ? 6 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
+          default: schur_invert<VT::NTGS, NW, (NW > 4 ? 7 : 0), VT::SCHUR_ROW_PASSES>(SP, k0, Ep); break;
         }
         __syncthreads();
         bad_start = SP.pn.bad != 0;
