@@ -47,6 +47,7 @@ EXPORTS = [
     "hmpc_download_rollout",
     "hmpc_default_rollout_cost", "hmpc_rollout_score_device", "hmpc_rollout_select_device", "hmpc_rollout_sweep_device",
     "hmpc_get_device_rollout_sweep",
+    "hmpc_default_swing", "hmpc_swing_state_init_device", "hmpc_swing_legs_device", "hmpc_tick_command_device", "hmpc_set_rollout_swing",
 ]
 
 
@@ -106,6 +107,26 @@ ROLLOUT_CHOICE = ("index", "score", "wrench", "tau", "summary")
 class RolloutChoice(C.Structure):
     """include/hector_mpc.h struct hmpc_rollout_choice (device pointers of a rollout selection's outputs; each may be NULL)."""
     _fields_ = [(k, C.c_void_p) for k in ROLLOUT_CHOICE]
+
+
+class Swing(C.Structure):
+    """include/hector_mpc.h struct hmpc_swing (the swing update's constants; hmpc_default_swing fills the reference's values)."""
+    _fields_ = [("dt_update", C.c_double), ("dtMPC", C.c_double), ("updates", C.c_int), ("ticks_per_step", C.c_int), ("subtick", C.c_int),
+                ("reserved", C.c_int), ("height", C.c_double), ("place_gain_v", C.c_double), ("place_gain_err", C.c_double),
+                ("place_max", C.c_double), ("hip_yaw", (C.c_double * 3) * 2), ("hip_roll", C.c_double * 3),
+                ("hip_width_offset", (C.c_double * 3) * 2), ("ik_link", C.c_double), ("ik_horizontal", C.c_double), ("ik_hip_x", C.c_double),
+                ("kp", C.c_double * 5), ("kd", C.c_double * 5)]
+
+
+class SwingState(C.Structure):
+    """include/hector_mpc.h struct hmpc_swing_state (one per instance, carried from tick to tick; all zero with first_swing = {1, 1} at the start)."""
+    _fields_ = [("p0", (C.c_double * 3) * 2), ("pf", (C.c_double * 3) * 2), ("swing_time", C.c_double * 2), ("q_des", C.c_double * 10),
+                ("first_swing", C.c_int32 * 2)]
+
+
+class MotorCmd(C.Structure):
+    """include/hector_mpc.h struct hmpc_motor_cmd (the complete command of the ten joints)."""
+    _fields_ = [(k, C.c_double * 10) for k in ("q", "dq", "Kp", "Kd", "tau")]
 
 
 class Command(C.Structure):
@@ -296,6 +317,12 @@ def load():
     L.hmpc_rollout_sweep_device.argtypes = [vp, vp, ci, vp, ci, ci, cd, ci, ci, C.POINTER(Plant), C.POINTER(RolloutCost), vp,
                                             C.POINTER(RolloutChoice), vp]
     L.hmpc_get_device_rollout_sweep.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.hmpc_default_swing.argtypes = [C.POINTER(Swing)]
+    L.hmpc_default_swing.restype = None
+    L.hmpc_swing_state_init_device.argtypes = [vp, vp, ci, vp]
+    L.hmpc_swing_legs_device.argtypes = [vp, vp, ci, C.POINTER(Swing), vp, vp, vp, vp, vp]
+    L.hmpc_tick_command_device.argtypes = [vp, vp, ci, cd, C.POINTER(Swing), vp, vp, vp, vp, vp]
+    L.hmpc_set_rollout_swing.argtypes = [vp, C.POINTER(Swing), vp, vp]
     L.hmpc_last_hip_error.restype = C.c_char_p
     L.hmpc_version.restype = C.c_char_p
     _lib = L

@@ -143,6 +143,12 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   DeviceBuffer<unsigned char> d_rsw_ticks, d_rsw_ticks0;
   DeviceBuffer<double> d_rsw_cost, d_rsw_score;
   int rsw_batch = 0, rscore_batch = 0, rscore_ticks = 0;
+  // swing legs in a rollout (hmpc_set_rollout_swing, hmpc_swing.hip): the constants, copied; the caller's state [batch] and command log
+  // [batch][n_ticks] (may be nullptr).  swing_on = false: a rollout enqueues nothing for them.
+  bool swing_on = false;
+  hmpc_swing swing_cfg{};
+  hmpc_swing_state *swing_state = nullptr;
+  hmpc_motor_cmd *swing_cmd_log = nullptr;
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 
@@ -211,5 +217,8 @@ int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes, Launc
 int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset);                           // what hmpc_solve enqueues
 int enqueue_command_sweep(hmpc_handle *h, hipStream_t stream, int group_size);                    // what hmpc_solve_command_sweep enqueues (group_size > 1)
 int resolve_failed(hmpc_handle *h, int *n_resolved);                                              // the host-driven repair of hmpc_resolve_failed (device set, batch > 0)
+// ---- hmpc_swing.hip
+// tick k of a rollout: the swing launch of hmpc_set_rollout_swing behind the tick's torque launch (nothing when the setting is off)
+int rollout_swing_tick(hmpc_handle *h, const void *device_ticks, int batch, int k, int n_ticks, int ticks_per_step, int subtick0, hipStream_t stream);
 
 #pragma GCC visibility pop

@@ -2,7 +2,8 @@
 // points of the closed loop on the device: hmpc_default_plant, hmpc_plant_step_device, hmpc_rollout_device and the
 // rollout's log buffers.  Built, like hmpc_builder.hip, under the no-contraction contract (-ffp-contract=off, HMPC-A1): the plant's
 // arithmetic is compared bit for bit with a numpy restatement of the header comment.  No kernel of the solve is touched: a rollout
-// enqueues exactly what hmpc_tick_solve_device enqueues, then one launch of the plant step, per tick.
+// enqueues exactly what hmpc_tick_solve_device enqueues, then one launch of the plant step, per tick -- and between the two, while
+// hmpc_set_rollout_swing is on, the swing launch of hmpc_swing.hip.
 #include "hmpc_plant.h"
 
 #include <string.h>
@@ -153,7 +154,8 @@ int hmpc_rollout_device(hmpc_handle *h, void *device_ticks, int batch, int n_tic
     if (h->tick_warm) h->tick_shift = shift;
     int rc = hmpc_tick_solve_device(h, device_ticks, batch, dtMPC, h->d_roll_wpd.get(), /*f_ff=*/nullptr, h->d_roll_tau.get(), stream);
     if (rc != HMPC_OK) return rc;
-    pl.advance_gait = ((subtick0 + k + 1) % ticks_per_step == 0) ? 1 : 0;
+    if (h->swing_on) RC_TRY(rollout_swing_tick(h, device_ticks, batch, k, n_ticks, ticks_per_step, subtick0, s));  // (hmpc_set_rollout_swing)
+    pl.advance_gait =((subtick0 + k + 1) % ticks_per_step == 0) ? 1 : 0;
     hmpc::PlantArgs a;
     rc = plant_args(h, batch, &pl, nullptr, 0, nullptr, h->d_roll_wpd.get(), lg.summary, &a);
     if (rc != HMPC_OK) return rc;

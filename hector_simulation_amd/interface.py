@@ -55,6 +55,36 @@ def default_rollout_cost(**fields):
     return c
 
 
+# struct hmpc_swing_state and struct hmpc_motor_cmd (swing legs on the device, include/hector_mpc.h)
+SWING_STATE_DTYPE = np.dtype([("p0", "f8", (2, 3)), ("pf", "f8", (2, 3)), ("swing_time", "f8", 2), ("q_des", "f8", 10), ("first_swing", "i4", 2)],
+                             align=True)
+MOTOR_CMD_DTYPE = np.dtype([("q", "f8", 10), ("dq", "f8", 10), ("Kp", "f8", 10), ("Kd", "f8", 10), ("tau", "f8", 10)], align=True)
+SWING_DETAIL = ("swing", "pFoot_w", "pDes", "vDes", "pFoot_b", "vFoot_b")  # a detail row [16] of swing_legs: one value, then five vectors of 3
+
+
+def default_swing(**fields):
+    """``struct hmpc_swing`` with the reference's values (``hmpc_default_swing``); keyword arguments overwrite the scalar fields and the
+    arrays ``hip_yaw`` / ``hip_width_offset`` (2 x 3), ``hip_roll`` (3), ``kp`` / ``kd`` (5)."""
+    c = _lib.Swing()
+    _lib.load().hmpc_default_swing(C.byref(c))
+    for k, v in fields.items():
+        if k in ("hip_yaw", "hip_width_offset"):
+            for leg in range(2):
+                getattr(c, k)[leg][:] = [float(x) for x in v[leg]]
+        elif k in ("hip_roll", "kp", "kd"):
+            getattr(c, k)[:] = [float(x) for x in v]
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def initial_swing_state(batch: int) -> np.ndarray:
+    """The reference's initial swing state of ``batch`` instances on the host: all zero, ``first_swing = {1, 1}``."""
+    s = np.zeros(int(batch), dtype=SWING_STATE_DTYPE)
+    s["first_swing"] = 1
+    return s
+
+
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "too_large", 4: "kkt", 5: "working_set_full", 6: "ok_relaxed", 7: "sweep_mismatch", 8: "hessian_not_positive_definite", 9: "regularisation_step"}
 
 
@@ -806,19 +836,129 @@ class BatchedMPC:
         _check(self.L.hmpc_download_rollout(self.h, *[out[k].ctypes.data for k in _lib.ROLLOUT_LOG]), "hmpc_download_rollout")
         return out
 
+    # ---- swing legs on the device (include/hector_mpc.h hmpc_swing_legs_device / hmpc_tick_command_device)
+    def _to_device(self, a: np.ndarray):
+        import torch
+
+        a = np.ascontiguousarray(a)
+        return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda(self.device)
+
+    def swing_state(self, batch: int, device_ptr: int = 0, stream: int = 0):
+        """The reference's initial swing state of ``batch`` instances (all zero, ``first_swing = {1, 1}``): a ``SWING_STATE_DTYPE`` array, or
+        with ``device_ptr`` written to that HBM buffer on ``stream`` (hmpc_swing_state_init_device; nothing is returned)."""
+        if device_ptr:
+            _check(self.L.hmpc_swing_state_init_device(self.h, C.c_void_p(int(device_ptr)), int(batch), C.c_void_p(stream)),
+                   "hmpc_swing_state_init_device")
+            return None
+        return initial_swing_state(batch)
+
+    def swing_legs(self, ticks, state, cfg=None, tau=None, detail=False, device: bool = False, batch: int = 0, cmd=0, stream: int = 0):
+        """One swing update per instance (include/hector_mpc.h hmpc_swing_legs_device): ``cfg.updates`` updates of the swing state, then
+        the complete motor command.  ``cfg``: a ``default_swing()`` (``None``: the defaults).  ``device=False``: ``ticks`` is a ``TICK_DTYPE``
+        array, ``state`` a ``SWING_STATE_DTYPE`` array (``swing_state(batch)`` at the start), ``tau`` float64[batch, 10] or ``None`` (zeros),
+        ``detail`` a bool; everything is staged through HBM and the call waits: returns ``dict(cmd=MOTOR_CMD_DTYPE[batch], state=the new
+        state)`` plus ``detail`` float64[batch, 2, 16] when asked for (``SWING_DETAIL`` names its columns).  ``device=True``: ``ticks``,
+        ``state``, ``tau``, ``cmd``, ``detail`` are device pointers (0 / None as in C), ``batch`` as in C; the launch is only enqueued."""
+        c = cfg if cfg is not None else default_swing()
+        if device:
+            _check(self.L.hmpc_swing_legs_device(self.h, C.c_void_p(int(ticks or 0)), int(batch), C.byref(c), C.c_void_p(int(state or 0)),
+                                                 C.c_void_p(int(tau or 0)), C.c_void_p(int(cmd or 0)), C.c_void_p(int(detail or 0)),
+                                                 C.c_void_p(stream)), "hmpc_swing_legs_device")
+            return None
+        import torch
+
+        ticks = np.ascontiguousarray(ticks, dtype=TICK_DTYPE)
+        nb = ticks.shape[0]
+        d_t, d_s = self._to_device(ticks), self._to_device(np.ascontiguousarray(state, dtype=SWING_STATE_DTYPE).reshape(nb))
+        d_tau = None if tau is None else self._to_device(np.ascontiguousarray(tau, dtype=np.float64).reshape(nb, 10))
+        d_c = torch.zeros(nb * MOTOR_CMD_DTYPE.itemsize, dtype=torch.uint8, device=d_t.device)
+        d_d = torch.zeros((nb, 2, 16), dtype=torch.float64, device=d_t.device) if detail else None
+        ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_swing_legs_device(self.h, ptr(d_t), nb, C.byref(c), ptr(d_s), ptr(d_tau), ptr(d_c), ptr(d_d), C.c_void_p(stream)),
+               "hmpc_swing_legs_device")
+        torch.cuda.synchronize(self.device)
+        out = dict(cmd=d_c.cpu().numpy().view(MOTOR_CMD_DTYPE).copy(), state=d_s.cpu().numpy().view(SWING_STATE_DTYPE).copy())
+        if detail:
+            out["detail"] = d_d.cpu().numpy()
+        return out
+
+    def tick_command(self, ticks, state, cfg=None, device: bool = False, batch: int = 0, cmd=0, wpd=0, f_ff=0, dt_mpc: float | None = None,
+                     stream: int = 0):
+        """Ticks in, complete motor commands out (include/hector_mpc.h hmpc_tick_command_device): what ``tick_solve_device`` enqueues, then
+        the swing update reading that tick's torques.  ``device=False``: ``ticks`` a ``TICK_DTYPE`` array, ``state`` a ``SWING_STATE_DTYPE``
+        array; the call waits and returns ``dict(cmd, state, f_ff float64[batch, 2, 6], wpd float64[batch, 2], forces, status)``.
+        ``device=True``: ``ticks``, ``state``, ``cmd``, ``wpd``, ``f_ff`` are device pointers, ``batch`` as in C; only enqueued."""
+        self.generation += 1
+        c = cfg if cfg is not None else default_swing()
+        dt = self.dt_mpc if dt_mpc is None else float(dt_mpc)
+        if device:
+            _check(self.L.hmpc_tick_command_device(self.h, C.c_void_p(int(ticks or 0)), int(batch), dt, C.byref(c), C.c_void_p(int(state or 0)),
+                                                   C.c_void_p(int(wpd or 0)), C.c_void_p(int(f_ff or 0)), C.c_void_p(int(cmd or 0)),
+                                                   C.c_void_p(stream)), "hmpc_tick_command_device")
+            return None
+        import torch
+
+        ticks = np.ascontiguousarray(ticks, dtype=TICK_DTYPE)
+        nb = ticks.shape[0]
+        d_t, d_s = self._to_device(ticks), self._to_device(np.ascontiguousarray(state, dtype=SWING_STATE_DTYPE).reshape(nb))
+        d_c = torch.zeros(nb * MOTOR_CMD_DTYPE.itemsize, dtype=torch.uint8, device=d_t.device)
+        d_w = torch.zeros((nb, 2), dtype=torch.float64, device=d_t.device)
+        d_f = torch.zeros((nb, 2, 6), dtype=torch.float64, device=d_t.device)
+        torch.cuda.synchronize(self.device)
+        _check(self.L.hmpc_tick_command_device(self.h, C.c_void_p(d_t.data_ptr()), nb, dt, C.byref(c), C.c_void_p(d_s.data_ptr()),
+                                               C.c_void_p(d_w.data_ptr()), C.c_void_p(d_f.data_ptr()), C.c_void_p(d_c.data_ptr()),
+                                               C.c_void_p(stream)), "hmpc_tick_command_device")
+        forces, status = self.download()  # (waits for the stream)
+        torch.cuda.synchronize(self.device)
+        return dict(cmd=d_c.cpu().numpy().view(MOTOR_CMD_DTYPE).copy(), state=d_s.cpu().numpy().view(SWING_STATE_DTYPE).copy(),
+                    f_ff=d_f.cpu().numpy(), wpd=d_w.cpu().numpy(), forces=forces, status=status)
+
+    def set_rollout_swing(self, cfg=None, state_ptr: int = 0, cmd_log_ptr: int = 0) -> None:
+        """While a ``cfg`` is set, every tick of a rollout or rollout sweep enqueues the swing update behind its torques
+        (include/hector_mpc.h hmpc_set_rollout_swing): ``state_ptr`` = ``SWING_STATE_DTYPE[batch]`` in HBM, ``cmd_log_ptr`` =
+        ``MOTOR_CMD_DTYPE[batch, n_ticks]`` in HBM or 0.  ``cfg=None`` turns it off (the default)."""
+        _check(self.L.hmpc_set_rollout_swing(self.h, C.byref(cfg) if cfg is not None else None, C.c_void_p(int(state_ptr or 0)),
+                                             C.c_void_p(int(cmd_log_ptr or 0))), "hmpc_set_rollout_swing")
+
+    def _stage_swing(self, swing, batch: int, n_ticks: int):
+        """``swing=`` of ``rollout`` / ``rollout_sweep`` in their host form: ``True`` or a ``_lib.Swing`` (a fresh initial state) or a dict
+        ``{"cfg": ..., "state": SWING_STATE_DTYPE[batch]}``; switches the setting on over fresh HBM buffers, which it returns."""
+        import torch
+
+        if isinstance(swing, dict):
+            cfg, state = swing.get("cfg"), swing.get("state")
+        else:
+            cfg, state = (None if swing is True else swing), None
+        cfg = cfg if cfg is not None else default_swing()
+        state = initial_swing_state(batch) if state is None else np.ascontiguousarray(state, dtype=SWING_STATE_DTYPE).reshape(batch)
+        d_s = self._to_device(state)
+        d_c = torch.zeros(batch * n_ticks * MOTOR_CMD_DTYPE.itemsize, dtype=torch.uint8, device=d_s.device)
+        self.set_rollout_swing(cfg, d_s.data_ptr(), d_c.data_ptr())
+        return d_s, d_c
+
     def rollout(self, ticks, n_ticks: int, ticks_per_step: int = 8, subtick0: int = 0, plant=None, device: bool = False, batch: int = 0,
-                dt_mpc: float | None = None, stream: int = 0, instance_mass=None, ext_wrench=None):
+                dt_mpc: float | None = None, stream: int = 0, instance_mass=None, ext_wrench=None, swing=None):
         """``n_ticks`` closed-loop ticks on one stream, nothing leaving the device in between: solve, then plant step, per tick
         (include/hector_mpc.h hmpc_rollout_device).  ``device=False``: ``ticks`` is a ``TICK_DTYPE`` array; the call uploads it, waits and
         returns the log of ``download_rollout`` plus ``ticks`` = the tick structs after the last step.  ``device=True``: ``ticks`` is a
         device pointer to ``batch`` tick structs, advanced in place; the rollout is only enqueued (log: the handle's own buffers, read
-        with ``download_rollout``)."""
+        with ``download_rollout``).  ``swing`` (default ``None``: the rollout as it is without it) adds the swing update to every tick
+        (``set_rollout_swing``, for this call only): host form ``True``, a ``default_swing()`` or ``{"cfg": ..., "state": ...}`` -- the
+        result gains ``cmd`` = ``MOTOR_CMD_DTYPE[batch, n_ticks]`` and ``swing_state``; device form ``{"cfg": ..., "state": pointer,
+        "cmd_log": pointer or 0}``."""
         self.generation += 1
         dt = self.dt_mpc if dt_mpc is None else float(dt_mpc)
         if device:
             p = plant if plant is not None else default_plant()
-            _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(int(ticks)), int(batch), int(n_ticks), dt, int(ticks_per_step), int(subtick0),
-                                              C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+            if swing is not None:
+                self.set_rollout_swing(swing.get("cfg") or default_swing(), swing["state"], swing.get("cmd_log", 0))
+            try:
+                _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(int(ticks)), int(batch), int(n_ticks), dt, int(ticks_per_step),
+                                                  int(subtick0), C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+            finally:
+                if swing is not None:
+                    self.set_rollout_swing(None)
             return None
         import torch
 
@@ -826,12 +966,20 @@ class BatchedMPC:
         nb = ticks.shape[0]
         p, keep = self._stage_plant(plant, nb, instance_mass, ext_wrench)
         d_t = torch.from_numpy(ticks.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
+        sw = self._stage_swing(swing, nb, int(n_ticks)) if swing is not None else None
         torch.cuda.synchronize(self.device)
-        _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(d_t.data_ptr()), nb, int(n_ticks), dt, int(ticks_per_step), int(subtick0),
-                                          C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+        try:
+            _check(self.L.hmpc_rollout_device(self.h, C.c_void_p(d_t.data_ptr()), nb, int(n_ticks), dt, int(ticks_per_step), int(subtick0),
+                                              C.byref(p), None, C.c_void_p(stream)), "hmpc_rollout_device")
+        finally:
+            if sw is not None:
+                self.set_rollout_swing(None)
         out = self.download_rollout(nb, int(n_ticks))
         del keep
         out["ticks"] = d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy()
+        if sw is not None:
+            out["swing_state"] = sw[0].cpu().numpy().view(SWING_STATE_DTYPE).copy()
+            out["cmd"] = sw[1].cpu().numpy().view(MOTOR_CMD_DTYPE).reshape(nb, int(n_ticks)).copy()
         return out
 
     # ---- closed-loop command sweeps (include/hector_mpc.h hmpc_rollout_score_device / _select_device / _sweep_device)
@@ -951,7 +1099,7 @@ class BatchedMPC:
 
     def rollout_sweep(self, ticks, commands, n_ticks: int, ticks_per_step: int = 8, subtick0: int = 0, plant=None, cost=None, penalty=None,
                       device: bool = False, n_states: int = 0, group_size: int = 0, choice=None, dt_mpc: float | None = None,
-                      stream: int = 0, instance_mass=None, ext_wrench=None):
+                      stream: int = 0, instance_mass=None, ext_wrench=None, swing=None):
         """Every robot state rolled out in closed loop under each of its candidate commands, scored and the best picked, nothing leaving
         the device in between (include/hector_mpc.h hmpc_rollout_sweep_device).  ``device=False``: ``ticks`` is a ``TICK_DTYPE`` array
         [n_states], ``commands`` a ``COMMAND_DTYPE`` array [n_states, K], ``penalty`` float64[n_states * K] or ``None``, ``instance_mass`` /
@@ -959,16 +1107,24 @@ class BatchedMPC:
         ``tau``, ``summary`` per state) plus ``cost`` float64[n_states * K, 4], ``all_scores`` float64[n_states * K], ``ticks`` (the expanded
         tick structs after the rollout), ``log`` (``download_rollout``) and ``ticks_in`` (the robot states read back from the device: the
         sweep does not modify them).  ``device=True``: ``ticks``, ``commands``, ``penalty`` are
-        device pointers, ``n_states`` and ``group_size`` as in C, ``choice`` a ``_lib.RolloutChoice``; the chain is only enqueued."""
+        device pointers, ``n_states`` and ``group_size`` as in C, ``choice`` a ``_lib.RolloutChoice``; the chain is only enqueued.
+        ``swing``: as for ``rollout``, state and command log per EXPANDED instance (the host form returns ``cmd`` [n_states * K, n_ticks] and
+        ``swing_state``)."""
         self.generation += 1
         dt = self.dt_mpc if dt_mpc is None else float(dt_mpc)
         c = cost if cost is not None else default_rollout_cost()
         if device:
             p = plant if plant is not None else default_plant()
-            _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(int(ticks)), int(n_states), C.c_void_p(int(commands)), int(group_size),
-                                                    int(n_ticks), dt, int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
-                                                    C.c_void_p(int(penalty or 0)), C.byref(choice), C.c_void_p(stream)),
-                   "hmpc_rollout_sweep_device")
+            if swing is not None:
+                self.set_rollout_swing(swing.get("cfg") or default_swing(), swing["state"], swing.get("cmd_log", 0))
+            try:
+                _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(int(ticks)), int(n_states), C.c_void_p(int(commands)), int(group_size),
+                                                        int(n_ticks), dt, int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
+                                                        C.c_void_p(int(penalty or 0)), C.byref(choice), C.c_void_p(stream)),
+                       "hmpc_rollout_sweep_device")
+            finally:
+                if swing is not None:
+                    self.set_rollout_swing(None)
             return None
         import torch
 
@@ -982,11 +1138,16 @@ class BatchedMPC:
         d_c = torch.from_numpy(commands.view(np.uint8).reshape(nb, -1).copy()).cuda(self.device)
         d_p = None if penalty is None else torch.from_numpy(np.ascontiguousarray(penalty, dtype=np.float64).reshape(nb).copy()).cuda(self.device)
         ch, bufs = self._choice_buffers(ns, _lib.ROLLOUT_CHOICE)
+        sw = self._stage_swing(swing, nb, int(n_ticks)) if swing is not None else None
         torch.cuda.synchronize(self.device)
-        _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(d_t.data_ptr()), ns, C.c_void_p(d_c.data_ptr()), K, int(n_ticks), dt,
-                                                int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
-                                                C.c_void_p(0 if d_p is None else d_p.data_ptr()), C.byref(ch), C.c_void_p(stream)),
-               "hmpc_rollout_sweep_device")
+        try:
+            _check(self.L.hmpc_rollout_sweep_device(self.h, C.c_void_p(d_t.data_ptr()), ns, C.c_void_p(d_c.data_ptr()), K, int(n_ticks), dt,
+                                                    int(ticks_per_step), int(subtick0), C.byref(p), C.byref(c),
+                                                    C.c_void_p(0 if d_p is None else d_p.data_ptr()), C.byref(ch), C.c_void_p(stream)),
+                   "hmpc_rollout_sweep_device")
+        finally:
+            if sw is not None:
+                self.set_rollout_swing(None)
         log = self.download_rollout(nb, int(n_ticks))  # (waits for the stream)
         torch.cuda.synchronize(self.device)
         del keep
@@ -997,6 +1158,9 @@ class BatchedMPC:
         out["all_scores"] = self._device_bytes(own["score"], nb * 8).view(np.float64).copy()
         out["log"] = log
         out["ticks_in"] = d_t.cpu().numpy().reshape(-1).view(TICK_DTYPE).copy()
+        if sw is not None:
+            out["swing_state"] = sw[0].cpu().numpy().view(SWING_STATE_DTYPE).copy()
+            out["cmd"] = sw[1].cpu().numpy().view(MOTOR_CMD_DTYPE).reshape(nb, int(n_ticks)).copy()
         return out
 
     def time_solve(self, reps: int, stream: int = 0) -> float:

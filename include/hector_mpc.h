@@ -1218,6 +1218,125 @@ int hmpc_rollout_sweep_device(hmpc_handle *h, const void *device_ticks, int n_st
                               const struct hmpc_rollout_cost *cost, const double *device_penalty, const struct hmpc_rollout_choice *choice,
                               void *stream);
 int hmpc_get_device_rollout_sweep(hmpc_handle *h, void **ticks_final, double **cost, double **score);
+/* ---- swing legs on the device: Bezier targets, inverse kinematics, complete motor commands (csrc/hmpc_swing.h) ----
+ * hmpc_tick_solve_device ends in forces and the stance feed-forward torques; the reference's controller ends in a COMPLETE command per joint
+ * (tau, q, dq, Kp, Kd -- LowlevelCmd, common/LegController.cpp:90-97), and for a leg in swing that command is a joint-angle target with gains:
+ * swingLegController::updateSwingLeg() of common/SwingLegController.cpp (line numbers below are that file's unless another is named).  One
+ * launch performs it for every instance: thread g -> instance g / 2, leg g % 2 (0 = left), 256 threads per workgroup, nothing synchronised,
+ * plain loads and stores.  The two legs of an instance share only what they read.
+ *
+ * THE ARITHMETIC IS A CONTRACT, as the plant's: ALL of it binary64, every operation a correctly rounded IEEE operation (+ - * / sqrt and
+ * comparisons; no contraction), evaluated as C evaluates the expressions written here -- parentheses first, operators of equal precedence
+ * from left to right, so a * b * c is (a * b) * c and a + b - c is (a + b) - c.  Trigonometry: sincos(x) = det_sincos, asin(v) = det_asin(v),
+ * acos(v) = det_atan2(sqrt((1 - v) * (1 + v)), v) of csrc/hmpc_math.h (a libm restatement agrees to a few ulp only).  PI3 = 3.14159 (the
+ * LegController's), PI = 3.141592653589793 (M_PI, the IK's).  clamp1(v) = max(-1, min(v, 1)) as std::max / std::min order their
+ * arguments: t = (1 < v) ? 1 : v;  clamp1 = (-1 < t) ? t : -1  (a NaN comes out as -1).
+ * Per instance i and leg j, tick struct tk, constants c (struct hmpc_swing), state st (struct hmpc_swing_state of instance i, of which leg
+ * j reads and writes only its own entries), h = the handle's horizon, R = tk.rBody (row-major, world -> body), pos = tk.position, v = tk.vWorld:
+ *   1. Joint angles (the rule of hmpc_tick_solve_device's torques).  q0, q1 = tk.leg_q[5 j + 0, 1]; with tk.flags & HMPC_TICK_LEG_Q_MOTOR
+ *      q2 = leg_q[5 j + 2] + 0.3 * PI3, q3 = leg_q[5 j + 3] - 0.6 * PI3, q4 = leg_q[5 j + 4] + 0.3 * PI3 (LegController.cpp:111-113), else as stored.
+ *   2. Foot position.  (sk, ck) = sincos(qk), k = 0 .. 4;  side = (j == 0) ? 1.0 : -1.0;  data[leg].p of LegController.cpp:190-193:
+ *        A = c0 * c2 - s0 * s1 * s2;   B = c0 * s2 + c2 * s0 * s1;   C = c2 * s0 + c0 * s1 * s2;   D = s0 * s2 - c0 * c2 * s1
+ *        p[0] = -(3 * c0) / 200 - (9 * s4 * (c3 * A - s3 * B)) / 250 - (11 * c0 * s2) / 50 - (side * s0) / 50 - (11 * c3 * B) / 50
+ *               - (11 * s3 * A) / 50 - (9 * c4 * (c3 * B + s3 * A)) / 250 - (23 * c1 * side * s0) / 1000 - (11 * c2 * s0 * s1) / 50
+ *        p[1] = (c0 * side) / 50 - (9 * s4 * (c3 * C - s3 * D)) / 250 - (3 * s0) / 200 - (11 * s0 * s2) / 50 - (11 * c3 * D) / 50
+ *               - (11 * s3 * C) / 50 - (9 * c4 * (c3 * D + s3 * C)) / 250 + (23 * c0 * c1 * side) / 1000 + (11 * c0 * c2 * s1) / 50
+ *        p[2] = (23 * side * s1) / 1000 - (11 * c1 * c2) / 50 - (9 * c4 * (c1 * c2 * c3 - c1 * s2 * s3)) / 250
+ *               + (9 * s4 * (c1 * c2 * s3 + c1 * c3 * s2)) / 250 - (11 * c1 * c2 * c3) / 50 + (11 * c1 * s2 * s3) / 50 - 3.0 / 50.0
+ *      u[k] = c.hip_yaw[j][k] + p[k];   pFoot_w[k] = pos[k] + (R[k] * u[0] + R[3 + k] * u[1] + R[6 + k] * u[2]), k = 0, 1;   pFoot_w[2] = +0.0   (:59-68)
+ *   3. Swing sub-phase (GaitGenerator.cpp:54-79, 109-113).  cur = tk.gait_iteration * c.ticks_per_step + c.subtick;  per = c.ticks_per_step * h;
+ *      phase = (double)(cur % per) / (double)per;   offP = (double)tk.gait_offsets[j] / (double)h;   durP = (double)tk.gait_durations[j] / (double)h
+ *      so = offP + durP;  if so > 1: so = so - 1.;    sd = 1. - durP;    pr = phase - so;  if pr < 0: pr = pr + 1.
+ *      swing = (pr > sd) ? 0. : (sd == 0 ? 0. : pr / sd)     -- the inner test is deviation 2 below
+ *   4. - 6a.  `c.updates` times, u = 0 .. updates - 1 (the reference calls updateSwingLeg() once per foot: twice a tick; what an update reads
+ *      of the tick does not change, so only these state steps repeat):
+ *      4.  Timer (:80-91).  if st.first_swing[j]: st.swing_time[j] = c.dtMPC * (double)(h - tk.gait_durations[0])
+ *          else: st.swing_time[j] = st.swing_time[j] - c.dt_update;  if st.swing_time[j] <= 0: st.first_swing[j] = 1
+ *      5.  Touchdown point (:96-126).  vdw[a] = R[a] * tk.v_des_robot[0] + R[3 + a] * tk.v_des_robot[1] + R[6 + a] * 0.0, a = 0, 1 (the builder's expression)
+ *          rh[k] = R[k] * c.hip_yaw[j][0] + R[3 + k] * c.hip_yaw[j][1] + R[6 + k] * c.hip_yaw[j][2];    Pf[k] = (pos[k] + rh[k]) + v[k] * st.swing_time[j]
+ *          rel[a] = c.place_gain_v * v[a] * 0.5 * (double)tk.gait_durations[0] * c.dtMPC + c.place_gain_err * (v[a] - vdw[a])
+ *          rel[a] = (double)fminf(fmaxf((float)rel[a], (float)-c.place_max), (float)c.place_max)         (the reference's binary32 narrowing, kept)
+ *          st.pf[j] = (Pf[0] + rel[0], Pf[1] + rel[1], +0.0)
+ *      6a. First swing update (:134-139).  if swing > 0 and st.first_swing[j]: st.first_swing[j] = 0;  st.p0[j] = pFoot_w
+ *   If swing > 0 (else: pDes, vDes, pFoot_b, vFoot_b of the detail row are +0.0 and steps 6b - 7 are skipped):
+ *   6b. Trajectory (FootSwingTrajectory.cpp:17-36 over Interpolation.h:53-74), p0 = st.p0[j], pf = st.pf[j], with
+ *         bez(y0, yf, x) = y0 + (x * x * x + 3 * (x * x * (1 - x))) * (yf - y0);      dbez(y0, yf, x) = (6 * x * (1 - x)) * (yf - y0)
+ *       pDes[k] = bez(p0[k], pf[k], swing),  vDes[k] = dbez(p0[k], pf[k], swing), k = 0, 1;   top = p0[2] + c.height
+ *       swing < 0.5:  x = swing * 2;  pDes[2] = bez(p0[2], top, x),  vDes[2] = dbez(p0[2], top, x);    else:  x = swing * 2 - 1;  pDes[2] = bez(top, pf[2], x),  vDes[2] = dbez(top, pf[2], x)
+ *       d = pDes - pos;   pFoot_b[k] = (R[3 k] * d[0] + R[3 k + 1] * d[1] + R[3 k + 2] * d[2]) + c.hip_width_offset[j][k]
+ *       e[k] = vDes[k] * 0.0 - v[k];   vFoot_b[k] = R[3 k] * e[0] + R[3 k + 1] * e[1] + R[3 k + 2] * e[2]                                    (:141-149)
+ *   7.  computeIK (:157-187).  sideK = (j == 0) ? -1.0 : 1.0;   hr = (c.hip_roll[0] - c.ik_hip_x, 0.0, c.hip_yaw[0][2] + c.hip_roll[2] * 2);   f = pFoot_b - hr
+ *         d3 = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);   dyz = sqrt(f[1] * f[1] + f[2] * f[2]);   dh = c.ik_horizontal;   L = c.ik_link
+ *         m = dyz * dyz - dh * dh;   dv = sqrt((0.00001 < m) ? m : 0.00001);   dxz = sqrt(d3 * d3 - dh * dh)
+ *         a1 = clamp1(dxz / (2.0 * L));   a2 = clamp1(dv / dxz);   div = |f[0]|;  if div == 0.0: div = 1e-6
+ *         ik[0] = 0.0;    ik[1] = asin(clamp1(f[1] / dyz)) + asin(clamp1(dh * sideK / dyz))
+ *         ik[2] = acos(a1) - acos(a2) * f[0] / div;    ik[3] = 2.0 * asin(clamp1(dxz / 2.0 / L)) - PI;    ik[4] = -q3 - q2       (q2, q3 of step 1)
+ *         ik[2] = ik[2] - 0.3 * PI;   ik[3] = ik[3] + 0.6 * PI;   ik[4] = ik[4] - 0.3 * PI
+ *   8.  setDesiredJointState (:192-219).  swing > 0:  st.q_des[5 j + k] = ik[k];  Kp[5 j + k] = c.kp[k], Kd[5 j + k] = c.kd[k].  Otherwise Kp = Kd = +0.0
+ *       and st.q_des is LEFT AS THE LAST UPDATE WROTE IT (zeros before the first swing).  Command of instance i (struct hmpc_motor_cmd), joints 5 j .. 5 j + 4:
+ *       q = st.q_des, dq = +0.0, Kp, Kd, tau = device_tau ? device_tau[10 i + 5 j + k] : +0.0.
+ *   Detail row [i][j][16], when asked for: swing, pFoot_w[3], pDes[3], vDes[3], pFoot_b[3], vFoot_b[3].
+ * Reference oddities KEPT: the timer subtracts the constant dt_update = _dt = 0.001 per update whatever the tick's length; a leg whose sub-phase
+ * is exactly 0 is not in swing on that tick; the touchdown heuristic is not the plant's (1.75, 0.1, clamp 0.3, vWorld * swingTimes); the IK does
+ * not invert the leg's forward kinematics at the toe (DESIGN.md section 4.25 says by how much); HMPC_TICK_FALLEN is not looked at.
+ * DEVIATIONS, both documented in DESIGN.md section 4.25: (1) tau of the command is always the tick's J' f_ff (device_tau) -- the reference
+ * leaves a stale feedforwardForce on the single tick where a leg is neither in swing nor in stance; (2) a leg whose stance lasts the whole
+ * horizon has sd = 0 and the reference forms 0 / 0 at phase 0: a NaN that only ever meets `> 0`; here it is +0.0, the same "not in swing".
+ *
+ * struct hmpc_swing_state: one per instance, in HBM, owned by the caller, carried from tick to tick.  All-zero bytes with first_swing = {1, 1}
+ * is the reference's initial state: hmpc_swing_state_init_device writes it for `batch` instances on `stream`.
+ * hmpc_swing_legs_device: the update alone.  device_ticks = hmpc_tick_inputs[batch] (read only), device_state [batch], device_tau
+ * [batch][10] or NULL (= zeros), device_cmd [batch], device_detail double[batch][2][16] or NULL.  It does not replace the handle's batch and
+ * reads nothing of a solve.
+ * hmpc_tick_command_device: what hmpc_tick_solve_device enqueues (its torques go to a small buffer of the handle's), then the swing launch
+ * reading that tick's torques: forces, status, f_ff, wpd and cmd.tau are bit for bit what hmpc_tick_solve_device leaves.  cfg->dtMPC is
+ * read as given (the dtMPC argument is the solve's).
+ * hmpc_set_rollout_swing: while cfg != NULL is set, every tick of hmpc_rollout_device and hmpc_rollout_sweep_device enqueues the swing launch
+ * behind the tick's torque launch (before the plant step), with subtick = (subtick0 + k) % ticks_per_step and ticks_per_step the rollout's own
+ * (the two members of cfg are not read; updates and the rest are, and are checked by the rollout); device_state [batch] as above (for a sweep:
+ * per EXPANDED instance), device_cmd_log [batch][n_ticks] or NULL: row (i, k) = the command of instance i at tick k.  cfg is copied; the two
+ * buffers are the caller's and must outlive the rollouts.  cfg == NULL turns it off (the default): a rollout then enqueues exactly what it
+ * did before.  The plant never reads the command (the plant has no legs); struct hmpc_rollout_log is unchanged.
+ * HMPC_E_ARG, nothing enqueued: a NULL handle, ticks, cfg, state or cmd; batch < 0 or > max_batch; updates < 1, ticks_per_step < 1, subtick < 0
+ * or >= ticks_per_step; a three-contact handle.  hmpc_set_rollout_swing: a NULL handle, cfg != NULL with a NULL state or updates < 1, a
+ * three-contact handle.  Device groups: per member, through hmpc_group_member. */
+struct hmpc_swing {
+  double dt_update;               /* 0.001: what one update takes off the swing timer (the reference's constant _dt) */
+  double dtMPC;                   /* 0.04: seconds per horizon step (_dtSwing) */
+  int updates;                    /* 2: updates per launch (run() calls updateSwingLeg() once per foot), >= 1 */
+  int ticks_per_step;             /* 40: ticks per horizon step (iterationsBetweenMPC), >= 1 */
+  int subtick;                    /* 0: this tick's position within its horizon step, 0 .. ticks_per_step - 1 */
+  int reserved;                   /* 0 */
+  double height;                  /* 0.15: apex of the swing above p0 */
+  double place_gain_v;            /* 1.75 */
+  double place_gain_err;          /* 0.1 */
+  double place_max;               /* 0.3: clamp of the touchdown offset, applied in binary32 */
+  double hip_yaw[2][3];           /* Biped.h getHipYawLocation: (-0.005, -0.057, -0.126) for leg 0, y negated for leg 1; body frame */
+  double hip_roll[3];             /* Biped.h getHipRollLocation(0): (0.0465, 0.015, -0.0705) */
+  double hip_width_offset[2][3];  /* (-0.015, 0.055, 0) for leg 0, y negated for leg 1 (SwingLegController.cpp:145-146) */
+  double ik_link;                 /* 0.22: thigh and calf length of the IK */
+  double ik_horizontal;           /* 0.0205: distance_horizontal */
+  double ik_hip_x;                /* 0.06: taken off hip_roll[0] */
+  double kp[5], kd[5];            /* (30, 30, 30, 30, 20), (1, 1, 1, 1, 1): joint gains of a swing leg */
+};
+struct hmpc_swing_state {
+  double p0[2][3], pf[2][3];      /* the trajectory's initial and final position per leg, world frame */
+  double swing_time[2];           /* swingTimes */
+  double q_des[10];               /* commands[leg].qDes as the last swing update left it */
+  int32_t first_swing[2];         /* firstSwing */
+};
+struct hmpc_motor_cmd {
+  double q[10], dq[10], Kp[10], Kd[10], tau[10];   /* left leg 0-4, right leg 5-9 */
+};
+void hmpc_default_swing(struct hmpc_swing *cfg);
+int hmpc_swing_state_init_device(hmpc_handle *h, struct hmpc_swing_state *device_state, int batch, void *stream);
+int hmpc_swing_legs_device(hmpc_handle *h, const void *device_ticks, int batch, const struct hmpc_swing *cfg,
+                           struct hmpc_swing_state *device_state, const double *device_tau, struct hmpc_motor_cmd *device_cmd,
+                           double *device_detail, void *stream);
+int hmpc_tick_command_device(hmpc_handle *h, const void *device_ticks, int batch, double dtMPC, const struct hmpc_swing *cfg,
+                             struct hmpc_swing_state *device_state, double *device_wpd_out, double *device_f_ff,
+                             struct hmpc_motor_cmd *device_cmd, void *stream);
+int hmpc_set_rollout_swing(hmpc_handle *h, const struct hmpc_swing *cfg, void *device_state, struct hmpc_motor_cmd *device_cmd_log);
 /* copies the current batch's packed records device -> host (parity hook for f1/f2) */
 int hmpc_download_records(hmpc_handle *h, void *host_records);
 

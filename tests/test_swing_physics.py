@@ -1,0 +1,150 @@
+"""Physics the text of the swing contract was not written from (no GPU): closed forms of the Bezier trajectory, the geometry of the IK, the
+touchdown clamp -- for the Python mirror (tests/swing_mirror.py) and for the CPU build of csrc/hmpc_swing.h (tests/src/swing_on_host.cpp).
+
+The ankle identity.  The reference's IK inverts the reference's forward kinematics WITH THE 0.04 m TOE LINK REMOVED, up to a constant
+offset: over 4 000 body-frame foot positions p = hipYaw + uniform([-0.15, 0.15], [-0.08, 0.08], [-0.45, -0.28]) with no clamp active
+(checked), FK_ankle(IK(p + hipWidthOffSet)) - p has mean (-0.0215, +-0.0204, +0.0807) m and a max-min spread of (4.5e-7, 5.2e-4, 2.42e-3) m
+per leg -- figures measured in numpy from the reference's formulas, independent of this library.  The bound is twice those figures.  With
+the IK's `side` flipped the spread is (., 8.2e-3, 4.2e-2), with the knee bending the other way 0.4: both wrong variants of the mirror are
+built here and must fail the bound."""
+import numpy as np
+import pytest
+
+import swing_mirror as sm
+from hector_simulation_amd import interface
+from test_swing_kernel_on_host import build_exe, ik_on_host, run_on_host
+
+SPREAD = np.array([4.5e-7, 5.2e-4, 2.42e-3])
+MEAN = np.array([-0.0215, 0.0204, 0.0807])
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return build_exe(str(tmp_path_factory.mktemp("swingphys") / "swing_on_host"))
+
+
+def test_bezier_closed_forms():
+    rng = np.random.default_rng(3)
+    for _ in range(20):
+        p0, pf = list(rng.uniform(-1, 1, 2)) + [0.0], list(rng.uniform(-1, 1, 2)) + [0.0]
+        height = float(rng.uniform(0.05, 0.2))
+        p, v = sm.trajectory(p0, pf, height, 0.0)
+        assert p == p0 and v == [0.0, 0.0, 0.0]  # phase 0: p0, at rest
+        p, v = sm.trajectory(p0, pf, height, 1.0)
+        np.testing.assert_allclose(p, pf, rtol=0, atol=1e-15)  # phase 1: pf (p0 + 1 * (pf - p0): an ulp), at rest
+        assert p[2] == pf[2] and v == [0.0, 0.0, 0.0]
+        p, v = sm.trajectory(p0, pf, height, 0.5)
+        assert p[2] == p0[2] + height and v[2] == 0.0  # the apex
+        np.testing.assert_allclose(p[:2], [0.5 * (a + b) for a, b in zip(p0[:2], pf[:2])], rtol=0, atol=1e-15)
+        # vDes is the derivative of pDes in phase: central differences, O(step^2); the third derivative of the cubic is 12 |pf - p0|, of the
+        # height polynomial (in phase) 96 height -> error <= step^2 / 6 of that, and 1e-9 for the rounding of the difference quotient
+        step = 1e-4
+        for ph in (0.1, 0.3, 0.45, 0.55, 0.7, 0.9):
+            lo, hi = sm.trajectory(p0, pf, height, ph - step)[0], sm.trajectory(p0, pf, height, ph + step)[0]
+            v = sm.trajectory(p0, pf, height, ph)[1]
+            for k in range(3):
+                third = 12 * abs(pf[k] - p0[k]) if k < 2 else 96 * height
+                scale = 1.0 if k < 2 else 2.0  # (the height runs at twice the phase: d pDes[2] / d phase = 2 vDes[2])
+                assert abs((hi[k] - lo[k]) / (2 * step) - scale * v[k]) <= step * step / 6 * third + 1e-9
+
+
+def test_bezier_closed_forms_in_the_host_build(exe, tmp_path):
+    """the phases a gait reaches exactly: 0.5 (the apex) for either leg, 1 (touchdown: pDes = pf) for the leg whose swing ends the cycle"""
+    nb = 8
+    t = sm.walking_ticks(nb, seed=41)
+    st = interface.initial_swing_state(nb)
+    st["first_swing"] = 0
+    st["swing_time"] = 0.05
+    st["p0"][:, :, :2] = t["position"][:, None, :2] + np.array([[-0.05, 0.06], [-0.05, -0.06]])
+    for gi, sub, leg, phase in ((7, 1, 0, 0.5), (2, 1, 1, 0.5), (5, 0, 1, 1.0)):
+        t["gait_iteration"] = gi
+        cfg = sm.default_swing(ticks_per_step=2, subtick=sub)
+        _, s1, d = run_on_host(exe, tmp_path, t, st, cfg)
+        assert (d[:, leg, 0] == phase).all()
+        if phase == 0.5:
+            assert (d[:, leg, 6] == cfg["height"]).all() and (d[:, leg, 9] == 0.0).all()
+            np.testing.assert_allclose(d[:, leg, 4:6], 0.5 * (st["p0"][:, leg, :2] + s1["pf"][:, leg, :2]), rtol=0, atol=1e-15)
+        else:
+            np.testing.assert_allclose(d[:, leg, 4:7], s1["pf"][:, leg], rtol=0, atol=1e-15)
+            assert (d[:, leg, 7:10] == 0.0).all()
+
+
+def ankle_rows(seed=0, n=4000):
+    c = sm.default_swing()
+    rng = np.random.default_rng(seed)
+    p = np.stack([rng.uniform(-0.15, 0.15, n), rng.uniform(-0.08, 0.08, n), rng.uniform(-0.45, -0.28, n)], axis=1)
+    leg = np.arange(n) % 2
+    p = p + np.array(c["hip_yaw"])[leg]
+    rows = np.concatenate([p + np.array(c["hip_width_offset"])[leg], leg[:, None].astype(np.float64), np.full((n, 1), 0.5), np.full((n, 1), -1.0)], axis=1)
+    return c, p, leg, rows
+
+
+def ankle_residual(c, p, leg, q_des):
+    """FK_ankle(q_des) - p: the reference's data[leg].p without its toe terms at the motor angles + the LegController's offsets, + hipYaw"""
+    out = np.zeros_like(p)
+    for n in range(len(p)):
+        q = q_des[n]
+        qq = [q[0], q[1], q[2] + 0.3 * sm.PI3, q[3] - 0.6 * sm.PI3, q[4] + 0.3 * sm.PI3]
+        out[n] = np.array(c["hip_yaw"][leg[n]]) + np.array(sm.leg_p(qq, 1.0 if leg[n] == 0 else -1.0, toe=False)) - p[n]
+    return out
+
+
+def spreads(res, leg):
+    return [res[leg == j].max(axis=0) - res[leg == j].min(axis=0) for j in range(2)], [res[leg == j].mean(axis=0) for j in range(2)]
+
+
+def check_identity(res, leg):
+    sp, mean = spreads(res, leg)
+    for j in range(2):
+        assert (sp[j] <= 2 * SPREAD).all(), (j, sp[j])
+        np.testing.assert_allclose(mean[j], MEAN * np.array([1.0, 1.0 if j == 0 else -1.0, 1.0]), rtol=0, atol=2e-4)
+
+
+def test_ik_ankle_identity_of_the_mirror_and_its_two_wrong_variants():
+    c, p, leg, rows = ankle_rows()
+    q, clamped = np.zeros((len(p), 5)), 0
+    for n in range(len(p)):
+        info = {}
+        q[n] = sm.ik(list(rows[n, :3]), c, int(leg[n]), 0.5, -1.0, info=info)
+        clamped += info["clamped"]
+    assert clamped == 0
+    check_identity(ankle_residual(c, p, leg, q), leg)
+    for wrong, axis, least in (("flip_side", 2, 4.2e-2 / 2), ("flip_knee", 0, 0.4 / 2)):
+        qw = np.array([sm.ik(list(rows[n, :3]), c, int(leg[n]), 0.5, -1.0, **{wrong: True}) for n in range(len(p))])
+        sp, _ = spreads(ankle_residual(c, p, leg, qw), leg)
+        for j in range(2):
+            assert not (sp[j] <= 2 * SPREAD).all() and sp[j][axis] > least, (wrong, j, sp[j])
+
+
+def test_ik_ankle_identity_of_the_host_build(exe, tmp_path):
+    c, p, leg, rows = ankle_rows()
+    q = ik_on_host(exe, tmp_path, rows, c)
+    check_identity(ankle_residual(c, p, leg, q), leg)
+    # and the kernel's IK is the mirror's within the trigonometric tolerance (no position of the box is near the acos pole: |f[0]| >= 1e-3
+    # is asserted for the rows compared)
+    f0 = rows[:, 0] - (c["hip_roll"][0] - c["ik_hip_x"])
+    far = np.abs(f0) >= sm.F0_MIN
+    qm = np.array([sm.ik(list(rows[n, :3]), c, int(leg[n]), 0.5, -1.0) for n in range(len(p))])
+    assert far.sum() > 3900 and np.abs(q[far] - qm[far]).max() <= sm.TRIG_TOL
+
+
+@pytest.mark.parametrize("impl", ["mirror", "host"])
+def test_touchdown_clamp_lands_on_float_0_3(impl, exe, tmp_path):
+    """two ticks driven past +-0.3 m on each side: the touchdown offset is (double)(float)0.3 exactly, the reference's fminf / fmaxf narrowing"""
+    t = sm.walking_ticks(4, seed=43)
+    t["vWorld"][:, :2] = [[3.0, 3.0], [-3.0, -3.0], [3.0, -3.0], [-3.0, 3.0]]
+    st = interface.initial_swing_state(4)
+    cfg = sm.default_swing(ticks_per_step=2)
+    lim = float(np.float32(0.3))
+    assert lim != 0.3
+    for tick in range(2):
+        cfg["subtick"] = tick
+        _, st, _ = sm.update(t, st, cfg) if impl == "mirror" else run_on_host(exe, tmp_path, t, st, cfg)
+        for i in range(4):
+            R, pos, v = t["rBody"][i], t["position"][i], t["vWorld"][i]
+            for j in range(2):
+                hy = cfg["hip_yaw"][j]
+                for a in range(2):
+                    rh = float(R[a]) * hy[0] + float(R[3 + a]) * hy[1] + float(R[6 + a]) * hy[2]
+                    Pf = (float(pos[a]) + rh) + float(v[a]) * float(st["swing_time"][i, j])
+                    assert st["pf"][i, j, a] == Pf + (lim if v[a] > 0 else -lim)
