@@ -26,6 +26,7 @@ EXPORTS = [
     "hmpc_upload_records_strided_async", "hmpc_set_max_iterations", "hmpc_legacy_set_max_iterations", "hmpc_tick_solve_device", "hmpc_set_dispatch_order",
     "hmpc_set_handover", "hmpc_default_params", "hmpc_set_params", "hmpc_get_params", "hmpc_legacy_set_params", "hmpc_group_set_params",
     "hmpc_solve_command_sweep", "hmpc_set_instance_mu", "hmpc_group_solve_command_sweep", "hmpc_debug_handover_slots",
+    "hmpc_debug_set_front_prologue", "hmpc_debug_front_scalars",
     "hmpc_predict_states", "hmpc_set_device_prediction", "hmpc_get_device_prediction", "hmpc_download_prediction",
     "hmpc_legacy_predicted_state",
     "hmpc_sweep_select", "hmpc_set_device_selection", "hmpc_get_device_selection", "hmpc_download_selection", "hmpc_tick_sweep_device",
@@ -258,6 +259,8 @@ def load():
     L.hmpc_group_last_error.restype = C.c_char_p
     L.hmpc_debug_phase_cycles.argtypes = [vp, vp]
     L.hmpc_debug_handover_slots.argtypes = [vp, vp]
+    L.hmpc_debug_set_front_prologue.argtypes = [vp, ci]
+    L.hmpc_debug_front_scalars.argtypes = [vp, vp]
     # the set, get and download entries of every derived result: one pointer per array of its family (interface.RESULTS), behind the handle
     # and, for the multi-seed adjoint, the seed count; the selection's get reports its groups last; the chain passes its struct
     from .interface import RESULTS  # (here, not at the top: interface.py imports this module)

@@ -20,12 +20,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhector_mpc_hip.so")
 VARIANT_GROUPS = 4  # = HMPC_VARIANT_GROUPS of csrc/hmpc_variants.h
 # the units of the library besides the kernel family: the batched C ABI, the results derived from a solve, what a solve launches, the reference's interface, device groups,
-# and the units that compile the kernels launched around a solve (builder, prediction, selection, margins, certificate, feedback gains, the adjoints, the plant step of the closed loop, the score and selection of closed-loop command sweeps, the swing legs).  THE list: compile_commands
+# and the units that compile the kernels launched around a solve (builder, prediction, selection, margins, certificate, feedback gains, the adjoints, the plant step of the closed loop, the score and selection of closed-loop command sweeps, the swing legs, the scalar front of the assembly ahead of the fast solve).  THE list: compile_commands
 # and every script that builds the library by hand (scripts/sanitize_host.sh) take the units from here.
 HOST_SOURCES = ["hmpc_capi.hip", "hmpc_results.hip", "hmpc_launch.hip", "hmpc_legacy.hip", "hmpc_group.hip", "hmpc_builder.hip", "hmpc_predict.hip",
                 "hmpc_select.hip", "hmpc_margins.hip", "hmpc_certificate.hip", "hmpc_feedback.hip", "hmpc_adjoint.hip", "hmpc_adjoint_multi.hip",
                 "hmpc_model_adjoint.hip", "hmpc_limit_adjoint.hip", "hmpc_pose_adjoint.hip", "hmpc_adjoint_chain.hip", "hmpc_plant.hip", "hmpc_rollout_score.hip",
-                "hmpc_swing.hip"]
+                "hmpc_swing.hip", "hmpc_front.hip"]
 # every header and unit of csrc/, so that a new header can never be left out of the staleness hash
 DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))) + [os.path.join("..", "..", "include", "hector_mpc.h")]
 # -ffp-contract=off is part of the numerical contract (HMPC-A1): every fused multiply-add in the source is explicit

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "hmpc_builder_launch.h"
+#include "hmpc_front.h"
 #include "hmpc_handle.h"
 #include "hmpc_record.h"
 
@@ -464,6 +465,29 @@ int hmpc_debug_handover_slots(hmpc_handle *h, int *slots) {
   return HMPC_OK;
 }
 
+int hmpc_debug_set_front_prologue(hmpc_handle *h, int on) {
+  if (!h) return HMPC_E_ARG;
+  h->front_prologue = on ? 1 : 0;  // (read at the head of the next fast pass: nothing enqueued depends on it)
+  return HMPC_OK;
+}
+
+int hmpc_debug_front_scalars(hmpc_handle *h, void *out) {
+  if (!h || !out || h->nc != 2) return HMPC_E_ARG;
+  if (h->batch == 0) return HMPC_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  const int vi = fast_variant(/*long_h=*/h->setup.horizon > 10, /*size=*/1, /*sweep=*/false);  // (a variant that reads the blocks, whatever the batch's own is)
+  const int was = h->front_prologue;
+  h->front_prologue = 1;
+  bool ready = false;
+  const int rc = enqueue_front(h, h->last_stream, &vi, 1, &ready);
+  h->front_prologue = was;
+  if (rc != HMPC_OK) return rc;
+  if (!ready) return HMPC_E_ARG;
+  RC_TRY(settle(h));
+  HIP_TRY(hipMemcpy(out, h->d_front.get(), (size_t)h->batch * sizeof(hmpc::FrontScalars), hipMemcpyDeviceToHost));
+  return HMPC_OK;
+}
+
 int hmpc_debug_phase_cycles(hmpc_handle *h, long long *cycles /*[batch][NPROF = 32]*/) {
 #ifndef HMPC_PROFILE
   (void)h;
@@ -477,7 +501,15 @@ int hmpc_debug_phase_cycles(hmpc_handle *h, long long *cycles /*[batch][NPROF = 
   if (!h->d_prof.get()) HIP_TRY(h->d_prof.alloc((size_t)h->max_batch * hmpc::NPROF));
   HIP_TRY(hipMemset(h->d_prof.get(), 0, nb));
   // (with the device-side repair on, the whole chain: an instance's slot then holds the numbers of the LAST variant that ran it)
-  int rc = h->device_repair ? enqueue_solve(h, h->last_stream, false) : launch(h, h->last_stream, pick_variant(h), LaunchOpt());
+  int rc;
+  if (h->device_repair) {
+    rc = enqueue_solve(h, h->last_stream, false);
+  } else {  // (one launch of the batch's variant behind the prologue a solve puts in front of it: the product path)
+    const int vi = pick_variant(h);
+    LaunchOpt po;
+    rc = enqueue_front(h, h->last_stream, &vi, 1, &po.front_ready);
+    if (rc == HMPC_OK) rc = launch(h, h->last_stream, vi, po);
+  }
   if (rc != HMPC_OK) return rc;
   RC_TRY(settle(h));
   HIP_TRY(hipMemcpy(cycles, h->d_prof.get(), (size_t)h->batch * hmpc::NPROF * sizeof(long long), hipMemcpyDeviceToHost));

@@ -149,6 +149,11 @@ struct hmpc_handle {  // (opaque to callers: its constructor and destructor are 
   hmpc_swing swing_cfg{};
   hmpc_swing_state *swing_state = nullptr;
   hmpc_motor_cmd *swing_cmd_log = nullptr;
+  // stages A1 / A2 ahead of the fast two-contact launches (front_scalars_kernel, hmpc_front.hip): one FrontScalars block per instance,
+  // [max_batch], allocated by the first solve that enqueues the prologue.  Written and read inside ONE enqueue on one stream
+  // (enqueue_front, then the launches whose LaunchOpt says front_ready): no later call reads it, so no block can be stale.
+  DeviceBuffer<unsigned char> d_front;
+  int front_prologue = 1;  // hmpc_debug_set_front_prologue: 0 = every launch runs the two stages in the kernel
   DeviceBuffer<double> d_sweep_m;  // command sweeps: every group's M = H^-1, [groups][36][threads per workgroup] doubles (grown on demand)
 };
 
@@ -170,6 +175,7 @@ struct LaunchOpt {
   int skip_ok = 0;         // list launch: instances an earlier pass over the same list solved are left alone (1: ok / ok-relaxed, 2: ok only)
   int sweep_k = 0, sweep_phase = 0;  // command sweep: group size; phase 0 = one workgroup per group forms M, 1 = one per instance solves with it (a SWEEP variant)
   bool list_indefinite = false;  // device-side chain, safe launch: instances ended as HMPC_S_INDEFINITE are appended to the handle's short list
+  bool front_ready = false;  // the caller has just enqueued the prologue for the whole batch on this stream (enqueue_front): a variant that reads it gets KernelArgs::front
   int reg_step = 0;        // safe pass over an index list: regularisation step 1 / 2 for instances whose Hessian is not positive definite (KernelArgs::reg_step)
 };
 
@@ -213,6 +219,10 @@ int scratch(hmpc_handle *h, size_t bytes, void **out);
 // prediction and margins kernels assemble from the very values the solve kernels do.
 void set_problem_args(const hmpc_handle *h, hmpc::KernelArgs &a);
 int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o);                       // one launch of variants()[vi]
+// The prologue of a fast pass whose launches are the variants vis[0 .. n): front_scalars_kernel over the current batch on `stream`, when
+// at least one of them reads it (and the handle's switch is on, no external QP is set).  *ready = whether it was enqueued: what the
+// caller passes on as LaunchOpt::front_ready to the launches that follow on the same stream, and to nothing else.
+int enqueue_front(hmpc_handle *h, hipStream_t stream, const int *vis, int n, bool *ready);
 int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes, LaunchOpt o);          // the fast pass of one solve
 int enqueue_solve(hmpc_handle *h, hipStream_t stream, bool carry_wset);                           // what hmpc_solve enqueues
 int enqueue_command_sweep(hmpc_handle *h, hipStream_t stream, int group_size);                    // what hmpc_solve_command_sweep enqueues (group_size > 1)

@@ -43,6 +43,7 @@
 
 #include "hmpc_kernel_args.h"
 #include "hmpc_record.h"  // RecLayout (RL:: below), stance()
+#include "hmpc_front.h"  // the lane bodies of stages A1 / A2 (stage_a_scalars below), quat_to_R, struct FrontScalars
 #include "hmpc_schur_tiles.h"  // the deal of the tiles to the waves (mfs_owner, MfsTiles); index arithmetic of the Schur tiles
 #include "hmpc_matvec_index.h"  // lane constants and coefficients of gather_w
 
@@ -245,28 +246,6 @@ __device__ __forceinline__ double wave_min(double v) {
   return dmin(dmin(r0, r1), dmin(r2, r3));
 }
 
-// body rotation from the quaternion (RobotState.cpp:17-30; Eigen toRotationMatrix closed form) and its transpose
-__device__ inline void quat_to_R(const float *q, float *R, float *Rt) {
-  const float qw = q[0], qx = q[1], qy = q[2], qz = q[3];
-  float tx = 2.0f * qx, ty = 2.0f * qy, tz = 2.0f * qz;
-  float twx = tx * qw, twy = ty * qw, twz = tz * qw;
-  float txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  float tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  R[0] = 1.0f - (tyy + tzz);
-  R[1] = txy - twz;
-  R[2] = txz + twy;
-  R[3] = txy + twz;
-  R[4] = 1.0f - (txx + tzz);
-  R[5] = tyz - twx;
-  R[6] = txz - twy;
-  R[7] = tyz + twx;
-  R[8] = 1.0f - (txx + tyy);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Rt[k * 3 + i] = R[i * 3 + k];
-}
-
 }  // namespace hmpc
 // Tuning constants.  (Until round 6 this was a list of 29 `#ifndef HMPC_*` A/B switches; every one whose other side had been measured worse -- profiles/r02
 // ... r05 keep the numbers -- is now simply the code: FLIP4, PIN_SWEEP, CHAIN_BALANCE, MFS_PUBLISH_FIRST, S0_ACTIVE_ROWS, REFINE_FROM_X, MFS_DEAL_PAIRED,
@@ -348,6 +327,10 @@ struct VariantTraits {
   // Iteration bound 10 m + 64 instead of 4 m + 16: the safe variants may take as long as a cold qpOASES run (nWSR up to ~330 seen), so may whatever cannot hand its
   // solve on (the 60-variable first pass) -- and the wide FAST variant 8 has it since it shared the literal "QCAP >= 140" with variant 7, by accident or not
   static constexpr bool ITER_LONG = ROLE == Role::SAFE || NO_OVERFLOW || WIDE_SHAPE;
+  // READS_FRONT: takes stages A1 / A2 from KernelArgs::front where the host hands it in (front_scatter; Variant::reads_front) -- the four fast
+  // two-contact rows with one register block per thread, 60 and 120 variables at h <= 10 and h <= 20.  Both sizes, so that the small
+  // variant's share of a routed walking batch shrinks with the large one's (tests/test_gpu_tick_pipeline.py compares the two).
+  static constexpr bool READS_FRONT = !ASM_ONLY && ROLE == Role::FAST && NC == 2 && BPT == 1;
 
   // ---- stage S, M = H^-1.  Matrix-core sweeps (4 x 4 block pivots, 16 x 16 tiles read straight from the staging of H): every variant of the hand-over shape
   // but the SAFE ones.  The safe-pass variants keep the scalar sweeps: 4 x 4 block pivots apply an explicitly inverted pivot block, whose forward error carries
@@ -1179,12 +1162,62 @@ struct BlockOwner {
   }
 };
 
+// The fast two-contact variants behind front_scalars_kernel (VariantTraits::READS_FRONT, args.front != nullptr): what stages A1 and A2
+// compute is in the instance's FrontScalars block, which stage A0 brought into LDS with the record (it lies in the first words of
+// Smem::Asm::Phi, which nothing writes before stage A3), and ONE parallel pass scatters it -- with what is copied from the record, the
+// handle's constants and the constant fills -- over Acd, Bcd, Fc, Cn, x0, W, the prefix counts, n / nls / m and rmap.  Every LDS word has
+// exactly one writer: an entry is its structural constant or its value from the block, decided by its own lane (front_*_entry,
+// hmpc_front.h).  The values are the ones stage_a_scalars' lanes store (the same functions of hmpc_front.h computed them), entry for entry.
+template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT>
+__device__ __forceinline__ void front_scatter(Smem<NMAX, HMAX, NT, QCAP, NC, BPT> &S, const KernelArgs &args, const int inst, const int h) {
+  using SM = Smem<NMAX, HMAX, NT, QCAP, NC, BPT>;
+  using RL = RecLayout<NC>;
+  static_assert(NC == 2 && HMAX <= FRONT_STEPS && FRONT_WORDS <= HMAX * SM::PS, "two contacts; the block is staged in Phi");
+  constexpr int U = SM::U, PS = SM::PS, C8 = 8 * NC;
+  auto &A = S.u.a;
+  const int tid = threadIdx.x;
+  const FrontScalars &F = *reinterpret_cast<const FrontScalars *>(A.Phi);
+  const float *rf = reinterpret_cast<const float *>(A.rec);
+  const float dt = args.dt;
+  const float mu = args.mu_inst ? args.mu_inst[inst] : args.mu;  // 2.0 in the reference (SolverMPC.cpp:488); per instance for terrain sweeps
+  // (every lane reads for all the arrays first, at indices clamped into them, and stores what is its own: the reads are in flight together)
+  constexpr int NPASS = (C8 * U + NT - 1) / NT;  // Fc is the longest array
+  static_assert(C8 * U >= 169 && C8 * U >= PS, "one pass structure for Acd, Bcd, Fc");
+#pragma unroll
+  for (int u = 0; u < NPASS; ++u) {
+    const int t = tid + u * NT;
+    const int ta = t < 169 ? t : 168, tb = t < PS ? t : PS - 1, tf = t < C8 * U ? t : C8 * U - 1, tn = t < NC * 8 * 6 ? t : 0, tx = t < 13 ? t : 12;
+    const float va = front_acd_entry(F, ta, dt);
+    const float vb = front_bcd_entry(F, tb, dt, args.inv_mass);
+    const float vf = front_fc_entry(F, tf / U, tf % U, mu);
+    // per-leg 8x6 constraint normals in binary64 (columns: F then M of this leg)
+    const int leg = tn / 48, rr = (tn / 6) % 8, k = tn % 6;
+    const float vn = front_fc_entry(F, 8 * leg + rr, (k < 3) ? 3 * leg + k : 3 * NC + 3 * leg + k - 3, mu);
+    const float vx = front_x0_entry(F, rf, tx, args.gravity);
+    const float vw = rf[RL::WT + (tx < 12 ? tx : 0)];
+    if (t < 169) A.Acd[t] = va;
+    if (t < PS) A.Bcd[t] = vb;
+    if (t < C8 * U) A.Fc[t] = vf;
+    if (t < NC * 8 * 6) S.Cn[leg][rr][k] = (double)vn;
+    if (t < 13) A.x0[t] = vx, A.W[t] = (t < 12) ? vw : 0.0f;
+  }
+  for (int t = tid; t < h; t += NT) A.pre_nl[t] = F.pre_nl[t], A.pre_nv[t] = F.pre_nv[t], A.pre_st[t] = F.pre_st[t];
+  for (int t = tid; t < U * h; t += NT) S.rmap[t] = 255;
+  if (tid == 0) {
+    const int nl = F.nls;
+    S.n = F.n, S.nls = nl, S.m = 8 * nl;
+    S.relax = args.relax, S.pad0 = 0;  // (pad0: "a row keeps being re-added", the anti-cycling variants' flag)
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Stage A1 + A2 of the kernel as a function.  In: the instance's packed record in S.u.a.rec (stage A0), the robot constants in
 // args.  Out, in LDS: the trigonometric tables, x0, Acd, Bcd, the weights W and the per-step constraint block Fc (Smem::Asm);
 // the per-contact constraint normals Cn, the stance prefix counts and every index table of the swing elimination, ub7 / sc7, n, m,
-// nls (Smem's persistent part); the identity power Apow[0].  Ends with a barrier.
-template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT>
+// nls (Smem's persistent part); the identity power Apow[0].  Ends with a barrier.  The lane bodies are the functions of hmpc_front.h.
+// FRONT (VariantTraits::READS_FRONT) and args.front != nullptr: A1 and A2 were run by front_scalars_kernel; front_scatter above takes
+// their place (the trigonometric tables are then not written: nothing behind the stage reads them in a solve kernel).
+template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT, bool FRONT = false>
 __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, BPT> &S, const KernelArgs &args, const int inst, const int h, Prof &prof) {
   using SM = Smem<NMAX, HMAX, NT, QCAP, NC, BPT>;
   using RL = RecLayout<NC>;
@@ -1198,23 +1231,20 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
               *in_ja = rf + RL::JA, *in_wt = rf + RL::WT;
   // Fz cap of a contact: f_max for the feet; the hand's own cap travels in the extension record
   auto fz_cap = [&](int c) __attribute__((always_inline)) -> float { return (NC == 3 && c == 2) ? rf[RL::FMH] : args.f_max; };
+  bool from_front = false;
+  if constexpr (FRONT) from_front = args.front != nullptr;  // uniform
+  if (from_front) {
+    if constexpr (FRONT) front_scatter<NMAX, HMAX, NT, QCAP, NC, BPT>(S, args, inst, h);
+    __syncthreads();
+    PROF_MARK(P_A1);
+  } else {
   // ---------------- A1: trigonometry, one lane per angle (SolverMPC.cpp:374-393, 333-342, 74-85); a lane of another
   // wave builds the swing-leg elimination tables meanwhile (SolverMPC.cpp:589-637)
   {
-    const double PI = 3.14159265359, PI2 = 2 * PI;
     constexpr int L_ROLL = (NT >= 256) ? 65 : 65, L_PITCH = (NT >= 256) ? 128 : 66, L_YAW = (NT >= 256) ? 192 : 12;
-    auto joint = [&](int i) __attribute__((always_inline)) -> float {
-      float a = in_ja[i];
-      const int k = i % 5;
-      if (k == 2 || k == 4) a = (float)((double)a + 0.3 * PI);
-      if (k == 3) a = (float)((double)a - 0.6 * PI);
-      const double ad = (double)a;
-      return (float)((__builtin_fabs(ad) < PI2) ? ad : fmod(ad, PI2));  // fmod(x,y) == x exactly when |x| < y
-    };
     if (tid < 12) {
       // lanes 0..9: the joint angles; lanes 10, 11: q2+q3+q4 of each leg -- one sincos evaluation for all twelve
-      const int b = 5 * (tid - 10);
-      const float ang = (tid < 10) ? joint(tid) : (joint(b + 2) + joint(b + 3)) + joint(b + 4);
+      const float ang = front_trig_angle(in_ja, tid);
       double s, c;
       det_sincos((double)ang, s, c);
       float *dst = (tid < 10) ? A.sc[tid] : A.sc234[tid - 10];
@@ -1223,26 +1253,17 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
     } else if (tid == L_ROLL || tid == L_PITCH || tid == L_YAW) {
       // the three Euler angles are the longest scalar chains of the stage (two binary64 divisions, a square root and a
       // sincos each): one lane each in different waves, so that they run side by side instead of one after the other
-      const float qw = in_q[0], qx = in_q[1], qy = in_q[2], qz = in_q[3];
       if (tid == L_ROLL) {
-        float n0 = 2.0f * (qw * qx + qy * qz);
-        double d0 = 1.0 - (double)(2.0f * (qx * qx + qy * qy));
-        A.rpy[0] = (float)det_atan2((double)n0, d0);
+        A.rpy[0] = front_euler_angle<0>(in_q);
       } else if (tid == L_PITCH) {
-        float t = qw * qy - qx * qz;
-        double asd = 2.0 * (double)t;
-        if (!(asd < 0.99999)) asd = 0.99999;
-        float as = (float)asd;
-        float pitch = (float)det_asin((double)as);
+        const float pitch = front_euler_angle<1>(in_q);
         A.rpy[1] = pitch;
         double s, c;
         det_sincos((double)pitch, s, c);
         A.ypsc[2] = (float)c;
         A.ypsc[3] = (float)s;
       } else {
-        float n2 = 2.0f * (qw * qz + qx * qy);
-        double d2 = 1.0 - (double)(2.0f * (qy * qy + qz * qz));
-        float yaw = (float)det_atan2((double)n2, d2);
+        const float yaw = front_euler_angle<2>(in_q);
         A.rpy[2] = yaw;
         double s, c;
         det_sincos((double)yaw, s, c);
@@ -1252,21 +1273,8 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
     } else if (tid == 64) {
       // a leg-step survives iff its Fz bound f_max*gait is not ~0 (SolverMPC.cpp:589-637): per-step prefix counts here,
       // the index tables are filled in parallel in the next stage
-      int nv = 0, nl = 0;
-      for (int i = 0; i < h; ++i) {
-        int bits = 0, nst = 0;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const bool st = stance(fz_cap(c), gait[NC * i + c]);
-          bits |= st ? (1 << c) : 0;
-          nst += (int)st;
-        }
-        A.pre_nl[i] = (unsigned char)(nl > 255 ? 255 : nl);
-        A.pre_nv[i] = (unsigned char)(nv > 255 ? 255 : nv);
-        A.pre_st[i] = (unsigned char)bits;
-        nv += 6 * nst;
-        nl += nst;
-      }
+      int nv, nl;
+      front_prefix<NC>(gait, h, fz_cap, A.pre_nl, A.pre_nv, A.pre_st, nv, nl);
       S.n = nv;
       S.nls = nl;
       S.m = 8 * nl;
@@ -1284,14 +1292,8 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
   // ---------------- A2: scalar algebra (RobotState.cpp:17-47, SolverMPC.cpp:65-89,302-331,420-433,488-548): body on a
   // lane of wave 0, one foot per lane of two other waves (different waves, so the three run concurrently)
   if (tid == 0) {
-    float R[9], Rt[9];
-    quat_to_R(in_q, R, Rt);
-    float Rbi[9];
-    {
-      const float cy = A.ypsc[0], sy = A.ypsc[1], cp = A.ypsc[2], sp = A.ypsc[3];
-      float Rb[9] = {cy * cp, -sy, 0.0f, sy * cp, cy, 0.0f, -sp, 0.0f, 1.0f};
-      inverse3(Rb, Rbi);
-    }
+    float Rbi_dt[9], Iinv_dt[9], blk_dt[NC][9];
+    front_body<NC>(in_q, A.ypsc, in_r, args.Ib, args.dt, Rbi_dt, Iinv_dt, blk_dt);
     for (int i = 0; i < 3; ++i) {
       A.x0[i] = A.rpy[i];
       A.x0[3 + i] = in_p[i];
@@ -1299,31 +1301,18 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
       A.x0[9 + i] = in_v[i];
     }
     A.x0[12] = args.gravity;                                     // 9.81f in the reference (SolverMPC.cpp:420)
-    const float Ib[3] = {args.Ib[0], args.Ib[1], args.Ib[2]};  // 0.5413, 0.5200, 0.0691 (RobotState.cpp:45)
-    float RI[9], Iw[9], Iinv[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) RI[i * 3 + k] = R[i * 3 + k] * Ib[k];
-    chain_mm<3, 3, 3>(RI, Rt, Iw);
-    inverse3(Iw, Iinv);
-
     // continuous model -> forward Euler (SolverMPC.cpp:312-331, 145-146); mass: hmpc_params (9.0 at :423)
     const float dt = args.dt;
     for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) A.Acd[i * 13 + 6 + j] = 0.0f + dt * Rbi[i * 3 + j];
+      for (int j = 0; j < 3; ++j) A.Acd[i * 13 + 6 + j] = Rbi_dt[i * 3 + j];
     for (int i = 0; i < 3; ++i) A.Acd[(3 + i) * 13 + 9 + i] = 0.0f + dt * 1.0f;
     A.Acd[11 * 13 + 12] = 0.0f + dt * -1.0f;
     const float inv_m = args.inv_mass;  // fl(1.0f / mass), mass = 9.0 in the reference (SolverMPC.cpp:423)
     for (int leg = 0; leg < NC; ++leg) {
-      const float r0 = in_r[0 * NC + leg], r1 = in_r[1 * NC + leg], r2 = in_r[2 * NC + leg];
-      float cm[9] = {0.0f, -r2, r1, r2, 0.0f, -r0, -r1, r0, 0.0f};
-      float blk[9];
-      chain_mm<3, 3, 3>(Iinv, cm, blk);
       for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
-          A.Bcd[(6 + i) * U + 3 * leg + j] = dt * blk[i * 3 + j];
-          A.Bcd[(6 + i) * U + 3 * NC + 3 * leg + j] = dt * Iinv[i * 3 + j];
+          A.Bcd[(6 + i) * U + 3 * leg + j] = blk_dt[leg][i * 3 + j];
+          A.Bcd[(6 + i) * U + 3 * NC + 3 * leg + j] = Iinv_dt[i * 3 + j];
         }
       for (int i = 0; i < 3; ++i) A.Bcd[(9 + i) * U + 3 * leg + i] = dt * inv_m;
     }
@@ -1336,51 +1325,9 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
     const int leg_lane0 = (NT >= 256) ? 128 : 64, leg_lane1 = (NT >= 256) ? 192 : 65, leg_lane2 = (NC == 3) ? (NT >= 512 ? 256 : 96) : -1;
     if (tid == leg_lane0 || tid == leg_lane1 || tid == leg_lane2) {
       const int leg = (tid == leg_lane0) ? 0 : (tid == leg_lane1 ? 1 : 2);
-      float R[9], Rt[9];
-      quat_to_R(in_q, R, Rt);
       const float mu = args.mu_inst ? args.mu_inst[inst] : args.mu;  // 2.0 in the reference (SolverMPC.cpp:488); per instance for terrain sweeps
-      const float lt = args.lt, lh = args.lh;                         // 0.09, 0.06 (SolverMPC.cpp:489-490)
-      const int b = (leg < 2) ? 5 * leg : 0;
-      const float s0 = A.sc[b][0], c0 = A.sc[b][1], s1 = A.sc[b + 1][0], c1 = A.sc[b + 1][1];
-      const float s2 = A.sc[b + 2][0], c2 = A.sc[b + 2][1], s3 = A.sc[b + 3][0], c3 = A.sc[b + 3][1];
-      const float s4 = A.sc[b + 4][0], c4 = A.sc[b + 4][1];
-      const float s234 = A.sc234[leg & 1][0], c234 = A.sc234[leg & 1][1];
-      // every operation in the type C++ gives it at SolverMPC.cpp:428-433: the "1.0" / "-1.0" literals promote the
-      // product they start, and whatever that product is combined with, to binary64; one narrowing per entry
-      const float a = c0 * s2 + (c2 * s0) * s1;
-      const double bb = (double)(c0 * c2) - (((double)s0 * (double)s1) * (double)s2);
-      const float d = c2 * s0 + (c0 * s1) * s2;
-      const double e = (double)(s0 * s2) - (((double)c0 * (double)c2) * (double)s1);
-      const double X = (double)(c3 * a) + (double)s3 * bb;
-      const double Y = ((double)s3 * (double)a) - (double)c3 * bb;
-      const double P = (double)(c3 * d) - ((double)s3) * e;
-      const double Q = (double)(s3 * d) + (double)c3 * e;
-      float Rf[9];
-      Rf[0] = (float)((-(double)s4) * X - (double)c4 * Y);
-      Rf[1] = -(c1 * s0);
-      Rf[2] = (float)((double)c4 * X - (double)s4 * Y);
-      Rf[3] = (float)((double)c4 * P - (double)s4 * Q);
-      Rf[4] = c0 * c1;
-      Rf[5] = (float)((double)c4 * Q + (double)s4 * P);
-      Rf[6] = -(s234 * c1);
-      Rf[7] = s1;
-      Rf[8] = c234 * c1;
-      if (NC == 3 && leg == 2) {  // the hand's contact frame is an input of the extension record
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rf[k] = rf[RL::RH + k];
-      }
-      float col0[3], col1[3], vlt[3], vlh[3], t0[3], t1[3], flt[3], flh[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        col0[k] = Rf[k * 3 + 0];
-        col1[k] = Rf[k * 3 + 1];
-        vlt[k] = -lt * Rf[k * 3 + 2];
-        vlh[k] = -lh * Rf[k * 3 + 2];
-      }
-      chain_mm<1, 3, 3>(col0, Rt, t0);
-      chain_mm<1, 3, 3>(col1, Rt, t1);
-      chain_mm<1, 3, 3>(vlt, Rt, flt);
-      chain_mm<1, 3, 3>(vlh, Rt, flh);
+      float t0[3], t1[3], flt[3], flh[3];
+      front_foot<NC>(in_q, A.sc, A.sc234, leg, args.lt, args.lh /* 0.09, 0.06 (SolverMPC.cpp:489-490) */, rf + RL::RH, t0, t1, flt, flh);
       float *row = A.Fc + (8 * leg) * U;
       const int cf = 3 * leg, cmo = 3 * NC + 3 * leg;
       row[0 * U + cf + 0] = -mu, row[0 * U + cf + 2] = 1.0f;
@@ -1403,6 +1350,7 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
         }
     }
   }
+  }  // !from_front
   if (args.ext_Fc) {  // uniform.  Parity hook: the constraint block comes from outside (after the lanes above have written theirs)
     __syncthreads();
     const float *xf = args.ext_Fc + (size_t)inst * C8 * U;
@@ -1984,7 +1932,19 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
   {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(args.records + (size_t)inst * args.stride);
     const int nwords = args.stride >> 2;
+    // the instance's block of front_scalars_kernel rides with the record: its load is issued first and stored behind the record's, so that
+    // the two are in flight together (front_scatter reads the block from Phi)
+    uint32_t fw = 0;
+    bool ff = false;
+    if constexpr (VT::READS_FRONT) {
+      static_assert(FRONT_WORDS <= NT, "one word of the block per lane");
+      ff = args.front != nullptr && tid < FRONT_WORDS;
+      if (ff) fw = reinterpret_cast<const uint32_t *>(args.front + inst)[tid];
+    }
     for (int t = tid; t < nwords; t += NT) A.rec[t] = src[t];
+    if constexpr (VT::READS_FRONT) {
+      if (ff) reinterpret_cast<uint32_t *>(A.Phi)[tid] = fw;
+    }
   }
   if constexpr (VT::SWEEP) {
     if (sweep_given) {
@@ -2018,7 +1978,7 @@ __global__ __launch_bounds__(NT, (VariantTraits<NMAX, HMAX, NT, QCAP, NC, BPT, R
   auto fz_cap = [&](int c) __attribute__((always_inline)) -> float { return (NC == 3 && c == 2) ? rf[RL::FMH] : args.f_max; };
 
   // ---------------- A1 + A2: trigonometry, scalar algebra, constraint block, elimination tables (stage_a_scalars above)
-  stage_a_scalars<NMAX, HMAX, NT, QCAP, NC, BPT>(S, args, inst, h, prof);
+  stage_a_scalars<NMAX, HMAX, NT, QCAP, NC, BPT, VT::READS_FRONT>(S, args, inst, h, prof);
   PROF_MARK(P_A2);
 
   const int n = uni(S.n), m = uni(S.m), ng = uni(S.nls);

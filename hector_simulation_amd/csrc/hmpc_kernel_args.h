@@ -16,6 +16,8 @@ namespace hmpc {
 // still flagged; SWEEP: command sweeps (a workgroup per chunk of instances sharing state and gait)
 enum class Role { FAST, CONT, SAFE, SWEEP };
 
+struct FrontScalars;  // hmpc_front.h
+
 struct KernelArgs {
   const unsigned char *records;
   int stride, batch, horizon;
@@ -117,6 +119,11 @@ struct KernelArgs {
   unsigned int *reg_count;
   int reg_cap;
   double *reg_rho;  // [batch]: the pivot (after reg_step 0), then rho; set for every launch over an index list
+  // Stages A1 / A2 done ahead of the launch (front_scalars_kernel, hmpc_front.hip): front[inst] holds what they compute of instance inst's
+  // record, written on this launch's stream inside the same enqueue.  Read by the fast two-contact variants (VariantTraits::READS_FRONT)
+  // only; nullptr = every variant runs the two stages itself (the safe and continuation passes, list launches, command sweeps, the
+  // external QP, three contacts, the wide variant, the assembly-only dump, every derived kernel).
+  const FrontScalars *front;
 };
 constexpr int NPROF = 32;
 enum : int { P_ASM = 0, P_HG, P_SWEEP, P_XU, P_SEL, P_D, P_ED, P_W, P_MV, P_T1, P_UPD, P_POLISH, P_FINAL, P_TOTAL, P_BLOCK, P_B_S0, P_B_INV, P_B_DROP, P_SEL_A, P_A0, P_A1, P_A2, P_G };

@@ -3,10 +3,13 @@
 // hmpc_resolve_failed.  The decisions themselves (which variant, which classes, what is repaired) are hmpc_plan.h's.
 #include <hip/hip_runtime.h>
 
+#include <string.h>
+
 #include <string>
 #include <vector>
 
 #include "hmpc_builder_launch.h"
+#include "hmpc_front.h"
 #include "hmpc_handle.h"
 #include "hmpc_variants.h"
 
@@ -133,6 +136,9 @@ int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
   if (o.list_indefinite && h->d_flag_list.get() && h->d_flag_count.get())
     a.reg_list = h->d_flag_list.get() + flag_list_cap(h->max_batch), a.reg_count = h->d_flag_count.get() + 1, a.reg_cap = REG_LIST_CAP;
   a.sweep_k = o.sweep_k > 0 ? o.sweep_k : 1, a.sweep_phase = o.sweep_phase, a.sweep_m = h->d_sweep_m.get();
+  // (never derived from "the buffer exists": only the caller that has just enqueued the prologue on this stream says so)
+  a.front = (o.front_ready && v.reads_front && !o.assemble_only && !o.d_index_list && o.sweep_k == 0 && !h->d_ext_H)
+                ? reinterpret_cast<const hmpc::FrontScalars *>(h->d_front.get()) : nullptr;
   set_problem_args(h, a);
   for (int off = 0; off < grid_all; off += chunk) {
     const int grid = (grid_all - off < chunk) ? grid_all - off : chunk;
@@ -140,6 +146,24 @@ int launch(hmpc_handle *h, hipStream_t stream, int vi, const LaunchOpt &o) {
     hipLaunchKernelGGL(fn, dim3(grid), dim3(v.nt), v.smem, stream, a);
     HIP_TRY(hipGetLastError());
   }
+  return HMPC_OK;
+}
+
+// Stages A1 / A2 of every instance of the batch in one launch ahead of the fast pass (front_scalars_kernel): a third small launch on the
+// solve's stream next to the dispatch order's.  Two contacts only; not for the external QP, whose constraint block comes from outside.
+int enqueue_front(hmpc_handle *h, hipStream_t stream, const int *vis, int n, bool *ready) {
+  *ready = false;
+  if (!h->front_prologue || h->nc != 2 || h->d_ext_H || h->batch < 1) return HMPC_OK;
+  bool reads = false;
+  for (int k = 0; k < n; ++k) reads = reads || variants()[vis[k]].reads_front;
+  if (!reads) return HMPC_OK;
+  RC_TRY(grow(h, h->d_front, (size_t)h->max_batch * sizeof(hmpc::FrontScalars)));
+  hmpc::KernelArgs ka;
+  memset(&ka, 0, sizeof(ka));
+  set_problem_args(h, ka);  // (the very values the solve kernels assemble from)
+  const hmpc::FrontArgs fa = {ka.records, ka.stride, ka.batch, ka.horizon, ka.dt, ka.f_max, {ka.Ib[0], ka.Ib[1], ka.Ib[2]}, ka.lt, ka.lh};
+  HIP_TRY(hmpc::launch_front_scalars(fa, reinterpret_cast<hmpc::FrontScalars *>(h->d_front.get()), stream));
+  *ready = true;
   return HMPC_OK;
 }
 
@@ -163,6 +187,12 @@ int enqueue_fast(hmpc_handle *h, hipStream_t stream, int vi, bool classes, Launc
     HIP_TRY(hipMemsetAsync(h->d_spill_slot.get(), 0xff, (size_t)h->batch * sizeof(int), stream));
   if (classes && !h->cls_valid)
     HIP_TRY(hmpc::launch_classify_records(h->d_records, (int)h->stride, h->batch, h->setup.horizon, h->setup.f_max, h->d_cls.get(), stream));
+  o.front_ready = false;
+  if (!sweep) {  // (the SWEEP variants run the two stages themselves)
+    int vis[SIZE_CLASSES];
+    for (int k = 0; k < n; ++k) vis[k] = l[k].vi;
+    RC_TRY(enqueue_front(h, stream, vis, n, &o.front_ready));
+  }
   const bool record_flagged = o.record_flagged;
   for (int k = 0; k < n; ++k) {
     o.cls_lo = l[k].lo, o.cls_hi = l[k].hi;

@@ -25,6 +25,7 @@ struct Variant {
   size_t smem;
   int dbg_floats;
   size_t spill_stride;  // bytes of one hand-over slot (KernelArgs::spill) when this variant SAVES its state (FAST on the hand-over shape), 0 otherwise
+  bool reads_front;     // takes stages A1 / A2 from KernelArgs::front where it is handed in (VariantTraits::READS_FRONT)
 };
 
 // index = position in hmpc_launch.hip's variants(); (NMAX, HMAX, NT, QCAP, NC, BPT, ROLE), group = translation unit that builds it.

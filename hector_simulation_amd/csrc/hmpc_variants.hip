@@ -18,7 +18,7 @@ Variant make_variant() {
   kernel_fn assemble = nullptr;  // (the assembly-only debug kernel: hmpc_debug_assemble launches the fast variant's)
   if constexpr (ROLE == Role::FAST) assemble = hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, true, NC, BPT, ROLE>;
   return Variant{NMAX, HMAX, NT, QCAP, NC, ROLE, VT::EGLOBAL, hmpc::hmpc_kernel<NMAX, HMAX, NT, QCAP, false, NC, BPT, ROLE>, assemble,
-                 sizeof(typename VT::SM), hmpc::DbgLayout<NMAX, NC>::TOTAL, VT::SPILL_STRIDE};
+                 sizeof(typename VT::SM), hmpc::DbgLayout<NMAX, NC>::TOTAL, VT::SPILL_STRIDE, VT::READS_FRONT};
 }
 }  // namespace
 

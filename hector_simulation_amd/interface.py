@@ -732,6 +732,20 @@ class BatchedMPC:
         _check(self.L.hmpc_debug_handover_slots(self.h, out.ctypes.data), "hmpc_debug_handover_slots")
         return out
 
+    # one block of hmpc_debug_front_scalars (include/hector_mpc.h; csrc/hmpc_front.h struct FrontScalars), 320 bytes
+    FRONT_DTYPE = np.dtype([("rpy", "<f4", 3), ("dt_Rbi", "<f4", 9), ("dt_Iinv", "<f4", 9), ("dt_blk", "<f4", (2, 9)), ("foot", "<f4", (2, 12)),
+                            ("pad0", "<f4"), ("pre_nl", "u1", 20), ("pre_nv", "u1", 20), ("pre_st", "u1", 20), ("n", "<u2"), ("nls", "<u2")])
+
+    def debug_set_front_prologue(self, on: bool) -> None:
+        """A/B switch (hmpc_debug_set_front_prologue, default on): the batched launch of the assembly's scalar front ahead of the fast pass."""
+        _check(self.L.hmpc_debug_set_front_prologue(self.h, int(bool(on))), "hmpc_debug_set_front_prologue")
+
+    def debug_front_scalars(self) -> np.ndarray:
+        """Test hook (hmpc_debug_front_scalars): that launch's blocks of the current two-contact batch, a structured array [batch]."""
+        out = np.zeros(self.batch, dtype=self.FRONT_DTYPE)
+        _check(self.L.hmpc_debug_front_scalars(self.h, out.ctypes.data), "hmpc_debug_front_scalars")
+        return out
+
     def solve_external_qp(self, H: np.ndarray, g: np.ndarray, Fc: np.ndarray) -> None:
         """Parity hook (hmpc_debug_solve_external_qp): solver stages on caller-supplied QP data; H [batch, ld, ld] and
         g [batch, ld] in the reference's reduced order, Fc [batch, 8 nc, 6 nc]."""

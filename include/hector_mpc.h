@@ -1362,6 +1362,16 @@ int hmpc_download_f64(hmpc_handle *h, double *x, double *obj);
  * left instance i's working set for the continuation pass (its status word HMPC_S_WORKSET) and no pass has consumed it yet,
  * -1 everywhere else.  Never an entry of an earlier solve or batch. */
 int hmpc_debug_handover_slots(hmpc_handle *h, int *slots);
+/* A/B switch (default on): a solve of a two-contact batch enqueues one small launch ahead of its fast pass that computes the serial
+ * scalar front of every instance's assembly -- joint and Euler trigonometry, body algebra, foot rotations, stance prefix counts -- for
+ * the whole batch (csrc/hmpc_front.hip), and the fast kernels read the result.  Off: every kernel computes it itself, as the safe and
+ * continuation passes, command sweeps, three-contact batches and the derived results always do.  The results are the same bits. */
+int hmpc_debug_set_front_prologue(hmpc_handle *h, int on);
+/* Test hook: runs that launch on the current batch (two contacts) and copies its blocks to the host, out[batch][320 bytes]; per block:
+ * float rpy[3], dt_Rbi[9] (0 + dt Rbi), dt_Iinv[9], dt_blk[2][9] (dt Iinv [r_leg]x), foot[2][12] (per leg t0, t1, flt, flh: the vectors
+ * the leg's rows of the constraint block are made of), one float of padding; unsigned char pre_nl[20], pre_nv[20], pre_st[20] (per
+ * horizon step: stance leg-steps and reduced variables before it, stance bits; zero beyond the horizon); unsigned short n, nls. */
+int hmpc_debug_front_scalars(hmpc_handle *h, void *out);
 
 /* Developer hook (only in builds with -DHMPC_PROFILE, scripts/phase_profile.py): per-phase shader-clock cycles of
  * one more launch of the current batch, [batch][32] (phase ids: hmpc_kernel.h P_*). */

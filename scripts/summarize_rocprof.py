@@ -40,6 +40,15 @@ def main():
         for c, v in sorted(acc.items()):
             rows.append((pas, c, len(v), sum(v) / len(v)))
             means[c] = sum(v) / len(v)
+        # the prologue ahead of the fast solve (csrc/hmpc_front.hip), its own rows: "front:<counter>"
+        accf = defaultdict(list)
+        with open(f) as fh:
+            for r in csv.DictReader(fh):
+                if "front_scalars_kernel" in r["Kernel_Name"] and int(r["Grid_Size"]) >= 8192 * 16:
+                    accf[r["Counter_Name"]].append(float(r["Counter_Value"]))
+        for c, v in sorted(accf.items()):
+            rows.append((pas, "front:" + c, len(v), sum(v) / len(v)))
+            means["front:" + c] = sum(v) / len(v)
     with open(os.path.join(dst, "pmc.csv"), "w") as fh:
         fh.write("pass,counter,dispatches,mean_per_dispatch\n")
         for r in rows:
@@ -180,7 +189,7 @@ def variant_lines(dst):
 def write_readme(dst, rnd, means, extra=()):
     """profiles/<round>/README.md generated from the CSV/JSON files next to it -- no hand-typed figures."""
     lines = ["# profiles/%s -- generated by scripts/summarize_rocprof.py from the files in this directory" % rnd, "",
-             "Collected with `scripts/gpu_rocprof.sh` (one `gpurun` call; rocprofv3 passes kept separate: kernel trace + "
+             "Collected with `scripts/gpu_rocprof.sh` (one GPU visit; rocprofv3 passes kept separate: kernel trace + "
              "stats, then one `--pmc` pass per counter group).  Command profiled: `python bench.py --full --steps 10 --warmup 2 "
              "--no-cpu-baseline --no-side-configs --check 0 --streams 1` (serial launches on one stream, so that per-kernel durations are not stretched by the overlap of the default two-stream mode; 8192 randomized 2-contact h=10 instances per launch, records "
              "resident in HBM).", ""]
@@ -191,6 +200,19 @@ def write_readme(dst, rnd, means, extra=()):
                 avg_ms = float(r["AverageNs"]) / 1e6
                 lines.append("* `kernel_stats.csv`: `%s` -- %s calls, average **%.4f ms** per 8192-instance launch = %.3f M "
                              "solves/s (kernel only)" % (r["Name"].rsplit("(", 1)[0], r["Calls"], avg_ms, 8192 / avg_ms / 1e3))
+    # the prologue's row beside the solve kernel's, and what a solve costs on its stream: their sum
+    with open(ks) as fh:
+        st = list(csv.DictReader(fh))
+    front = [r for r in st if "front_scalars_kernel" in r["Name"]]
+    solve = [r for r in st if "hmpc_kernel" in r["Name"]]
+    if front and solve:
+        f_ms = float(front[0]["AverageNs"]) / 1e6
+        s_ms = float(max(solve, key=lambda r: int(r["Calls"]))["AverageNs"]) / 1e6
+        lines.append("* `kernel_stats.csv`: `%s` -- %s calls, average **%.4f ms** per launch; prologue + solve kernel = **%.4f ms** per solve "
+                     "= %.3f M solves/s" % (front[0]["Name"].rsplit("(", 1)[0], front[0]["Calls"], f_ms, f_ms + s_ms, 8192 / (f_ms + s_ms) / 1e3))
+    if "front:FETCH_SIZE" in means and "front:WRITE_SIZE" in means:
+        lines.append("* `pmc.csv`: the prologue moves FETCH_SIZE %.0f KB + WRITE_SIZE %.0f KB per launch (as reported)"
+                     % (means["front:FETCH_SIZE"], means["front:WRITE_SIZE"]))
     bj = os.path.join(dst, "bench_standing.json")
     if os.path.exists(bj):
         try:
