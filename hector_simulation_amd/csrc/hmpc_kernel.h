@@ -43,6 +43,7 @@
 
 #include "hmpc_kernel_args.h"
 #include "hmpc_record.h"  // RecLayout (RL:: below), stance()
+#include "hmpc_chains.h"  // the chains of stages A3 / A4 over the compact table of the powers (stage_a_chains below)
 #include "hmpc_front.h"  // the lane bodies of stages A1 / A2 (stage_a_scalars below), quat_to_R, struct FrontScalars
 #include "hmpc_schur_tiles.h"  // the deal of the tiles to the waves (mfs_owner, MfsTiles); index arithmetic of the Schur tiles
 #include "hmpc_matvec_index.h"  // lane constants and coefficients of gather_w
@@ -139,7 +140,7 @@ struct Smem {
     float rpy[3];
     float ypsc[4];  // cy, sy, cp, sp
     float Acd[169], Bcd[PS], x0[13], W[13], Fc[8 * NC * U];
-    float Apow[2 * 169];
+    float Pw[(HMAX + 1) * CH_SLOTS];  // Acd^k, k <= HMAX, as the compact table of hmpc_chains.h (live entries, 1.0f, +0.0f)
     float Phi[HMAX * PS];  // Phi_k = Acd^k Bcd; S Phi_k = fl(w_s Phi_k) is formed where it is consumed (one multiply)
     float e[13 * HMAX];
     unsigned char pre_nl[HMAX], pre_nv[HMAX], pre_st[HMAX];  // per step: leg-steps / variables before it, stance bits
@@ -1214,7 +1215,7 @@ __device__ __forceinline__ void front_scatter(Smem<NMAX, HMAX, NT, QCAP, NC, BPT
 // Stage A1 + A2 of the kernel as a function.  In: the instance's packed record in S.u.a.rec (stage A0), the robot constants in
 // args.  Out, in LDS: the trigonometric tables, x0, Acd, Bcd, the weights W and the per-step constraint block Fc (Smem::Asm);
 // the per-contact constraint normals Cn, the stance prefix counts and every index table of the swing elimination, ub7 / sc7, n, m,
-// nls (Smem's persistent part); the identity power Apow[0].  Ends with a barrier.  The lane bodies are the functions of hmpc_front.h.
+// nls (Smem's persistent part); the identity power Pw[0].  Ends with a barrier.  The lane bodies are the functions of hmpc_front.h.
 // FRONT (VariantTraits::READS_FRONT) and args.front != nullptr: A1 and A2 were run by front_scalars_kernel; front_scatter above takes
 // their place (the trigonometric tables are then not written: nothing behind the stage reads them in a solve kernel).
 template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT, bool FRONT = false>
@@ -1393,12 +1394,12 @@ __device__ __forceinline__ void stage_a_scalars(Smem<NMAX, HMAX, NT, QCAP, NC, B
     }
   }
   // identity power
-  for (int t = tid; t < 169; t += NT) A.Apow[t] = (t % 14 == 0) ? 1.0f : 0.0f;
+  if (tid < CH_SLOTS) A.Pw[tid] = chains_identity_slot(tid);
   __syncthreads();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Stages A3 / A4 and the gradient as a function.  In (LDS, Smem::Asm): Acd, Bcd, x0, W, the identity in Apow[0], the record's
+// Stages A3 / A4 and the gradient as a function.  In (LDS, Smem::Asm): Acd, Bcd, x0, W, the identity in Pw[0], the record's
 // trajectory; the reference-order index tables vstep / vcomp / o2s.  Out: Phi_k = Acd^k Bcd for k < h, the tracking error e
 // (Smem::Asm) and g in sweep order (Smem::g, binary64 copy of the binary32 value).  n = reduced variables of the instance.
 template <int NMAX, int HMAX, int NT, int QCAP, int NC, int BPT>
@@ -1410,73 +1411,75 @@ __device__ __forceinline__ void stage_a_chains(Smem<NMAX, HMAX, NT, QCAP, NC, BP
   const int tid = threadIdx.x;
   (void)prof;
   const float *in_traj = reinterpret_cast<const float *>(A.rec) + RL::NF;
-  // ---------------- A3/A4: Acd^k by repeated right-multiplication from the identity (SolverMPC.cpp:148-158), and from each
-  // power as it appears: Phi_k = Acd^k Bcd (:161-178), SPhi = fl(w_s Phi) (B'S first, as B'*S*B evaluates left to right),
-  // tracking error e_i = Acd^(i+1) x0 - X_d (:457-461, :570).  Only two powers are kept (ping-pong).
+  // ---------------- A3/A4: Acd^k by repeated right-multiplication from the identity (SolverMPC.cpp:148-158), and from the powers:
+  // Phi_k = Acd^k Bcd (:161-178), SPhi = fl(w_s Phi) (B'S first, as B'*S*B evaluates left to right), tracking error
+  // e_i = Acd^(i+1) x0 - X_d (:457-461, :570).
   // The fmaf chains run over the structurally non-zero terms only, in ascending index order: a term whose factor is an
   // exact structural zero (fl(dt*0), the off-diagonal zeros of the identity, the zero pattern of Acd^k) adds +-0 to the
   // running sum, which leaves it bit for bit unchanged (HMPC-A1), so the result equals the dense 13-term chain.
   //   Acd  = I + dt A_ct:  column j has its diagonal 1 and  rows 0..2 (j = 6..8),  row j-6 (j = 9..11),  row 11 (j = 12);
   //   Bcd:                 column of a force component c has rows 6..8 and row 9+c, a moment column rows 6..8;
   //   Acd^k:               row s has its diagonal and  columns 6..8 (s < 3),  s+6 (s = 3, 4),  11 and 12 (s = 5),  12 (s = 11).
-  // Every lane runs the same four-term chain; a lane with fewer live terms pads with a term whose factor is a
-  // structural zero (row 12 / row 0 of Acd, row 0 of Bcd, column 0 of Acd^k), so there is no divergence.
-  // The work items (an entry of the next power, of Phi_k, of e) and their operand addresses do not depend on k: they
-  // are set up once, so that a step of the loop is 8 LDS reads, 4 fmaf and the store(s) per item.
-  constexpr int NITEM = 169 + PS + 13, NTRIP = (NITEM + NT - 1) / NT;
-  int it_p[NTRIP][4];            // offsets of the four Acd^k factors inside the 13x13 power
-  const float *it_c[NTRIP][4];   // the four right-hand factors
-  int it_kind[NTRIP], it_out[NTRIP];
+  // Every chain has four terms; one with fewer live terms pads with a term whose factor is a structural zero.  Fourteen entries
+  // of a power are not the identity's, and each depends on its own row of the power before it only: the powers are fourteen
+  // recurrences in the registers of fourteen lanes, kept as 16 floats per power (hmpc_chains.h: the chains, the slot map).
+  //   phase P: lanes 0..13 run Acd^1 .. Acd^h and store their slot of each; no LDS read and no barrier between the steps;
+  //   phase F: one lane per entry of Phi (and of e, on a wave of its own where the lanes allow it) takes it through every k; its operand
+  //            slots and its four right-hand factors do not depend on k and are set up once, ahead of phase P; the steps are
+  //            independent, so the reads of KB of them are in flight together.
+  constexpr int PSE = (PS + 63) / 64 * 64, NITEM = PSE + 13, NTRIP = (NITEM + NT - 1) / NT, KB = 5;
+  static_assert(HMAX % KB == 0, "phase F reads the powers KB at a time, up to Pw[HMAX]");
+  ChainsItem it[NTRIP];
 #pragma unroll
   for (int u = 0; u < NTRIP; ++u) {
     const int t = tid + u * NT;
-    int row, cs, m0, m1, m2, m3, kind, out;
-    const float *cf;
-    if (t < 169) {
-      const int i = t / 13, j = t % 13, pad = (j == 12) ? 0 : 12;
-      const bool w3 = j >= 6 && j < 9;
-      row = i, cf = A.Acd + j, cs = 13, kind = 0, out = t;
-      m0 = w3 ? 0 : ((j >= 9 && j < 12) ? j - 6 : (j == 12 ? 11 : pad));
-      m1 = w3 ? 1 : pad, m2 = w3 ? 2 : pad, m3 = j;
-    } else if (t < 169 + PS) {
-      const int rem = t - 169, i = rem / U, j = rem % U;
-      row = i, cf = A.Bcd + j, cs = U, kind = 1, out = rem;
-      m0 = 6, m1 = 7, m2 = 8, m3 = (j < 3 * NC) ? 9 + j % 3 : 0;
-    } else {
-      const int s = (t < NITEM) ? t - (169 + PS) : 0;
-      row = s, cf = A.x0, cs = 1, kind = (t < NITEM) ? 2 : 3, out = s;
-      m0 = s;
-      m1 = (s < 3) ? 6 : ((s < 5) ? s + 6 : ((s == 5) ? 11 : ((s == 11) ? 12 : 0)));
-      m2 = (s < 3) ? 7 : ((s == 5) ? 12 : 0);
-      m3 = (s < 3) ? 8 : 0;
-    }
-    it_p[u][0] = row * 13 + m0, it_p[u][1] = row * 13 + m1, it_p[u][2] = row * 13 + m2, it_p[u][3] = row * 13 + m3;
-    it_c[u][0] = cf + m0 * cs, it_c[u][1] = cf + m1 * cs, it_c[u][2] = cf + m2 * cs, it_c[u][3] = cf + m3 * cs;
-    it_kind[u] = kind, it_out[u] = out;
+    if (t < PS) chains_phi_item<NC>(it[u], t, A.Bcd);
+    else chains_e_item(it[u], (t >= PSE && t < NITEM) ? t - PSE : 0, A.x0);
   }
-  for (int k = 0; k <= h; ++k) {
-    const float *Pk = A.Apow + (k & 1) * 169;
-    float *Pn = A.Apow + ((k + 1) & 1) * 169;
+  if (tid < CH_SLOTS) {
+    ChainsPowerLane P;
+    chains_power_setup(P, tid < CH_LIVE ? tid : 0, A.Acd);
+    for (int k = 0; k < h; ++k) {
+      chains_power_step(P);
+      A.Pw[(k + 1) * CH_SLOTS + tid] = (tid < CH_LIVE) ? P.v[0] : chains_identity_slot(tid);
+    }
+  }
+  __syncthreads();
 #pragma unroll
-    for (int u = 0; u < NTRIP; ++u) {
-      float acc = ffma(Pk[it_p[u][0]], *it_c[u][0], 0.0f);
-      acc = ffma(Pk[it_p[u][1]], *it_c[u][1], acc);
-      acc = ffma(Pk[it_p[u][2]], *it_c[u][2], acc);
-      acc = ffma(Pk[it_p[u][3]], *it_c[u][3], acc);
-      const int kind = it_kind[u], out = it_out[u];
-      if (kind == 0) {
-        if (k < h) Pn[out] = acc;
-      } else if (kind == 1) {
-        if (k < h) {
-          A.Phi[k * PS + out] = acc;
+  for (int u = 0; u < NTRIP; ++u) {
+    const int t = tid + u * NT;
+    if (t < PS) {
+      for (int k0 = 0; k0 < h; k0 += KB) {
+        float p[KB][4];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+          for (int tt = 0; tt < 4; ++tt) p[kk][tt] = A.Pw[(k0 + kk) * CH_SLOTS + it[u].s[tt]];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+          const float acc = chains_chain4(p[kk], it[u].c);
+          if (k0 + kk < h) A.Phi[(k0 + kk) * PS + t] = acc;
         }
-      } else if (kind == 2 && k >= 1) {
-        const float xd = (out < 12) ? in_traj[12 * (k - 1) + out] : 0.0f;
-        A.e[13 * (k - 1) + out] = acc - xd;
+      }
+    } else if (t >= PSE && t < NITEM) {
+      const int s = t - PSE;
+      for (int k0 = 0; k0 < h; k0 += KB) {
+        float p[KB][4], xd[KB];
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+#pragma unroll
+          for (int tt = 0; tt < 4; ++tt) p[kk][tt] = A.Pw[(k0 + kk + 1) * CH_SLOTS + it[u].s[tt]];
+          xd[kk] = (s < 12) ? in_traj[12 * (k0 + kk) + s] : 0.0f;
+        }
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk) {
+          const float acc = chains_chain4(p[kk], it[u].c);
+          if (k0 + kk < h) A.e[13 * (k0 + kk) + s] = acc - xd[kk];
+        }
       }
     }
-    __syncthreads();
   }
+  __syncthreads();
 
   PROF_MARK(P_ASM);
   // ---------------- A5: g = 2 (B'S) e and H = 2(B'S B + alpha) (SolverMPC.cpp:569-570), indexed in reference order ------
