@@ -179,8 +179,8 @@ struct AdjointOut {
   double *grad_x0, *grad_traj, *grad_weights, *grad_alpha, *dir, *summary;  // [batch][13], [batch][h][12], [batch][12], [batch][6 nc], [batch][h][6 nc], [batch][2]
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
-// robot constants, mu_inst) and `forces`; it reads seed[batch][h][6 nc], writes `out` and nothing else.  nc = 2 (horizon <= 20) or 3
-// (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// robot constants, mu_inst) and `forces`; it reads seed[batch][h][6 nc], writes `out` and nothing else.  Shapes: derived_shape
+// (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_adjoint(int nc, const KernelArgs &args, double act_tol, const double *seed, const AdjointOut &out, hipStream_t stream);
 }  // namespace hmpc
 #endif

@@ -20,12 +20,13 @@
 // Every loop's trip count is fixed by (h, NC, the seeds of the tile) and the number of admitted normals: nothing iterates on data, so
 // NaN in one seed ends like any other and reaches no other seed.  No atomics, no inline assembly, no matrix cores.
 #pragma once
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_limit_adjoint.h"
 #include "hmpc_model_adjoint.h"
 #include "hmpc_pose_adjoint.h"
 
 namespace hmpc {
-constexpr int CADJ_NT = 128;  // lanes of the workgroup
+constexpr int CADJ_NT = DERIVED_NT;  // lanes of the workgroup
 
 // what adjoint_chain_of_instance keeps of its inputs and forms once for all seeds (LDS, or any memory all lanes see); the part that
 // must not overlay the binary32 inputs: filled by the first phase, which reads them
@@ -686,8 +687,8 @@ struct AdjointChainOut {  // slice 0, seed-major over args.batch; the detail mem
   double *grad_A, *grad_B, *grad_r, *costate, *grad_Fc, *grad_bound, *lambda, *nu;
 };
 // One launch per tile of 6 nc seeds over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch,
-// horizon, dt, f_max, the robot constants, mu_inst) and `forces`; it reads `in`, writes `out` and nothing else.  nc = 2 (horizon <= 20)
-// or 3 (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// horizon, dt, f_max, the robot constants, mu_inst) and `forces`; it reads `in`, writes `out` and nothing else.  Shapes: derived_shape
+// (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_adjoint_chain(int nc, const KernelArgs &args, double act_tol, double mass, const AdjointChainIn &in, int n_seeds,
                                 const AdjointChainOut &out, hipStream_t stream);
 }  // namespace hmpc

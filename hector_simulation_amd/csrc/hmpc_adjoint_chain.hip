@@ -3,9 +3,9 @@
 // hmpc_limit_adjoint.hip and hmpc_pose_adjoint.hip leave behind hmpc_select_adjoint_seed(s) -- with the record load, the assembly, the
 // forward chain, the tracking costate, the active set, the admitted normals and lambda formed once per tile of seeds.
 //
-// A launch of its own behind hmpc_solve_adjoint_multi (never part of hmpc_kernel, not a row of hmpc_variants.h).  Like its neighbours
-// it assembles by CALLING the solve kernel's own stage function -- stage_a_scalars of hmpc_kernel.h, behind the record load of A0, over
-// the smallest Smem that serves (NC, HMAX).  Everything behind the assembly is adjoint_chain_of_instance of hmpc_adjoint_chain.h.
+// A launch of its own behind hmpc_solve_adjoint_multi (never part of hmpc_kernel, not a row of hmpc_variants.h).  Like its neighbours it
+// assembles by CALLING the solve kernel's own stage function -- the common front of hmpc_derived.h.  Everything behind the assembly is
+// adjoint_chain_of_instance of hmpc_adjoint_chain.h.
 // Mapping: one workgroup of 128 threads per instance and tile; a tile is 6 NC seeds (the multi-seed adjoint's), worked off in sub-tiles
 // of as many seeds as static LDS below 64 KB holds beside the shared part (chain_sub_tile).  The passes' arrays and the seeds' overlay
 // the assembly's Smem, which is dead once the first phase has widened what the passes read.
@@ -14,20 +14,16 @@
 // matrix cores, nothing kept between launches.
 #include <hip/hip_runtime.h>
 
-#include "hmpc_kernel.h"
+#include "hmpc_derived.h"
 #include "hmpc_adjoint_chain.h"
 
 namespace hmpc {
 namespace {
 
-// the smallest Smem stage_a_scalars can be instantiated over (as hmpc_adjoint.hip)
-template <int HMAX, int NC>
-using CadjSmem = Smem<12, HMAX, CADJ_NT, 1, NC, 1>;
-
 template <int HMAX, int NC, int SUB>
 struct CadjLds {
   union {
-    CadjSmem<HMAX, NC> S;           // the assembly, and the first phase of adjoint_chain_of_instance
+    DerivedSmem<HMAX, NC> S;        // the assembly, and the first phase of adjoint_chain_of_instance
     ChainWork<NC, HMAX, SUB> Wk;    // the passes and the sub-tile's seeds
   } o;
   ChainKeep<NC, HMAX> Kp;
@@ -45,35 +41,21 @@ constexpr int chain_sub_tile() {
 
 // seeds s0 .. s0 + ns - 1 of the launch's n_seeds; in and out point at slice 0
 template <int HMAX, int NC>
-__global__ __launch_bounds__(CADJ_NT) void hmpc_adjoint_chain_kernel(KernelArgs args, double act_tol, double mass, AdjointChainIn in, int s0, int ns,
-                                                                     AdjointChainOut out) {
+__global__ __launch_bounds__(DERIVED_NT) void hmpc_adjoint_chain_kernel(KernelArgs args, double act_tol, double mass, AdjointChainIn in, int s0, int ns,
+                                                                          AdjointChainOut out) {
   using RL = RecLayout<NC>;
-  constexpr int U = 6 * NC, NT = CADJ_NT, SUB = chain_sub_tile<HMAX, NC>();
+  constexpr int U = 6 * NC, NT = DERIVED_NT, SUB = chain_sub_tile<HMAX, NC>();
   __shared__ CadjLds<HMAX, NC, SUB> L;
   static_assert(sizeof(CadjLds<HMAX, NC, SUB>) <= 64 * 1024, "static LDS of one workgroup");
   auto &S = L.o.S;
-  const int tid = threadIdx.x, inst = blockIdx.x, h = args.horizon;
-  if (inst >= args.batch || h > HMAX || args.stride > (int)sizeof(S.u.a.rec) || ns < 1 || ns > U) return;  // uniform
-  {
-    // stage A0 as hmpc_kernel has it: the record, one coalesced burst into LDS (restated as in hmpc_predict.hip, for the reason given there)
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(args.records + (size_t)inst * (size_t)args.stride);
-    const int nwords = args.stride >> 2;
-    for (int t = tid; t < nwords; t += NT) S.u.a.rec[t] = src[t];
-  }
-  for (int t = tid; t < U * h; t += NT) L.u[t] = args.forces[(size_t)inst * U * h + t];
-  __syncthreads();
-  Prof prof;
-  stage_a_scalars<12, HMAX, NT, 1, NC, 1>(S, args, inst, h, prof);  // (ends with a barrier)
+  const int inst = blockIdx.x, h = args.horizon;
+  if (ns < 1 || ns > U) return;  // uniform
+  if (!derived_front(S, L.u, args)) return;  // uniform
   const auto &A = S.u.a;
-  const float *rf = reinterpret_cast<const float *>(A.rec);
-  const unsigned char *gait = reinterpret_cast<const unsigned char *>(A.rec + RL::NF + 12 * h);
-  if (tid < NC) L.cap[tid] = (NC == 3 && tid == 2) ? rf[RL::FMH] : args.f_max;
-  if (tid == NT - 1) {  // the body rotation, as stage A2 forms it
-    float R[9], Rt[9];
-    quat_to_R(rf + RL::Q, R, Rt);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) L.R[k] = R[k];
-  }
+  const float *rf = derived_record_floats(S);
+  const unsigned char *gait = derived_gait(S, h);
+  derived_fill_caps(S, args, L.cap);
+  derived_fill_rotation(S, L.R);
   __syncthreads();
   const size_t i = (size_t)inst, nb = (size_t)args.batch, hz = (size_t)h, s = (size_t)s0 * nb;
   const size_t nrec = (size_t)RL::NF + 12 * hz, nls = (size_t)10 * NC * hz;
@@ -98,19 +80,10 @@ hipError_t launch_adjoint_chain(int nc, const KernelArgs &args, double act_tol, 
       !in.grad_alpha || !out.grad_record || !out.grad_frames || !out.grad_rpy || !out.grad_params || !out.grad_limits || !out.limit_summary ||
       !args.forces || !args.records)
     return hipErrorInvalidValue;
-  const int shape = (nc == 2 && args.horizon <= 10) ? 0 : (nc == 2 && args.horizon <= 20) ? 1 : (nc == 3 && args.horizon <= 10) ? 2 : -1;
-  if (shape < 0) return hipErrorInvalidValue;
-  const dim3 grid(args.batch), block(CADJ_NT);
-  const int tile = 6 * nc;
-  for (int s0 = 0; s0 < n_seeds; s0 += tile) {
-    const int ns = (n_seeds - s0 < tile) ? n_seeds - s0 : tile;
-    if (shape == 0) hipLaunchKernelGGL((hmpc_adjoint_chain_kernel<10, 2>), grid, block, 0, stream, args, act_tol, mass, in, s0, ns, out);
-    else if (shape == 1) hipLaunchKernelGGL((hmpc_adjoint_chain_kernel<20, 2>), grid, block, 0, stream, args, act_tol, mass, in, s0, ns, out);
-    else hipLaunchKernelGGL((hmpc_adjoint_chain_kernel<10, 3>), grid, block, 0, stream, args, act_tol, mass, in, s0, ns, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  const dim3 grid(args.batch), block(DERIVED_NT);
+  return for_derived_seed_tiles(nc, args.horizon, n_seeds, [&](auto H, auto C, int s0, int ns) {
+    hipLaunchKernelGGL((hmpc_adjoint_chain_kernel<H(), C()>), grid, block, 0, stream, args, act_tol, mass, in, s0, ns, out);
+  });
 }
 
 }  // namespace hmpc

@@ -24,11 +24,12 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_margins.h"
 #include "hmpc_record.h"
 
 namespace hmpc {
-constexpr int CERT_NT = 128;  // threads per workgroup (one workgroup per instance)
+constexpr int CERT_NT = DERIVED_NT;  // threads per workgroup (one workgroup per instance)
 constexpr int CERT_WAVES = CERT_NT / 64;
 constexpr int CERT_CLASSES = 4;  // stationarity, complementarity, primal violation, gradient scale
 constexpr int CERT_WHERE = 2;    // positions of the first two
@@ -363,7 +364,7 @@ struct CertificateOut {
   int32_t *where;                           // [batch][2]
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
-// robot constants, mu_inst) and `forces`; it writes `out` and nothing else.  nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else:
+// robot constants, mu_inst) and `forces`; it writes `out` and nothing else.  Shapes: derived_shape (hmpc_derived_shape.h); anything else:
 // hipErrorInvalidValue, nothing launched.
 hipError_t launch_certificate(int nc, const KernelArgs &args, double act_tol, const CertificateOut &out, hipStream_t stream);
 // out[batch] from summary[batch][4] and ceil[3]; penalty_in may be nullptr or out.

@@ -35,12 +35,13 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_certificate.h"
 #include "hmpc_margins.h"
 #include "hmpc_record.h"
 
 namespace hmpc {
-constexpr int FB_NT = 128;  // threads per workgroup (one workgroup per instance); lane 64 keeps the pivot minimum
+constexpr int FB_NT = DERIVED_NT;  // threads per workgroup (one workgroup per instance); lane 64 keeps the pivot minimum
 static_assert(FB_NT > 64, "a lane of a second wave");
 constexpr int FB_SUMMARY = 2;
 constexpr double FB_DEPENDENT = 1e-12;
@@ -548,7 +549,7 @@ struct FeedbackOut {
   int32_t *free_dims;                 // [batch][h]
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
-// robot constants, mu_inst) and `forces`; it writes `out` and nothing else.  nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else:
+// robot constants, mu_inst) and `forces`; it writes `out` and nothing else.  Shapes: derived_shape (hmpc_derived_shape.h); anything else:
 // hipErrorInvalidValue, nothing launched.
 hipError_t launch_feedback(int nc, const KernelArgs &args, double act_tol, const FeedbackOut &out, hipStream_t stream);
 // One launch over the batch: wrench[batch][6 nc], worst_slack[batch] from the gains in `gains`, the records of `args` (the solved ones),

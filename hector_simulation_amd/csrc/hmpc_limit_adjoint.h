@@ -32,10 +32,11 @@
 // two solutions in registers; G one lane per non-zero entry (48 NC); the chain rules on lanes 0 .. 2 (mu, lt, lh) and 64 .. 64 + NC - 1
 // (caps), the three maxima on lanes 32 .. 34.  No atomics, no inline assembly, no matrix cores.
 #pragma once
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_feedback.h"
 
 namespace hmpc {
-constexpr int LADJ_NT = 128;    // lanes of the workgroup
+constexpr int LADJ_NT = DERIVED_NT;    // lanes of the workgroup
 constexpr int LADJ_SUMMARY = 3;
 constexpr int LADJ_SWING = 7;   // `held` of a swing leg-step (a stance leg-step admits 0 .. 6)
 
@@ -308,7 +309,7 @@ struct LimitAdjointOut {
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
 // robot constants, mu_inst) and `forces`; it reads dir[batch][h][6 nc] (what hmpc_solve_adjoint wrote) and seed[batch][h][6 nc], writes
-// `out` and nothing else.  nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// `out` and nothing else.  Shapes: derived_shape (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_limit_adjoint(int nc, const KernelArgs &args, double act_tol, const double *dir, const double *seed, const LimitAdjointOut &out,
                                 hipStream_t stream);
 }  // namespace hmpc

@@ -20,10 +20,11 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_record.h"
 
 namespace hmpc {
-constexpr int MARGINS_NT = 128;  // threads per workgroup (one workgroup per instance)
+constexpr int MARGINS_NT = DERIVED_NT;  // threads per workgroup (one workgroup per instance)
 constexpr int MARGINS_WAVES = MARGINS_NT / 64;
 constexpr int MARGIN_CLASSES = 6;  // friction, Mx, line contact, Fz floor, Fz cap, friction headroom fraction
 constexpr int PENALTY_NT = 256;
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(NT) void margin_penalty_kernel(const double *summar
 namespace hmpc {
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
 // robot constants, mu_inst) and `forces`; it writes slack[batch][horizon][nc][10], summary[batch][6] (binary64) and where[batch][6] and
-// nothing else.  nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// nothing else.  Shapes: derived_shape (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_margins(int nc, const KernelArgs &args, double *slack, double *summary, int32_t *where, hipStream_t stream);
 // out[batch] from summary[batch][6] and floor[6]; penalty_in may be nullptr or out.
 hipError_t launch_margin_penalty(const double *summary, const double floor[MARGIN_CLASSES], const double *penalty_in, double *out, int batch,

@@ -35,8 +35,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
+
 namespace hmpc {
-constexpr int MADJ_NT = 128;     // lanes of the workgroup
+constexpr int MADJ_NT = DERIVED_NT;     // lanes of the workgroup
 constexpr int MADJ_PARAMS = 4;   // grad_params: mass, inertia 0 .. 2
 constexpr int MADJ_COSTATE = 26; // costate: c_1[13], d_1[13]
 
@@ -227,8 +229,8 @@ struct ModelAdjointOut {
   double *grad_A, *grad_B, *grad_r, *grad_params, *costate;  // [batch][13][13], [batch][13][6 nc], [batch][3][nc], [batch][4], [batch][2][13]
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, the robot
-// constants, mu_inst) and `forces`; it reads dir[batch][h][6 nc] (what hmpc_solve_adjoint wrote), writes `out` and nothing else.  nc = 2
-// (horizon <= 20) or 3 (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// constants, mu_inst) and `forces`; it reads dir[batch][h][6 nc] (what hmpc_solve_adjoint wrote), writes `out` and nothing else.  Shapes:
+// derived_shape (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_model_adjoint(int nc, const KernelArgs &args, double mass, const double *dir, const ModelAdjointOut &out, hipStream_t stream);
 }  // namespace hmpc
 #endif

@@ -40,10 +40,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_record.h"
 
 namespace hmpc {
-constexpr int PADJ_NT = 128;  // lanes of the workgroup
+constexpr int PADJ_NT = DERIVED_NT;  // lanes of the workgroup
 
 // the staged upstream gradients, the partial results and the staged outputs (LDS, or any memory all lanes see)
 template <int NC, int HMAX>
@@ -322,7 +323,7 @@ struct PoseAdjointOut {
   double *grad_record, *grad_frames, *grad_rpy;  // [batch][NF + 12 h], [batch][1 + nc][9], [batch][3]
 };
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, the robot
-// constants, mu_inst); it reads `in`, writes `out` and nothing else.  nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else:
+// constants, mu_inst); it reads `in`, writes `out` and nothing else.  Shapes: derived_shape (hmpc_derived_shape.h); anything else:
 // hipErrorInvalidValue, nothing launched.
 hipError_t launch_pose_adjoint(int nc, const KernelArgs &args, const PoseAdjointIn &in, const PoseAdjointOut &out, hipStream_t stream);
 }  // namespace hmpc

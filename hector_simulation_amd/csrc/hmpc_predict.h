@@ -3,14 +3,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hmpc_derived_shape.h"  // DERIVED_NT
 #include "hmpc_kernel_args.h"
 
 namespace hmpc {
-constexpr int PREDICT_NT = 128;  // threads per workgroup (one workgroup per instance)
+constexpr int PREDICT_NT = DERIVED_NT;  // threads per workgroup (one workgroup per instance)
 
 // One launch over the batch on `stream`.  Of `args` the kernel reads what stage A reads (records, stride, batch, horizon, dt, f_max, the
 // robot constants) and `forces`; it writes states[batch][horizon][13] (binary32) and cost[batch][2] (binary64) and nothing else.
-// nc = 2 (horizon <= 20) or 3 (horizon <= 10); anything else: hipErrorInvalidValue, nothing launched.
+// Shapes: derived_shape (hmpc_derived_shape.h); anything else: hipErrorInvalidValue, nothing launched.
 hipError_t launch_predict(int nc, const KernelArgs &args, float *states, double *cost, hipStream_t stream);
 
 }  // namespace hmpc

@@ -2,9 +2,8 @@
 //
 // The solve kernel optimises over x_{i+1} = Acd x_i + Bcd u_i and leaves only the forces; this kernel rolls the same model out over
 // whatever the force buffer holds.  It is a launch of its own (never part of hmpc_kernel, not a row of hmpc_variants.h) and it
-// assembles by CALLING the solve kernel's own stage function -- stage_a_scalars of hmpc_kernel.h, behind the record load of A0, instantiated
-// over the smallest Smem that serves (NC, HMAX) -- so that x0, Acd, Bcd, the weights and the trajectory are the very binary32
-// values the solve used, robot constants (hmpc_params) included.
+// assembles by CALLING the solve kernel's own stage function -- the common front of hmpc_derived.h -- so that x0, Acd, Bcd, the weights
+// and the trajectory are the very binary32 values the solve used, robot constants (hmpc_params) included.
 //
 // Arithmetic (fixed: tests/test_gpu_prediction.py restates it in numpy).  Per instance, U = 6 NC, state order rpy, position,
 // angular velocity, velocity, gravity constant (SolverMPC.cpp:420):
@@ -23,20 +22,15 @@
 // Traffic: the record and 6 NC h floats in (coalesced bursts), 13 h floats and 2 doubles out.  No atomics, no inline assembly.
 #include <hip/hip_runtime.h>
 
-#include "hmpc_kernel.h"
+#include "hmpc_derived.h"
 #include "hmpc_predict.h"
 
 namespace hmpc {
 namespace {
 
-// the smallest Smem stage_a_scalars can be instantiated over: 12 reduced variables (two leg-steps: Smem wants an even count; the
-// swing-elimination tables of larger instances are simply not filled, nothing here reads them), a working set of one row
-template <int HMAX, int NC>
-using PredictSmem = Smem<12, HMAX, PREDICT_NT, 1, NC, 1>;
-
 template <int HMAX, int NC>
 struct PredictLds {
-  PredictSmem<HMAX, NC> S;
+  DerivedSmem<HMAX, NC> S;
   double x[2][16];            // x_i, un-rounded, ping-pong
   double part[16 + 6 * NC];   // per-state / per-component partial costs
   float u[6 * NC * HMAX];     // the instance's slot of the force buffer
@@ -44,26 +38,16 @@ struct PredictLds {
 };
 
 template <int HMAX, int NC>
-__global__ __launch_bounds__(PREDICT_NT) void hmpc_predict_kernel(KernelArgs args, float *states, double *cost) {
+__global__ __launch_bounds__(DERIVED_NT) void hmpc_predict_kernel(KernelArgs args, float *states, double *cost) {
   using RL = RecLayout<NC>;
-  constexpr int U = 6 * NC, NT = PREDICT_NT;
+  constexpr int U = 6 * NC, NT = DERIVED_NT;
   __shared__ PredictLds<HMAX, NC> L;
+  static_assert(sizeof(PredictLds<HMAX, NC>) <= 64 * 1024, "static LDS of one workgroup");
   auto &S = L.S;
   const int tid = threadIdx.x, inst = blockIdx.x, h = args.horizon;
-  if (inst >= args.batch || h > HMAX) return;  // uniform
-  {
-    // stage A0 as hmpc_kernel has it: the record, one coalesced burst into LDS.  (Three lines restated: in hmpc_kernel they are not a
-    // function, and moving them into one changes the machine code of four safe variants -- profiles/r09/isa_hash.txt, README there)
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(args.records + (size_t)inst * args.stride);
-    const int nwords = args.stride >> 2;
-    for (int t = tid; t < nwords; t += NT) S.u.a.rec[t] = src[t];
-  }
-  for (int t = tid; t < U * h; t += NT) L.u[t] = args.forces[(size_t)inst * U * h + t];
-  __syncthreads();
-  Prof prof;
-  stage_a_scalars<12, HMAX, NT, 1, NC, 1>(S, args, inst, h, prof);  // (ends with a barrier)
+  if (!derived_front(S, L.u, args)) return;  // uniform
   const auto &A = S.u.a;
-  const float *rf = reinterpret_cast<const float *>(A.rec);
+  const float *rf = derived_record_floats(S);
 
   if (tid >= 64 && tid < 64 + U) {  // force cost, one component per lane
     const int c = tid - 64;
@@ -118,12 +102,10 @@ __global__ __launch_bounds__(PREDICT_NT) void hmpc_predict_kernel(KernelArgs arg
 
 hipError_t launch_predict(int nc, const KernelArgs &args, float *states, double *cost, hipStream_t stream) {
   if (args.batch < 1 || args.horizon < 1 || !states || !cost || !args.forces || !args.records) return hipErrorInvalidValue;
-  const dim3 grid(args.batch), block(PREDICT_NT);
-  if (nc == 2 && args.horizon <= 10) hipLaunchKernelGGL((hmpc_predict_kernel<10, 2>), grid, block, 0, stream, args, states, cost);
-  else if (nc == 2 && args.horizon <= 20) hipLaunchKernelGGL((hmpc_predict_kernel<20, 2>), grid, block, 0, stream, args, states, cost);
-  else if (nc == 3 && args.horizon <= 10) hipLaunchKernelGGL((hmpc_predict_kernel<10, 3>), grid, block, 0, stream, args, states, cost);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  const dim3 grid(args.batch), block(DERIVED_NT);
+  return for_derived_shape(nc, args.horizon, [&](auto H, auto C) {
+    hipLaunchKernelGGL((hmpc_predict_kernel<H(), C()>), grid, block, 0, stream, args, states, cost);
+  });
 }
 
 }  // namespace hmpc

@@ -8,8 +8,10 @@ What a refactor of hmpc_kernel.h that must not change the product (macro removal
 with: the kernel's instructions as llvm-objdump prints them (addresses and symbol-relative branch targets stripped), hashed
 per kernel symbol.  Two builds with the same hash run the same instructions.  --diff pairs kernels across a rename: an old
 row whose name is gone is matched to a new kernel with the same hash and instruction count; only what stays unmatched is
-CHANGED / NEW / MISSING.  --unit adds the kernels of another translation unit of csrc/ (hmpc_predict.hip, hmpc_select.hip,
-hmpc_margins.hip, hmpc_certificate.hip, the builder kernels of hmpc_builder.hip) to the listing."""
+CHANGED / NEW / MISSING.  --unit adds the kernels of another translation unit of csrc/ (any unit of build.HOST_SOURCES: hmpc_front.hip,
+hmpc_select.hip, the builder kernels of hmpc_builder.hip, the ten units over csrc/hmpc_derived.h -- hmpc_predict.hip, hmpc_margins.hip,
+hmpc_certificate.hip, hmpc_feedback.hip, hmpc_adjoint.hip, hmpc_adjoint_multi.hip, hmpc_model_adjoint.hip, hmpc_limit_adjoint.hip,
+hmpc_pose_adjoint.hip, hmpc_adjoint_chain.hip) to the listing."""
 import concurrent.futures
 import hashlib
 import os

@@ -37,7 +37,7 @@ for line in out.splitlines():
         short = re.sub(r"^void hmpc::", "", short).replace("(hmpc::KernelArgs)", "")
         if "true" not in short or "--all" in sys.argv:
             print(f"{short:64s} vgpr {row.get('vgpr'):>3} agpr {row.get('agpr'):>3} spill {row.get('spill'):>3} "
-                  f"scratch {row.get('scratch'):>3} B  occupancy {row.get('occ')}")
+                  f"scratch {row.get('scratch'):>3} B  occupancy {row.get('occ')}  lds {row.get('lds')}")
         name = None
 if "error" in out:
     print(out[-3000:])
