@@ -1279,8 +1279,14 @@ int hmpc_get_device_rollout_sweep(hmpc_handle *h, void **ticks_final, double **c
  * Reference oddities KEPT: the timer subtracts the constant dt_update = _dt = 0.001 per update whatever the tick's length; a leg whose sub-phase
  * is exactly 0 is not in swing on that tick; the touchdown heuristic is not the plant's (1.75, 0.1, clamp 0.3, vWorld * swingTimes); the IK does
  * not invert the leg's forward kinematics at the toe (DESIGN.md section 4.25 says by how much); HMPC_TICK_FALLEN is not looked at.
- * DEVIATIONS, both documented in DESIGN.md section 4.25: (1) tau of the command is always the tick's J' f_ff (device_tau) -- the reference
- * leaves a stale feedforwardForce on the single tick where a leg is neither in swing nor in stance; (2) a leg whose stance lasts the whole
+ * DEVIATIONS, both documented in DESIGN.md section 4.25: (1) tau of the command is always the tick's J' f_ff (device_tau).  The reference
+ * differs on one tick per leg and cycle, the first tick of the leg's stance step (cur % per == tk.gait_offsets[j] * c.ticks_per_step): step 0
+ * of the MPC table already has leg j in stance there and the solve gives it a force, but its swing sub-phase is sd / sd = exactly 1, "in
+ * swing", so setDesiredJointState writes feedforwardForce << 0, the swing branch of run() sets nothing and updateCommand commands
+ * tau = J' 0 = 0 for that leg -- measured on the executed reference (tests/test_swing_update_reference.py: ticks 0, 25, 50 of a 51-tick
+ * walking cycle).  Where the rounding of phase - so puts that tick an ulp past the swing (sub-phase 0, contact sub-phase 0) the leg is
+ * neither in swing nor in stance and the reference leaves the feedforwardForce of the tick before, the swing leg's 0: the same command.
+ * On every other tick a swing leg has no force in the solve and both give 0; (2) a leg whose stance lasts the whole
  * horizon has sd = 0 and the reference forms 0 / 0 at phase 0: a NaN that only ever meets `> 0`; here it is +0.0, the same "not in swing".
  *
  * struct hmpc_swing_state: one per instance, in HBM, owned by the caller, carried from tick to tick.  All-zero bytes with first_swing = {1, 1}

@@ -21,6 +21,9 @@
  * oracle/_ref/libcaller_ref.so = GaitGenerator.cpp + ConvexMPCLocomotion.cpp + LegController.cpp (+ FootSwingTrajectory.cpp,
  * DesiredCommand.cpp) compiled unmodified (tests/test_caller_reference.py: tables and records bit for bit, wrench bit for
  * bit, Jacobian within one ulp of 1.0).
+ * oracle/_ref/libswing_ref.so = the same caller-side sources + src/common/SwingLegController.cpp compiled unmodified, driven by
+ * oracle/swing_ref_shim.cpp: the swing update of csrc/hmpc_swing.h (timer, touchdown point, first-swing capture, Bezier target,
+ * computeIK, gains, whole ticks to LowlevelCmd) is pinned to it (tests/test_swing_update_reference.py, tests/test_gpu_swing_reference.py).
  *
  * Pinned arithmetic ("HMPC-A1"): IEEE binary32, round-to-nearest-even, no implicit
  * contraction; every matrix contraction is a k-ascending fmaf chain started at +0; trigonometry is evaluated

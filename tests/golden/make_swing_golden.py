@@ -2,8 +2,9 @@
 
 Provenance: oracle/_ref/libcaller_ref.so = ConvexMPC/GaitGenerator.cpp + src/common/LegController.cpp (+ the rest of the caller) compiled
 unmodified from the reference checkout against the Eigen stand-in oracle/mini_eigen (recipe oracle/Makefile; what the shim supplies:
-oracle/caller_ref_shim.cpp).  The reference's SwingLegController.cpp itself does not compile against that stand-in (norm(), asDiagonal(),
-the sized VectorXd constructor), so the pins are the two pieces of it that do: the swing sub-phase and the leg's foot position.
+oracle/caller_ref_shim.cpp).  These are the two pieces the swing update takes from those files: the swing sub-phase and the leg's foot
+position.  The reference's SwingLegController.cpp itself is executed by oracle/_ref/libswing_ref.so and recorded by
+tests/golden/make_swing_update_golden.py (timer, touchdown point, first-swing capture, Bezier target, computeIK, gains, whole ticks).
 
 Run where the reference checkout is (oracle/Makefile's REF):  python tests/golden/make_swing_golden.py
 

@@ -18,6 +18,13 @@ H = 10
 PI3, PI = 3.14159, 3.141592653589793
 TRIG_MEASURED = 2.8199664825478976e-14
 TRIG_TOL = 4 * TRIG_MEASURED
+# the largest |this mirror - the reference's own SwingLegController.cpp| (tests/golden/swing_update_ref.npz) in what passes through
+# trigonometry or pow, over the gait cycles and the IK rows of tests/swing_update_cases.py: pow(x, 2) / pow(x, 0.5) against x * x / sqrt and
+# libm's last bits.  Measured and printed by tests/test_swing_update_reference.py, which holds this mirror to four times it and the kernel to
+# TRIG_TOL + four times it.  It is 2^-54: on this libm the mirror is the reference to the last bit almost everywhere, and four times it is one
+# ulp at 1.0, less than an ulp of a q_des near -1.4 pi (8.9e-16) -- so the MIRROR's tolerance amounts to bit for bit, and a libm whose sin /
+# cos / asin / acos differ in a last bit will fail the mirror's tests (not the kernel's, whose TRIG_TOL is 1.1e-13).  Re-measure there.
+REF_MEASURED = 5.551115123125783e-17
 F0_MIN = 1e-3  # |foot_des_to_hip_roll[0]| below which q_des[2] is left out of the tolerance comparison
 
 
@@ -44,6 +51,11 @@ def swing_struct(c: dict):
         else:
             setattr(s, k, v)
     return s
+
+
+def sqrt(x):
+    """IEEE sqrt: a negative argument gives NaN (math.sqrt raises)"""
+    return math.sqrt(x) if x >= 0 else float("nan")
 
 
 def clamp1(v):
@@ -117,9 +129,11 @@ def trajectory(p0, pf, height, swing):
     return pDes, vDes
 
 
-def ik(pFoot_b, c, j, q2, q3, flip_side=False, flip_knee=False, info=None):
+def ik(pFoot_b, c, j, q2, q3, flip_side=False, flip_knee=False, pi3=False, info=None):
     """step 7.  ``flip_side`` / ``flip_knee``: two WRONG variants (the lateral offset on the other side; the knee bending the other way) that
-    the geometry test must tell from the right one.  ``info``: a dict that receives f and whether a clamp was active."""
+    the geometry test must tell from the right one; ``pi3``: a third, PI3 where the three offsets have PI (8e-7 rad), which only the executed
+    reference tells (tests/test_swing_update_reference.py).  ``info``: a dict that receives f and whether a clamp was active."""
+    off = PI3 if pi3 else PI
     sideK = -1.0 if j == 0 else 1.0
     if flip_side:
         sideK = -sideK
@@ -130,7 +144,7 @@ def ik(pFoot_b, c, j, q2, q3, flip_side=False, flip_knee=False, info=None):
     dh, L = c["ik_horizontal"], c["ik_link"]
     m = dyz * dyz - dh * dh
     dv = math.sqrt(m if 0.00001 < m else 0.00001)
-    dxz = math.sqrt(d3 * d3 - dh * dh)
+    dxz = sqrt(d3 * d3 - dh * dh)
     r1, r2 = dxz / (2.0 * L), dv / dxz
     a1, a2 = clamp1(r1), clamp1(r2)
     div = abs(f[0])
@@ -144,18 +158,24 @@ def ik(pFoot_b, c, j, q2, q3, flip_side=False, flip_knee=False, info=None):
     if flip_knee:
         out[3] = -out[3]
     out[4] = -q3 - q2
-    out[2] = out[2] - 0.3 * PI
-    out[3] = out[3] + 0.6 * PI
-    out[4] = out[4] - 0.3 * PI
+    out[2] = out[2] - 0.3 * off
+    out[3] = out[3] + 0.6 * off
+    out[4] = out[4] - 0.3 * off
     if info is not None:
         info["f"] = f
         info["clamped"] = any(clamp1(r) != r for r in (r1, r2, r3, r4, r5)) or not 0.00001 < m
     return out
 
 
-def update(ticks, state, c, h=H, tau=None):
+WRONG = ("flip_side", "flip_knee", "pi3", "swing_len_dur1", "timer_dtmpc")
+
+
+def update(ticks, state, c, h=H, tau=None, wrong=()):
     """One launch: ``c['updates']`` updates per leg.  Returns (cmd MOTOR_CMD_DTYPE[nb], new state, detail [nb, 2, 16]); the inputs are left
-    unchanged."""
+    unchanged.  ``wrong``: names of ``WRONG`` -- deliberately wrong variants of this mirror (never of the product) that the reference test
+    must tell from the right one: the three of ``ik``; ``swing_len_dur1``: h - durations[1] as the swing length (the reference: gait->_swing =
+    h - durations[0]); ``timer_dtmpc``: the timer loses dtMPC per update (the reference: the constant _dt = 0.001)."""
+    assert all(w in WRONG for w in wrong)
     nb = len(ticks)
     st = np.array(state, dtype=interface.SWING_STATE_DTYPE, copy=True)
     cmd = np.zeros(nb, dtype=interface.MOTOR_CMD_DTYPE)
@@ -180,9 +200,9 @@ def update(ticks, state, c, h=H, tau=None):
             rh = [R[k] * hy[0] + R[3 + k] * hy[1] + R[6 + k] * hy[2] for k in range(3)]
             for _ in range(c["updates"]):
                 if first:  # 4
-                    timer = c["dtMPC"] * float(h - dur0)
+                    timer = c["dtMPC"] * float(h - (int(tk["gait_durations"][1]) if "swing_len_dur1" in wrong else dur0))
                 else:
-                    timer = timer - c["dt_update"]
+                    timer = timer - (c["dtMPC"] if "timer_dtmpc" in wrong else c["dt_update"])
                     if timer <= 0:
                         first = 1
                 for a in range(2):  # 5
@@ -205,7 +225,7 @@ def update(ticks, state, c, h=H, tau=None):
                 e = [vDes[k] * 0.0 - v[k] for k in range(3)]
                 pFoot_b = [(R[3 * k] * d[0] + R[3 * k + 1] * d[1] + R[3 * k + 2] * d[2]) + c["hip_width_offset"][j][k] for k in range(3)]
                 vFoot_b = [R[3 * k] * e[0] + R[3 * k + 1] * e[1] + R[3 * k + 2] * e[2] for k in range(3)]
-                st["q_des"][i, sl] = ik(pFoot_b, c, j, q[2], q[3])  # 7, 8
+                st["q_des"][i, sl] = ik(pFoot_b, c, j, q[2], q[3], **{w: True for w in wrong if w in WRONG[:3]})  # 7, 8
                 cmd["Kp"][i, sl], cmd["Kd"][i, sl] = c["kp"], c["kd"]
             cmd["q"][i, sl] = st["q_des"][i, sl]
             if tau is not None:
@@ -234,6 +254,18 @@ def drift(t, rng, k):
     t["vWorld"] += rng.normal(0.0, 0.01, t["vWorld"].shape)
     t["leg_q"] += rng.normal(0.0, 0.01, t["leg_q"].shape)
     return t
+
+
+def ankle_rows(seed=0, n=4000):
+    """(cfg, p [n, 3], leg [n], rows [n, 6] = pFoot_b, leg, q2, q3): body-frame foot positions p = hipYaw + a box reachable without any clamp
+    of the IK, alternating legs -- the rows of the ankle identity (tests/test_swing_physics.py) and of the IK's reference pins"""
+    c = default_swing()
+    rng = np.random.default_rng(seed)
+    p = np.stack([rng.uniform(-0.15, 0.15, n), rng.uniform(-0.08, 0.08, n), rng.uniform(-0.45, -0.28, n)], axis=1)
+    leg = np.arange(n) % 2
+    p = p + np.array(c["hip_yaw"])[leg]
+    rows = np.concatenate([p + np.array(c["hip_width_offset"])[leg], leg[:, None].astype(np.float64), np.full((n, 1), 0.5), np.full((n, 1), -1.0)], axis=1)
+    return c, p, leg, rows
 
 
 def mid_swing_state(ticks, seed):

@@ -69,14 +69,7 @@ def test_bezier_closed_forms_in_the_host_build(exe, tmp_path):
             assert (d[:, leg, 7:10] == 0.0).all()
 
 
-def ankle_rows(seed=0, n=4000):
-    c = sm.default_swing()
-    rng = np.random.default_rng(seed)
-    p = np.stack([rng.uniform(-0.15, 0.15, n), rng.uniform(-0.08, 0.08, n), rng.uniform(-0.45, -0.28, n)], axis=1)
-    leg = np.arange(n) % 2
-    p = p + np.array(c["hip_yaw"])[leg]
-    rows = np.concatenate([p + np.array(c["hip_width_offset"])[leg], leg[:, None].astype(np.float64), np.full((n, 1), 0.5), np.full((n, 1), -1.0)], axis=1)
-    return c, p, leg, rows
+ankle_rows = sm.ankle_rows  # (the box of body-frame foot positions, shared with tests/swing_update_cases.py)
 
 
 def ankle_residual(c, p, leg, q_des):
